@@ -6,7 +6,13 @@
 
 A "step" is one pass of the hot path over one batch: Diffusion.sample() = Philox start noise + 400 denoise steps + the
 final device->host copy of x, inputs (E, layers) already resident in HBM.  One process per GPU; the batch
-dimension is sharded with no data-path collective (weak scaling: 64 showers per GPU).  Rank 0 prints ONE JSON line.
+dimension is sharded with no data-path collective (weak scaling: 64 showers per GPU).  Rank 0 prints ONE JSON line;
+`ms_per_step` in it is the wall time of one timed step.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (sample: `showers`; --mode train: `loss`, and the
+`params` / `grads` the step left, flattened).  Inputs, weights and the device noise stream are seeded, so two builds run with the
+same arguments can be compared output for output -- to fp32 rounding, not bit for bit: the convolution autotune picks its tilings
+by timing them in each process (two runs of one build: 5e-7 relative L2 on Dataset-2).
 
 Extra legs, rank 0 at N = 1 only:
   * roofline: one eager denoise step with HIP events around every launch (cd_profile_*), pricing the dominant kernel
@@ -238,6 +244,23 @@ def roofline_leg(model, cfg, batch, E, layers):
     return roof, breakdown
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: what the timed path returned in its last step, one `<name>.npy` per array (float64 stays float64, all else
+    float32), `<name>_rank<r>.npy` per rank when sharded.  Above 64 MB in all, every array keeps the same fixed, seeded sample of
+    rows along its first axis, so that two builds run with the same arguments can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def train_roofline_leg(model, step, data, E, layers, B, step_ms):
     """Roofline entry of the training step (outside the timed region).  Algorithmic work = 3 x the forward's FLOPs (forward, input
     gradients, weight gradients: every convolution / linear map runs three times), the forward's FLOPs being what the launchers of
@@ -310,6 +333,11 @@ def train_bench(args, model, cfg, E, layers, rank, world):
     ar_ms = max_over_ranks(sum(a.elapsed_time(b) for a, b in events) / max(1, args.steps))
     nbytes = model.engine().grad_layout()[1] * 4
     step_ms = 1e3 * dt / args.steps
+    if args.dump_outputs:  # before the roofline leg, which steps the model again
+        params = [p for p in model.parameters() if p.grad is not None]
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1).cpu().numpy(),
+                                         "params": torch.cat([p.detach().reshape(-1) for p in params]).cpu().numpy(),
+                                         "grads": torch.cat([p.grad.reshape(-1) for p in params]).cpu().numpy()}, rank, world)
     roof = None
     if rank == 0 and world == 1 and not args.no_extra:
         roof = train_roofline_leg(model, step, data, E, layers, B, step_ms)
@@ -349,7 +377,11 @@ def main():
     ap.add_argument("--no-clocks", action="store_true", help="do not sample the GPU's clocks / power during the timed region")
     ap.add_argument("--mode", default="sample", choices=["sample", "train"],
                     help="train: BASELINE configs[2], a step = one training iteration (fwd + bwd + grad all-reduce + Adam)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (sample: showers; train: loss, params, grads)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     dflt = CONFIG_DEFAULTS.get(args.config, {"batch": 64, "sample_steps": 400, "sampler": None})
     if args.batch is None:
         args.batch = TRAIN_BATCH if args.mode == "train" else dflt["batch"]
@@ -429,6 +461,8 @@ def main():
         smp.th.join()
         gpu_state = dict(clock_trace.phase_summary(smp, "timed", drop_head=0.1), source=smp.source)
     assert np.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"showers": out}, rank, world)
 
     result = {
         "metric": "sampled showers/sec (Dataset-2, 400-step DDIM)"

@@ -1,10 +1,11 @@
 """CPU: bench.py's multi-GPU entry.  `python bench.py --gpus N` without a launcher must start N ranks (or fail), never print
-an N-GPU line measured on one GPU."""
+an N-GPU line measured on one GPU.  Its argument checks and the --dump-outputs writer."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -73,3 +74,26 @@ def test_launcher_relays_the_ranks_json_line(tmp_path, monkeypatch):
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line == {"value": 2.0, "collective": {"backend": "gloo", "ranks": 2}}
+
+
+def test_steps_below_one_is_refused():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per returned array; above the cap, the same seeded rows from run to run."""
+    showers = np.arange(64 * 3 * 5, dtype=np.float32).reshape(64, 3, 5)
+    dbl = np.linspace(0.0, 1.0, 64)
+    bench.dump_outputs(str(tmp_path / "a"), {"showers": showers, "scalar": np.float16(2.5).reshape(1), "dbl": dbl}, 0, 1)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("showers", "scalar", "dbl")}
+    assert got["showers"].dtype == np.float32 and np.array_equal(got["showers"], showers)
+    assert got["scalar"].dtype == np.float32 and got["dbl"].dtype == np.float64 and np.array_equal(got["dbl"], dbl)
+    bench.dump_outputs(str(tmp_path / "r"), {"showers": showers}, 1, 2)
+    assert np.array_equal(np.load(tmp_path / "r" / "showers_rank1.npy"), showers)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", showers.nbytes // 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"showers": showers}, 0, 1)
+    b, c = np.load(tmp_path / "b" / "showers.npy"), np.load(tmp_path / "c" / "showers.npy")
+    assert b.nbytes <= showers.nbytes // 4 and b.shape[1:] == showers.shape[1:] and np.array_equal(b, c)
+    assert all(any(np.array_equal(row, s) for s in showers) for row in b)

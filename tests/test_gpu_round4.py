@@ -141,7 +141,7 @@ def test_workspace_cache_follows_precision_and_switches(monkeypatch):
 
 
 @pytest.mark.parametrize("parts", [2, 4])
-def test_cooperating_workgroups_attention_equals_the_single_workgroup_form(parts):
+def test_cooperating_workgroups_attention_equals_the_single_workgroup_form(parts, tmp_path):
     """attn_coop_kernel (CD_ATTN_COOP: a sample's voxels dealt to several co-operating workgroups with two in-launch barriers)
     against the one-workgroup-per-sample attn_small_kernel at Dataset-2's level-1 grids (736 voxels, 32 and 64 channels, batch a
     multiple of 8 so that a sample's workgroups share an XCD) -- run in a child process, CD_ATTN_COOP is read once.  The two forms
@@ -170,7 +170,7 @@ np.save(sys.argv[1], y.cpu().numpy())
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
     for tag, env in (("single", {}), ("coop", {"CD_ATTN_COOP": str(parts)})):
-        path = f"/tmp/coop_{parts}_{tag}.npy"
+        path = str(tmp_path / f"coop_{parts}_{tag}.npy")
         e = dict(os.environ, **env)
         subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests")), path], check=True, env=e, timeout=600)
         outs[tag] = np.load(path)
