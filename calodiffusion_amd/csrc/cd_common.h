@@ -140,12 +140,19 @@ struct ConvFusion {
     int* done = nullptr;
   } gn_out;
 };
-// device word holding max |x| (bit pattern) of the tensor last passed to launch_absmax_bits; valid in stream order
-const unsigned* launch_absmax_bits(const float* x, size_t n, hipStream_t s);
-// the zeroed word for a producer that tracks max |x| itself while writing x; claimed by the next launch_absmax_bits(x)
-unsigned* absmax_word_fresh(const float* x, hipStream_t s);
-// forget which tensor the word describes (end of the convolution backward that computed it)
-void absmax_note_drop();
+// Zeroed device words for max |x| bit patterns (launch_absmax_bits, launch_gn_backward), handed out in order from a region the
+// caller owns and has zeroed on the stream: a training step's sits beside its demb in the workspace, a cd_op_* primitive's in its
+// own scratch
+struct AbsmaxWords {
+  unsigned* next = nullptr;
+  unsigned* end = nullptr;
+  unsigned* take() {
+    CD_REQUIRE(next && next < end, "internal: out of max-|x| words");
+    return next++;
+  }
+};
+// max |x| (bit pattern) into a word taken from `words`; valid in stream order
+const unsigned* launch_absmax_bits(const float* x, size_t n, AbsmaxWords* words, hipStream_t s);
 // 2^s and 2^-s for a tensor whose max |x| has bit pattern mb: s = 10 - floor(log2 max)
 __host__ __device__ inline void pow2_scale_for(unsigned mb, float* scale, float* inv) {
   const int e = (int)((mb >> 23) & 0xff) - 127;
@@ -279,11 +286,10 @@ void launch_gn_finalize(const float* part, int units, const float* gamma, const 
 // ---- backward (kernels_bwd.hip) ---------------------------------------------------------------------------------
 size_t wgrad_partial_floats(int64_t out_vox, int batch, bool per_sample, int A, int Bc, int T);
 // Deferred slot reductions of the weight gradients (training step).  Every launch_wgrad ends in a reduction of its per-workgroup
-// partials: ~28 MB read for a few hundred KB of dw whatever the level, 65 launches of 4-7 us per step.  While a queue is current
-// (wgrad_queue_set), launch_wgrad takes its partial buffer from the queue's own region instead of the caller's (which the caller
-// reuses for its next weight gradient) and records the reduction as a job; wgrad_queue_flush runs all of them in ONE launch (same
-// two-level fixed-order sum per output: deterministic).  A queue without room (region too small, job table full) simply leaves
-// the reduction where it was.
+// partials: ~28 MB read for a few hundred KB of dw whatever the level, 65 launches of 4-7 us per step.  Given a queue
+// (WgradAux::queue), launch_wgrad records the reduction as a job instead -- the caller keeps `partial` until the flush -- and
+// wgrad_queue_flush runs all of them in ONE launch (same two-level fixed-order sum per output: deterministic).  A full job table
+// is flushed on the spot.
 struct WgradReduceJob {
   const float* partial;
   float* dw;
@@ -295,27 +301,32 @@ struct WgradReduceQueue {
   WgradReduceJob job[kMax];
   int n = 0;
   unsigned blocks = 0;
-  float* base = nullptr;            // region the owner keeps until the flush
-  size_t cap = 0, used = 0;         // floats
-  size_t need = 0;                  // floats all requests of this pass asked for (the owner sizes the next pass's region by it)
 };
-void wgrad_queue_set(WgradReduceQueue* q);  // nullptr: reductions are launched where they arise
 void wgrad_queue_flush(WgradReduceQueue* q, hipStream_t s);
+// What a weight gradient takes from its caller besides the tensors (all optional): the queue its slot reduction joins, the words
+// its max-|x| passes fill (the fp16-pipe kernels rescale g and x by powers of two), and max |g| / max |x| where the caller has
+// measured them already (the input-gradient conv of the same backward)
+struct WgradAux {
+  WgradReduceQueue* queue = nullptr;
+  AbsmaxWords* words = nullptr;
+  const unsigned* gmax = nullptr;
+  const unsigned* xmax = nullptr;
+};
 // dW[a][b][tap] (or [b][a][tap] if transposed_out) = sum_{n,o} g[n][o][a] * x[n][in(o,tap)][xoff + b]; see kernels_bwd.hip
 void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int kh, int kw,
                   int sz, int sxy, int batch, bool per_sample, float* partial, float* dw, bool accumulate, bool transposed_out,
                   hipStream_t s, int b_total = 0, int b_off = 0,
                   // x is read through silu(coef[0] x + coef[1]) + coef[2] per (sample, channel) ([B][xld][4]): only where
                   // wgrad_x_norm_supported() says so (the fp16-pipe 3x3x3 kernel)
-                  const float* xcoef = nullptr);
+                  const float* xcoef = nullptr, const WgradAux& aux = WgradAux());
 bool wgrad_x_norm_supported(Dims3 dg, Dims3 dx, int kd, int kh, int kw, int sz, int sxy);
 // stride-1 3x3x3 weight gradient on the fp16 matrix pipe (kernels_wgrad16.hip); false = geometry not eligible
 bool wgrad_f16x2_eligible(Dims3 d);
 bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int xld, int xoff, Dims3 d, int batch, float* partial,
-                            unsigned* gmax_word, int* nblk_out, hipStream_t s, const float* xcoef = nullptr);
+                            const WgradAux& aux, int* nblk_out, hipStream_t s, const float* xcoef = nullptr);
 // the strided (KD, 4, 4) convs between the levels (and the transposed conv with the tensors' roles swapped): kernels_wgrad16.hip
 bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int sz,
-                                    int batch, float* partial, int max_slots, int* nblk_out, hipStream_t s);
+                                    int batch, float* partial, int max_slots, const WgradAux& aux, int* nblk_out, hipStream_t s);
 void launch_strided_dgrad_naive(const float* dy, const float* w, float* dx, int batch, int cin, int cout, Dims3 din, Dims3 dout,
                                 int kd, int sz, hipStream_t s);
 void launch_softmax32(const float* qkv, float* qs, int64_t rows, hipStream_t s);
@@ -357,7 +368,9 @@ struct GnParamJobs {
 };
 struct GnParamQueue {
   GnParamJobs jobs;
-  float* next_sums = nullptr;  // bump pointer into a region of gn_param_queue_floats(...) the caller keeps until the flush
+  float* sums = nullptr;       // region of the jobs' per-sample sums, kept by the caller until the flush: [sums, sums_end)
+  float* sums_end = nullptr;
+  float* next_sums = nullptr;  // bump pointer into it (back to `sums` after a flush)
 };
 void launch_gn_param_jobs(const GnParamJobs& jobs, hipStream_t s);
 void launch_gn_backward(const float* dy, const float* h, const float* coef, const float* stat, const float* gamma, float* dh,
@@ -367,7 +380,10 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
                         // gradient of a conv that adds into y): both fall out of the statistics pass, see kernels_bwd.hip
                         float* dbias = nullptr, float* dsumdy = nullptr,
                         // (optional) queue the batch reduction of the parameter gradients instead of launching it (training step)
-                        GnParamQueue* queue = nullptr);
+                        GnParamQueue* queue = nullptr,
+                        // (optional) a zeroed device word that receives max |dh| (bit pattern): the conv gradients that consume dh
+                        // rescale by it (WgradAux::gmax, ConvFusion::in_absmax) without a pass of their own
+                        unsigned* dh_absmax = nullptr);
 int gn_apply_blocks_per_sample(int batch, int channels, int64_t vox);
 // y = act(scale*x + shift) + add (+ residual; residual1/res_c0: shortcut read from a two-source channel concat);
 // part_out (optional): channel partials of y, [B][gn_apply_blocks_per_sample][C][2]
@@ -422,8 +438,10 @@ void launch_attn_small(const float* x, int C, const float* coef, const void* wqk
                        float scale, const float* bias, const float* out_gamma, const float* out_beta, float* y, float* ch_part,
                        int batch, int64_t vox, hipStream_t s, const GnDefer* defer, int* status = nullptr,
                        // capacity of partials ([B][max_parts][1088]) and ch_part ([B][max_parts][C][2]) in parts per sample: with
-                       // CD_ATTN_COOP the sample's voxels are dealt to up to that many co-operating workgroups
-                       int max_parts = 1);
+                       // CD_ATTN_COOP the sample's voxels are dealt to up to that many co-operating workgroups, which meet at
+                       // barriers on coop_sync ([kAttnCoopSamples][2] words the caller owns; null: no co-operative form)
+                       int max_parts = 1, unsigned* coop_sync = nullptr);
+constexpr int kAttnCoopSamples = 8192;
 // moments ([B][nsplit][1056], attn_moment_floats): pass 1 also accumulates the first and second moments of softmax(q), from which
 // pass 2 (given the same buffer and the closing GroupNorm's parameters) writes the BLOCK's output gn(y) + x directly -- no y
 // tensor, no channel sums, no gn_apply pass
@@ -634,7 +652,7 @@ size_t init_wgrad_partial_floats(int batch, int64_t vox, int cin, int cout);
 void launch_init_wgrad(const InitConvArgs& a, const float* g, float* part, float* dw, hipStream_t s);
 // the same through the general weight-gradient kernels (padded 32-channel input); scratch: init_wgrad_mfma_floats floats
 size_t init_wgrad_mfma_floats(int batch, int64_t vox, int cout);
-void launch_init_wgrad_mfma(const InitConvArgs& a, const float* g, float* scratch, float* dw, hipStream_t s);
+void launch_init_wgrad_mfma(const InitConvArgs& a, const float* g, float* scratch, float* dw, hipStream_t s, AbsmaxWords* words);
 // per-sample record the embedding backward leaves for the Linear weight gradients
 struct EmbedTapeLayout {
   int t_in, a1t, a2t, a1c, a2c, sc;      // inputs of the Linears (time: 1, q, half; cond: cond(copied), hidden, half; proj: 2*half)

@@ -49,7 +49,7 @@ struct AttnArgs {
   const float *out_gamma, *out_beta;  // attn_small_kernel: affine parameters of the closing GroupNorm(1, C)
   int* status;        // bit 0: an operand of the fp16-pipe products (normalised x, v, the folded output weights) left the fp16 range
   // attn_coop_kernel: the nsplit workgroups of a sample meet at two barriers inside the launch
-  unsigned* sync;     // [B][2] = {arrivals, generation}: zero once, self-resetting
+  unsigned* sync;     // [B][2] = {arrivals, generation}: zeroed before the launch, self-resetting
   int coop;           // the partials / channel sums read below were written by OTHER workgroups of this launch
   // moment form (MOM instances): pass 1 also emits, per partial, s'[d] = sum_n (softmax(q)[n][d] - 1/32) and the 32 x 32 matrix
   // S'[d][d'] = sum_n (softmax(q)[n][d] - 1/32)(softmax(q)[n][d'] - 1/32), from which pass 2 knows the statistics of its own
@@ -1019,7 +1019,7 @@ bool attn_small_eligible(int64_t vox) {
 }
 void launch_attn_small(const float* x, int C, const float* coef, const void* wqkv_f16x2, float* partials, const float* w_out,
                        float scale, const float* bias, const float* out_gamma, const float* out_beta, float* y, float* ch_part,
-                       int batch, int64_t vox, hipStream_t s, const GnDefer* defer, int* status, int max_parts) {
+                       int batch, int64_t vox, hipStream_t s, const GnDefer* defer, int* status, int max_parts, unsigned* coop_sync) {
   CD_REQUIRE(C == 32 || C == 64 || C == 96 || C == 128, "fused attention: 32..128 channels");
   CD_REQUIRE((vox * C) % 4 == 0, "fused attention: whole float4 rows");
   AttnArgs a{};
@@ -1038,18 +1038,14 @@ void launch_attn_small(const float* x, int C, const float* coef, const void* wqk
   const int64_t T = (vox + 31) / 32;
   int P = coop_env < max_parts ? coop_env : max_parts;
   while (P > 1 && ((int64_t)batch * P > 256 || T < 4 * P)) --P;
-  if (P > 1 && batch % 8 == 0 && status) {
+  if (P > 1 && batch % 8 == 0 && status && coop_sync) {
     int per = (int)((T + P - 1) / P);
     while (P > 1 && (int64_t)(P - 1) * per >= T) { --P; per = (int)((T + P - 1) / P); }  // (every part has a tile)
     if (P > 1) {
-      static unsigned* sync = nullptr;
-      static const int kSyncSamples = 8192;
-      if (!sync) {
-        CD_HIP(hipMalloc((void**)&sync, sizeof(unsigned) * 2 * kSyncSamples));
-        CD_HIP(hipMemset(sync, 0, sizeof(unsigned) * 2 * kSyncSamples));
-      }
-      CD_REQUIRE(batch <= kSyncSamples, "attention: batch too large for the co-operative form");
-      a.sync = sync; a.coop = 1; a.nsplit = P; a.tiles_per_wg = per;
+      CD_REQUIRE(batch <= kAttnCoopSamples, "attention: batch too large for the co-operative form");
+      // (cleared before every launch: a barrier that timed out cannot leave its counters to the next one)
+      CD_HIP(hipMemsetAsync(coop_sync, 0, sizeof(unsigned) * 2 * batch, s));
+      a.sync = coop_sync; a.coop = 1; a.nsplit = P; a.tiles_per_wg = per;
       const dim3 cgrid((unsigned)(batch * P));
       switch (C / 32) {
         case 1: hipLaunchKernelGGL(attn_coop_kernel<1>, cgrid, dim3(512), 0, s, a); break;

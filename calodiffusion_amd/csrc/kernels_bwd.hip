@@ -592,10 +592,6 @@ __global__ void __launch_bounds__(256) wgrad_reduce_jobs_kernel(WgradReduceJobs 
     *d = (j.flags & 1) ? *d + sum : sum;
   }
 }
-namespace {
-thread_local WgradReduceQueue* g_wq = nullptr;
-}
-void wgrad_queue_set(WgradReduceQueue* q) { g_wq = q; }
 void wgrad_queue_flush(WgradReduceQueue* q, hipStream_t s) {
   if (!q || q->n <= 0) return;
   WgradReduceJobs J;
@@ -606,22 +602,10 @@ void wgrad_queue_flush(WgradReduceQueue* q, hipStream_t s) {
   q->n = 0;
   q->blocks = 0;
 }
-// a partial buffer of the current queue (or nullptr: none current / no room); counts the request either way
-static float* wgrad_queue_alloc(size_t nfloats) {
-  WgradReduceQueue* q = g_wq;
-  if (!q) return nullptr;
-  nfloats = (nfloats + 63) & ~(size_t)63;
-  q->need += nfloats;
-  if (!q->base || q->used + nfloats > q->cap) return nullptr;
-  float* r = q->base + q->used;
-  q->used += nfloats;
-  return r;
-}
-// the reduction of `partial` (a buffer of the current queue) as a job; false if it has to be launched here
-static bool wgrad_queue_push(const float* partial, float* dw, int A, int Bc, int T, int nslots, bool accumulate, bool transposed_out,
-                             int b_total, int b_off, hipStream_t s) {
-  WgradReduceQueue* q = g_wq;
-  if (!q || !q->base || partial < q->base || partial >= q->base + q->cap) return false;
+// the reduction of `partial` as a job of q; false (no queue) if it has to be launched here
+static bool wgrad_queue_push(WgradReduceQueue* q, const float* partial, float* dw, int A, int Bc, int T, int nslots, bool accumulate,
+                             bool transposed_out, int b_total, int b_off, hipStream_t s) {
+  if (!q) return false;
   if (q->n == WgradReduceQueue::kMax) wgrad_queue_flush(q, s);  // (deeper networks than the shipped ones: flush and go on)
   WgradReduceJob& j = q->job[q->n++];
   j.partial = partial; j.dw = dw; j.A = A; j.Bc = Bc; j.T = T; j.nslots = nslots;
@@ -632,10 +616,10 @@ static bool wgrad_queue_push(const float* partial, float* dw, int A, int Bc, int
 }
 
 // the slot reduction of the 27- and 48-tap weight gradients (up to 256 partials, one per workgroup): two-level from 64 slots on
-static void launch_wgrad_reduce_slots(const float* partial, float* dw, int A, int Bc, int T, int nslots, bool accumulate,
-                                      bool transposed_out, int b_total, int b_off, hipStream_t s) {
+static void launch_wgrad_reduce_slots(WgradReduceQueue* q, const float* partial, float* dw, int A, int Bc, int T, int nslots,
+                                      bool accumulate, bool transposed_out, int b_total, int b_off, hipStream_t s) {
   const size_t total = (size_t)A * Bc * T;
-  if (wgrad_queue_push(partial, dw, A, Bc, T, nslots, accumulate, transposed_out, b_total, b_off, s)) return;
+  if (wgrad_queue_push(q, partial, dw, A, Bc, T, nslots, accumulate, transposed_out, b_total, b_off, s)) return;
   static const bool one_level = getenv("CD_WGRAD_REDUCE_1LEVEL") != nullptr;
   if (nslots >= 64 && !one_level)
     hipLaunchKernelGGL(wgrad_reduce1_kernel, dim3((unsigned)((total + 63) / 64), 1), dim3(256), 0, s, partial, dw, A, Bc, nslots,
@@ -701,14 +685,12 @@ bool wgrad_x_norm_supported(Dims3 dg, Dims3 dx, int kd, int kh, int kw, int sz, 
 
 void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int kh, int kw,
                   int sz, int sxy, int batch, bool per_sample, float* partial, float* dw, bool accumulate, bool transposed_out,
-                  hipStream_t s, int b_total, int b_off, const float* xcoef) {
+                  hipStream_t s, int b_total, int b_off, const float* xcoef, const WgradAux& aux) {
   CD_REQUIRE(A % 32 == 0 && Bc % 32 == 0, "wgrad: channel counts must be multiples of 32");
   CD_REQUIRE(!xcoef || (!per_sample && wgrad_x_norm_supported(dg, dx, kd, kh, kw, sz, sxy)),
              "wgrad: a normalised x operand is only read by the fp16-pipe 3x3x3 kernel");
+  CD_REQUIRE(!per_sample || !aux.queue, "wgrad: per-sample reductions are not queued");
   if (b_total <= 0) b_total = Bc;
-  if (!per_sample) {  // training step: a buffer that outlives the caller's, its reduction deferred (WgradReduceQueue)
-    if (float* qp = wgrad_queue_alloc(wgrad_partial_floats(dg.vox(), batch, false, A, Bc, kd * kh * kw))) partial = qp;
-  }
   WgradArgs a;
   a.g = g; a.x = x; a.A = A; a.Bc = Bc; a.xld = xld; a.xoff = xoff;
   a.Dg = dg.d; a.Hg = dg.h; a.Wg = dg.w; a.Dx = dx.d; a.Hx = dx.h; a.Wx = dx.w;
@@ -716,15 +698,13 @@ void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int x
   const int Tt = kd * kh * kw;
   if (Tt == 27 && sz == 1 && sxy == 1 && !per_sample && dg.vox() == dx.vox()) {
     // fp16 matrix pipe (f16x2), transposing LDS loads: kernels_wgrad16.hip
-    static unsigned* gmax_word = nullptr;
-    if (!gmax_word) CD_HIP(hipMalloc((void**)&gmax_word, 64));
     int nblk16 = 0;
     if (wgrad_f16x2_eligible(dg)) {
       char cat16[96];
       std::snprintf(cat16, sizeof cat16, "wgrad T27 C%dx%d n%ld", A, Bc, (long)dg.vox());
       prof::Scope scope16(cat16, s, 2.0 * 27 * A * Bc * (double)dg.vox() * batch, 4.0 * batch * (double)dg.vox() * (A + Bc));
-      CD_REQUIRE(try_launch_wgrad_f16x2(g, A, x, Bc, xld, xoff, dg, batch, partial, gmax_word, &nblk16, s, xcoef), "internal: wgrad f16x2");
-      launch_wgrad_reduce_slots(partial, dw, A, Bc, 27, nblk16, accumulate, transposed_out, b_total, b_off, s);
+      CD_REQUIRE(try_launch_wgrad_f16x2(g, A, x, Bc, xld, xoff, dg, batch, partial, aux, &nblk16, s, xcoef), "internal: wgrad f16x2");
+      launch_wgrad_reduce_slots(aux.queue, partial, dw, A, Bc, 27, nblk16, accumulate, transposed_out, b_total, b_off, s);
       return;
     }
   }
@@ -760,7 +740,7 @@ void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int x
       }
       hipLaunchKernelGGL(wgrad_flat_kernel<4>, dim3(nblk, tiles), dim3(64 * 7), lds, s, f);
       CD_HIP(hipGetLastError());
-      launch_wgrad_reduce_slots(partial, dw, A, Bc, 27, nblk, accumulate, transposed_out, b_total, b_off, s);
+      launch_wgrad_reduce_slots(aux.queue, partial, dw, A, Bc, 27, nblk, accumulate, transposed_out, b_total, b_off, s);
       return;
     }
   }
@@ -772,8 +752,8 @@ void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int x
     char cats[96];
     std::snprintf(cats, sizeof cats, "wgrad T%d C%dx%d n%ld", Ts, A, Bc, (long)dg.vox());
     prof::Scope scope_s(cats, s, 2.0 * Ts * A * Bc * (double)dg.vox() * batch, 4.0 * batch * ((double)dg.vox() * A + (double)dx.vox() * Bc));
-    if (try_launch_wgrad_strided_f16x2(g, A, dg, x, Bc, xld, xoff, dx, kd, sz, batch, partial, max_slots, &nblk, s)) {
-      launch_wgrad_reduce_slots(partial, dw, A, Bc, Ts, nblk, accumulate, transposed_out, b_total, b_off, s);
+    if (try_launch_wgrad_strided_f16x2(g, A, dg, x, Bc, xld, xoff, dx, kd, sz, batch, partial, max_slots, aux, &nblk, s)) {
+      launch_wgrad_reduce_slots(aux.queue, partial, dw, A, Bc, Ts, nblk, accumulate, transposed_out, b_total, b_off, s);
       return;
     }
   }
@@ -785,7 +765,7 @@ void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int x
     prof::Scope scope1(cat1, s, 2.0 * A * Bc * (double)dg.vox() * batch, 4.0 * batch * (double)dg.vox() * (A + Bc));
     if (try_launch_wgrad1x1(g, A, x, Bc, xld, xoff, dg.vox(), batch, per_sample, partial, cap_slots, &ns, s)) {
       const size_t total = (size_t)A * Bc;
-      if (!per_sample && wgrad_queue_push(partial, dw, A, Bc, 1, ns, accumulate, transposed_out, b_total, b_off, s)) return;
+      if (wgrad_queue_push(aux.queue, partial, dw, A, Bc, 1, ns, accumulate, transposed_out, b_total, b_off, s)) return;
       dim3 rg1((unsigned)((total + 63) / 64), per_sample ? batch : 1);
       hipLaunchKernelGGL(wgrad_reduce1_kernel, rg1, dim3(256), 0, s, partial, dw, A, Bc, ns, accumulate ? 1 : 0,
                          transposed_out ? 1 : 0, (size_t)ns * total, total, b_total, b_off);
@@ -1377,7 +1357,7 @@ void launch_gn_param_jobs(const GnParamJobs& jobs, hipStream_t s) {
 void launch_gn_backward(const float* dy, const float* h, const float* coef, const float* stat, const float* gamma, float* dh,
                         float* dgamma, float* dbeta, float* dadd, int dadd_ld, int batch, int channels, int64_t vox, int groups,
                         int silu, float* scratch, bool accumulate_params, hipStream_t s, float* dbias, float* dsumdy,
-                        GnParamQueue* queue) {
+                        GnParamQueue* queue, unsigned* dh_absmax) {
   CD_REQUIRE(channels % 4 == 0 && channels <= 256 && groups <= 64, "group norm backward: <= 256 channels, <= 64 groups");
   const int ns = gn_nsplit_for(vox, batch);
   float* part = scratch;                                         // [B][ns][C][4]
@@ -1388,7 +1368,9 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
     if (queue->jobs.n == GnParamJobs::kMax) {  // (deeper networks than the shipped ones: flush and go on)
       launch_gn_param_jobs(queue->jobs, s);
       queue->jobs.n = 0;
+      queue->next_sums = queue->sums;
     }
+    CD_REQUIRE(queue->next_sums + (size_t)batch * channels * 4 <= queue->sums_end, "gn backward: queued sums overflow their region");
     sums_bc = queue->next_sums;
     queue->next_sums += (size_t)batch * channels * 4;
     GnParamJob& j = queue->jobs.job[queue->jobs.n++];
@@ -1400,9 +1382,8 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
   // with 64 channels -- it took 35 us against the split form's 27, so the bound sits between the two)
   static const size_t small_max = getenv("CD_GN_BWD_SMALL_KB") ? (size_t)atoi(getenv("CD_GN_BWD_SMALL_KB")) * 1024 : 100 * 1024;
   if (!no_small && (size_t)vox * channels * 4 <= small_max && channels <= 128 && 512 % (channels >> 2) == 0) {
-    unsigned* amax_word = absmax_word_fresh(dh, s);
     hipLaunchKernelGGL(gn_bwd_small_kernel, dim3((unsigned)batch), dim3(512), 0, s, dy, h, coef, stat, gamma, dh, sums_bc, dadd, dadd_ld,
-                       channels, vox, groups, silu, amax_word);
+                       channels, vox, groups, silu, dh_absmax);
     if (!queue)
       hipLaunchKernelGGL(param_grad_from_samples_kernel, dim3((channels + 63) / 64), dim3(64), 0, s, sums_bc, batch, channels, dgamma,
                          dbeta, accumulate_params ? 1 : 0, dbias, dsumdy);
@@ -1430,9 +1411,8 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
   int bps = gn_apply_blocks_per_sample(batch, channels, vox);
   const int bps_cap = (bwd_wgs + batch - 1) / batch;
   if (fold.part && bps > bps_cap) bps = bps_cap < 1 ? 1 : bps_cap;
-  unsigned* amax_word = absmax_word_fresh(dh, s);  // zeroed; the consumer's launch_absmax_bits(dh) finds it instead of re-reading dh
   hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)(batch * bps)), dim3(256), 0, s, dy, h, coef, gcoef, dh, channels, vox, silu, bps,
-                     amax_word, fold);
+                     dh_absmax, fold);
   CD_HIP(hipGetLastError());
 }
 // out[v][c] = a[v][aoff + c] + (b ? b[v][boff + c] : 0)   (row strides lda / ldb / C): gradient fan-in, channel slices of
@@ -1890,7 +1870,7 @@ __global__ void init_extract_dw_kernel(const float* __restrict__ dw32, float* __
 size_t init_wgrad_mfma_floats(int batch, int64_t vox, int cout) {  // padded input + 32-wide gradient + slot partials
   return (size_t)batch * vox * 32 + (size_t)cout * 32 * 27 + 64 + wgrad_partial_floats(vox, batch, false, cout, 32, 27) + 128;
 }
-void launch_init_wgrad_mfma(const InitConvArgs& a, const float* g, float* scratch, float* dw, hipStream_t s) {
+void launch_init_wgrad_mfma(const InitConvArgs& a, const float* g, float* scratch, float* dw, hipStream_t s, AbsmaxWords* words) {
   CD_REQUIRE(a.cin <= 4 && a.cout % 32 == 0, "init conv wgrad: 1..4 input channels, 32 k output channels");
   const int64_t vox = a.dims.vox();
   float* xin = scratch;
@@ -1898,18 +1878,9 @@ void launch_init_wgrad_mfma(const InitConvArgs& a, const float* g, float* scratc
   float* part = dw32 + (((size_t)a.cout * 32 * 27 + 63) & ~(size_t)63);
   hipLaunchKernelGGL(init_pad_input_kernel, dim3((unsigned)((vox + 255) / 256), (unsigned)a.batch), dim3(256), 0, s, a, xin);
   CD_HIP(hipGetLastError());
-  {
-    // dw32 is read right below: this reduction cannot wait in a queue
-    WgradReduceQueue* const q = g_wq;
-    g_wq = nullptr;
-    try {
-      launch_wgrad(g, a.cout, a.dims, xin, 32, 32, 0, a.dims, 3, 3, 3, 1, 1, a.batch, false, part, dw32, false, false, s);
-    } catch (...) {
-      g_wq = q;
-      throw;
-    }
-    g_wq = q;
-  }
+  WgradAux aux;  // (no queue: dw32 is read right below)
+  aux.words = words;
+  launch_wgrad(g, a.cout, a.dims, xin, 32, 32, 0, a.dims, 3, 3, 3, 1, 1, a.batch, false, part, dw32, false, false, s, 0, 0, nullptr, aux);
   const int total = a.cout * a.cin * 27;
   hipLaunchKernelGGL(init_extract_dw_kernel, dim3((total + 255) / 256), dim3(256), 0, s, dw32, dw, a.cout, a.cin);
   CD_HIP(hipGetLastError());

@@ -858,74 +858,19 @@ __global__ void __launch_bounds__(512, 1) wgrad_strided_f16x2_kernel(WgradS16Arg
 
 }  // namespace
 
-// returns false when the geometry does not fit (caller falls back to the fp32 kernels).  gmax_word: a device word the
-// caller owns (zeroed here); `partial` sized by wgrad_partial_floats.
-namespace {
-unsigned* g_absmax_word = nullptr;
-const float* g_absmax_of = nullptr;  // tensor the word currently describes (stream order)
-size_t g_absmax_n = 0;               // ... and its element count (0: a producer's note, size unknown)
-}  // namespace
-namespace {
-bool g_absmax_fresh = false;  // the word was filled by the producer of g_absmax_of and has not been claimed yet
-}
-// A producer that can track max |x| while it writes x (gn_bwd_apply_kernel) takes the zeroed word here; the next
-// launch_absmax_bits call claims it if (and only if) it asks for the same tensor -- a later tensor at a recycled workspace
-// address can never match a stale note.
-// The words come from a ring that is zeroed as a whole when it wraps (a hipMemsetAsync per request was ~80 four-byte fills per
-// training step, 4 us each): a request takes the next word, still zero -- every launch that used the ring's previous round was
-// enqueued on the stream before the wrap's memset.
-namespace {
-constexpr int ABSMAX_RING = 4096;
-unsigned* g_absmax_ring = nullptr;
-int g_absmax_next = 0;
-unsigned* absmax_next_word(hipStream_t s) {
-  if (!g_absmax_ring) {
-    CD_HIP(hipMalloc((void**)&g_absmax_ring, sizeof(unsigned) * ABSMAX_RING));
-    CD_HIP(hipMemsetAsync(g_absmax_ring, 0, sizeof(unsigned) * ABSMAX_RING, s));
-    g_absmax_next = 0;
-  }
-  if (g_absmax_next == ABSMAX_RING) {
-    CD_HIP(hipMemsetAsync(g_absmax_ring, 0, sizeof(unsigned) * ABSMAX_RING, s));
-    g_absmax_next = 0;
-  }
-  return g_absmax_ring + g_absmax_next++;
-}
-}  // namespace
-unsigned* absmax_word_fresh(const float* x, hipStream_t s) {
-  g_absmax_word = absmax_next_word(s);
-  g_absmax_of = x;
-  g_absmax_n = 0;
-  g_absmax_fresh = true;
-  return g_absmax_word;
-}
-// The note is only good for the backward of ONE convolution: its owner drops it when that backward is enqueued, so a later tensor
-// at a recycled workspace address (or the same tensor rewritten in place) can never pick up a stale maximum.
-void absmax_note_drop() {
-  g_absmax_of = nullptr;
-  g_absmax_n = 0;
-  g_absmax_fresh = false;
-}
-const unsigned* launch_absmax_bits(const float* x, size_t n, hipStream_t s) {
-  if (g_absmax_fresh && g_absmax_of == x && g_absmax_word) {
-    g_absmax_fresh = false;
-    g_absmax_n = n;  // the note now has the consumer's size: the weight gradient of the same conv_backward re-uses it too
-                     // (it was left at 0, so every weight gradient behind a producer-tracked dy ran its own pass: 28 per step)
-    return g_absmax_word;
-  }
-  g_absmax_fresh = false;
+const unsigned* launch_absmax_bits(const float* x, size_t n, AbsmaxWords* words, hipStream_t s) {
   CD_REQUIRE(n % 4 == 0, "absmax: element count must be a multiple of 4");
-  g_absmax_word = absmax_next_word(s);
+  CD_REQUIRE(words, "internal: absmax pass without words");
+  unsigned* word = words->take();
   // one atomic per workgroup on ONE word: same-address atomics retire at ~12 ns each, so the 2048 workgroups this pass used to
   // launch spent 25 us in them whatever the tensor's size (rocprofv3, round 4: 35 calls x 25 us per training step).  256-512
   // workgroups with eight 16-byte loads in flight per thread stream a level-0 gradient (26 MB) in ~7 us.
   size_t blocks = (n / 4 + 256 * 8 - 1) / (256 * 8);
   if (blocks < 1) blocks = 1;
   if (blocks > 512) blocks = 512;
-  hipLaunchKernelGGL(absmax_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, n / 4, g_absmax_word);
+  hipLaunchKernelGGL(absmax_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, n / 4, word);
   CD_HIP(hipGetLastError());
-  g_absmax_of = x;
-  g_absmax_n = n;
-  return g_absmax_word;
+  return word;
 }
 
 static size_t wgrad16_lds(Dims3 d) {
@@ -959,8 +904,9 @@ bool wgrad_f16x2_eligible(Dims3 d) {
   static const int min_pv = getenv("CD_WGRAD16_MINPV") ? atoi(getenv("CD_WGRAD16_MINPV")) : 8;
   return d.d >= 1 && d.h * d.w >= min_pv && wgrad16_lds(d) <= 160 * 1024;
 }
+// returns false when the geometry does not fit (caller falls back to the fp32 kernels); `partial` sized by wgrad_partial_floats
 bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int xld, int xoff, Dims3 d, int batch, float* partial,
-                            unsigned* gmax_word, int* nblk_out, hipStream_t s, const float* xcoef) {
+                            const WgradAux& aux, int* nblk_out, hipStream_t s, const float* xcoef) {
   if (!wgrad_f16x2_eligible(d)) return false;
   const size_t lds = wgrad16_lds(d);
   Wgrad16Args f;
@@ -969,11 +915,8 @@ bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int x
   f.units_per_sample = (d.d + WG_NZ - 1) / WG_NZ;
   f.total_units = f.units_per_sample * batch;
   f.partial = partial; f.tilesB = Bc / 32;
-  // max |dy|: reuse the word if the caller (conv_backward) already computed it for this tensor
-  // (same pointer AND same size, noted since the last absmax_note_drop(): the dx convolution of this very backward)
-  const size_t gn = (size_t)batch * d.vox() * A;
-  f.gmax_bits = (g_absmax_of == g && g_absmax_n == gn && g_absmax_word) ? g_absmax_word : launch_absmax_bits(g, gn, s);
-  (void)gmax_word;
+  // max |dy|: the caller's word if it has one (conv_backward: the dx convolution of this very backward measured it)
+  f.gmax_bits = aux.gmax ? aux.gmax : launch_absmax_bits(g, (size_t)batch * d.vox() * A, aux.words, s);
   const int tiles = (A / 32) * (Bc / 32);
   int nblk = 256 / tiles;
   if (nblk < 32) nblk = 32;
@@ -1029,7 +972,7 @@ bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int x
 // the fine grid (x).  max_slots: capacity of `partial` in [A x Bc x T]-float slots.  Returns false when it does not apply (the
 // caller runs the f32-MFMA kernel).
 bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int sz,
-                                    int batch, float* partial, int max_slots, int* nblk_out, hipStream_t s) {
+                                    int batch, float* partial, int max_slots, const WgradAux& aux, int* nblk_out, hipStream_t s) {
   static const bool off = getenv("CD_NO_WGRAD16") != nullptr || getenv("CD_NO_WGRAD16_STRIDED") != nullptr;
   if (off || (kd != 3 && kd != 4) || dx.h < 2 || A % 32 || Bc % 32 || xld % 4 || xoff % 4) return false;
   // the coarse grid must be the strided conv's output of the fine one (padding 1 everywhere, circular in phi)
@@ -1050,15 +993,9 @@ bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float
   f.units_per_sample = (dg.d + NZ - 1) / NZ;
   f.total_units = f.units_per_sample * batch;
   f.partial = partial; f.tilesB = Bc / 32;
-  // both operands are rescaled from their maxima; the one the caller's input-gradient conv already measured is re-used (it must
-  // be looked up BEFORE the other one's pass replaces the note)
-  const size_t gn = (size_t)batch * dg.vox() * A, xn = (size_t)batch * dx.vox() * xld;
-  auto noted = [&](const float* p, size_t n) { return (g_absmax_of == p && g_absmax_n == n && g_absmax_word) ? g_absmax_word : nullptr; };
-  const unsigned* wg = noted(g, gn);
-  const unsigned* wx = noted(x, xn);
-  if (!wg) wg = launch_absmax_bits(g, gn, s);
-  if (!wx) wx = launch_absmax_bits(x, xn, s);
-  f.gmax_bits = wg; f.xmax_bits = wx;
+  // both operands are rescaled from their maxima; the one the caller's input-gradient conv already measured is re-used
+  f.gmax_bits = aux.gmax ? aux.gmax : launch_absmax_bits(g, (size_t)batch * dg.vox() * A, aux.words, s);
+  f.xmax_bits = aux.xmax ? aux.xmax : launch_absmax_bits(x, (size_t)batch * dx.vox() * xld, aux.words, s);
   const int tiles = (A / 32) * (Bc / 32);
   int nblk = 128 / tiles;  // x two tap groups = one round of the 256 CUs
   if (nblk < 16) nblk = 16;

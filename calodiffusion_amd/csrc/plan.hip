@@ -32,7 +32,7 @@ struct WeightEntry {
   size_t pk3_off = 0;  // split-bf16 image of 3x3x3 convs (floats into the arena; 0 = none)
   size_t grad_off = 0; // floats into the flat gradient buffer of cd_train_step
   bool set = false;
-  // input-gradient images of the training step (dgrad_images below), floats into CdPlan::dg_arena; dg_mode 0 = none
+  // input-gradient images of the training step (dgrad_images below), floats into the step's image block; dg_mode 0 = none
   int dg_mode = 0;
   size_t dg_pk_off = 0, dg_pk3_off = 0;
   bool dg_1x1 = false;  // a 1x1 conv kept raw for the forward (attention to_out: folded per sample) whose backward wants the image
@@ -166,23 +166,25 @@ struct CdPlan {
   std::vector<PackJob> pack_jobs;
   PackJob* d_pack_jobs = nullptr;
   // training: the re-packed (channel-transposed, tap-flipped) weight images of every convolution's input gradient, made by ONE
-  // job list per step (two launches) instead of two or three pack launches inside each conv_backward (118 launches per step)
-  float* dg_arena = nullptr;
-  // training: region for the weight gradients' per-workgroup partials while their reductions are queued (WgradReduceQueue); sized by
-  // the first step's requests (that step reduces where it always did), re-sized if a later step asks for more (a larger batch)
-  float* wq_region = nullptr;
-  size_t wq_cap = 0;
+  // job list per step (two launches) instead of two or three pack launches inside each conv_backward (118 launches per step).
+  // The images live in a block of the step's workspace (dg_floats, at dg_images during a step); the device job list points into
+  // the block at dg_jobs_at and is re-pointed when a step's block lies elsewhere (dg_jobs: host copy)
+  size_t dg_floats = 0;
+  std::vector<PackJob> dg_jobs;
   PackJob* d_dg_jobs = nullptr;
-  int n_dg_jobs = 0;
+  const float* dg_jobs_at = nullptr;
+  const float* dg_images = nullptr;
   DgImg dg(int i) const {
     DgImg g;
     const WeightEntry& w = weights[i];
-    if (dg_arena && w.dg_mode) {
-      g.pk = dg_arena + w.dg_pk_off;
-      if (w.dg_mode != 1) g.pk3 = dg_arena + w.dg_pk3_off;
+    if (dg_images && w.dg_mode) {
+      g.pk = dg_images + w.dg_pk_off;
+      if (w.dg_mode != 1) g.pk3 = dg_images + w.dg_pk3_off;
     }
     return g;
   }
+  // barrier words of the co-operative attention (launch_attn_small, CD_ATTN_COOP): [kAttnCoopSamples][2]
+  unsigned* d_attn_sync = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   hipGraphExec_t graph_exec_chunk = nullptr;  // kEmbedChunk consecutive steps as ONE graph (same key): no gap between their launches
   struct GraphKey {
@@ -421,6 +423,7 @@ void build_plan(CdPlan* p) {
   CD_HIP(hipMemset(p->d_counter, 0, sizeof(int) * 4));
   p->status_word = p->d_counter + 2;
   CD_HIP(hipMalloc((void**)&p->d_stepvals, sizeof(float) * 8));
+  CD_HIP(hipMalloc((void**)&p->d_attn_sync, sizeof(unsigned) * 2 * kAttnCoopSamples));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -433,7 +436,27 @@ struct Run {
   int groups;
   int* status = nullptr;  // device word for sticky range flags (cd_plan_status), or null
   GnParamQueue* gq = nullptr;  // training step: the GroupNorm layers' parameter-gradient reductions, flushed once at the end
+  // training step: the weight gradients' slot reductions, flushed once at the end (null: each runs where it arises), and the
+  // workspace blocks of their partials, held until that flush
+  WgradReduceQueue* wq = nullptr;
+  std::vector<float*> wq_held;
+  AbsmaxWords amax;  // zeroed words for max |x| (launch_absmax_bits, launch_gn_backward); none in a dry run
   bool dry() const { return ws->dry(); }
+  unsigned* amax_word() { return dry() ? nullptr : amax.take(); }
+  // partial buffer of one launch_wgrad; with a queue it stays taken until the flush, so one buffer per queued reduction
+  float* wgrad_part(size_t floats) {
+    float* part = ws->get<float>(floats);
+    if (wq) wq_held.push_back(part);
+    return part;
+  }
+  void release_wgrad_part(float* part) {
+    if (!wq) ws->release(part);
+  }
+  WgradAux wgrad_aux(const unsigned* gmax = nullptr, const unsigned* xmax = nullptr) {
+    WgradAux a;
+    a.queue = wq; a.words = &amax; a.gmax = gmax; a.xmax = xmax;
+    return a;
+  }
 };
 
 // weights of one block resolved to device pointers (conv weights in packed MFMA layout)
@@ -452,6 +475,7 @@ struct AttnP {
   int c = 0;
   const float *ng = nullptr, *nb = nullptr, *qkv = nullptr, *ow = nullptr, *ob = nullptr, *gg = nullptr, *gb = nullptr;
   const void* qkv16 = nullptr;  // f16x2 image of to_qkv (fused attention kernels)
+  unsigned* coop_sync = nullptr;  // the plan's barrier words of the co-operative form (launch_attn_small), or null
 };
 
 ResP resolve(const CdPlan* p, const ResW& w, const float* emb) {
@@ -473,6 +497,7 @@ AttnP resolve(const CdPlan* p, const AttnW& w) {
   a.ng = p->raw(w.ng); a.nb = p->raw(w.nb); a.qkv = p->packed(w.qkv); a.ow = p->raw(w.ow); a.ob = p->raw(w.ob);
   a.qkv16 = (const char*)p->packed3(w.qkv) + packed_bf16x3_bytes(w.c, 96, 1);
   a.gg = p->raw(w.gg); a.gb = p->raw(w.gb);
+  a.coop_sync = p->d_attn_sync;
   return a;
 }
 
@@ -677,7 +702,7 @@ float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpa
     ypart = ws->get<float>((size_t)r.B * cap * C * 2);
     if (!r.dry() && single) {
       launch_attn_small(x, C, coefn, w.qkv16, part, w.ow, 0.17677669529663689f /* 32^-1/2 */, w.ob, w.gg, w.gb, y, ypart, r.B, vox,
-                        r.s, dnp, r.status, cap);
+                        r.s, dnp, r.status, cap, w.coop_sync);
     } else if (!r.dry()) {
       launch_attn_kv_context(x, C, coefn, w.qkv16, part, r.B, vox, nsp, r.s, dnp, r.status, momb);
       if (sep_combine) {
@@ -752,11 +777,12 @@ void bias_grad(Run& r, const float* dy, int C, int64_t vox, float* db) {
 //   dw: torch layout (cout, c0+c1, taps);  db: (cout) or null.   w_raw: torch-layout weights (device).
 // img (optional): the input gradient's weight images already packed for this step (CdPlan::dg); without them they are packed here.
 // xcoef (optional, single-source x0 only): the conv's input was silu(coef[0] x0 + coef[1]) + coef[2] (see launch_wgrad)
+// dy_max (optional): max |dy| in a device word (the GroupNorm backward that wrote dy filled it); else measured here where needed
 void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, const float* w_raw, const float* dy, float* dx,
                    float* dw, float* db, int cout, const ConvGeom& g, const DgImg* img = nullptr, const float* xcoef = nullptr,
                    // dx = (input gradient) + dx_add, a tensor shaped like dx, where the kernel that runs can add it in its
                    // epilogue (3x3x3 stride 1 on the fp16 pipe): *dx_added says whether it did
-                   const float* dx_add = nullptr, int* dx_added = nullptr) {
+                   const float* dx_add = nullptr, int* dx_added = nullptr, const unsigned* dy_max = nullptr) {
   Arena* ws = r.ws;
   const int cin = c0 + c1, T = g.kd * g.kh * g.kw;
   const bool pre = img && img->pk;
@@ -782,7 +808,8 @@ void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, con
         ConvGeom gd{g.out, g.in, g.kd, g.kh, g.kw, 1, 1, 1};
         ConvFusion fu;
         fu.wpk_bf16x3 = pre ? img->pk3 : wp3;
-        fu.in_absmax = launch_absmax_bits(dy, (size_t)r.B * g.out.vox() * cout, r.s);  // also serves the weight gradient below
+        if (!dy_max) dy_max = launch_absmax_bits(dy, (size_t)r.B * g.out.vox() * cout, &r.amax, r.s);  // (serves the weight gradient too)
+        fu.in_absmax = dy_max;
         fu.add_src = dx_add; fu.add_done = dx_added;
         launch_conv_mfma(dy, cout, nullptr, 0, pre ? img->pk : wp, nullptr, dx, r.B, cin, gd, r.s, fu);
       }
@@ -801,22 +828,24 @@ void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, con
           launch_pack_weights(w_raw, wp, cin, cout, T, true, r.s);
           launch_pack_weights_f16x2(w_raw, wp16, cin, cout, T, r.s, true, false);
         }
-        const unsigned* amax = launch_absmax_bits(dy, (size_t)r.B * g.out.vox() * cout, r.s);
+        if (!dy_max) dy_max = launch_absmax_bits(dy, (size_t)r.B * g.out.vox() * cout, &r.amax, r.s);
         launch_conv_transpose_mfma(dy, cout, pre ? img->pk : wp, nullptr, dx, r.B, cin, g.out, g.in, g.kd, g.sz, r.s,
-                                   pre ? img->pk3 : wp16, r.status, amax);
+                                   pre ? img->pk3 : wp16, r.status, dy_max);
       }
       if (wp16) ws->release(wp16);
       if (wp) ws->release(wp);
     }
   }
-  float* part = ws->get<float>(wgrad_partial_floats(g.out.vox(), r.B, false, cout, c0 > c1 ? c0 : c1, T));
-  if (!r.dry()) {
-    CD_REQUIRE(!xcoef || !c1, "conv backward: a normalised input has one source");
-    launch_wgrad(dy, cout, g.out, x0, c0, c0, 0, g.in, g.kd, g.kh, g.kw, g.sz, g.sh, r.B, false, part, dw, false, false, r.s, cin, 0, xcoef);
-    if (c1) launch_wgrad(dy, cout, g.out, x1, c1, c1, 0, g.in, g.kd, g.kh, g.kw, g.sz, g.sh, r.B, false, part, dw, false, false, r.s, cin, c0);
-    absmax_note_drop();  // max |dy| served this backward only
+  CD_REQUIRE(!xcoef || !c1, "conv backward: a normalised input has one source");
+  const float* xs[2] = {x0, x1};
+  const int cs[2] = {c0, c1};
+  for (int k = 0; k < 2 && cs[k]; ++k) {
+    float* part = r.wgrad_part(wgrad_partial_floats(g.out.vox(), r.B, false, cout, cs[k], T));
+    if (!r.dry())
+      launch_wgrad(dy, cout, g.out, xs[k], cs[k], cs[k], 0, g.in, g.kd, g.kh, g.kw, g.sz, g.sh, r.B, false, part, dw, false, false, r.s,
+                   cin, k ? c0 : 0, xcoef, r.wgrad_aux(dy_max));
+    r.release_wgrad_part(part);
   }
-  ws->release(part);
   if (db) bias_grad(r, dy, cout, g.out.vox(), db);
 }
 
@@ -826,6 +855,7 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
   Arena* ws = r.ws;
   const int T = kz * 16;
   const bool pre = img && img->pk;
+  const unsigned* dy_max = nullptr;  // (measured by the input gradient's conv; the weight gradient reads dy as its x operand)
   // Odd output phi extent (output_padding 1 along phi: Dataset-3 level 1, Dataset-1 grid): the forward's last phi row
   // duplicates row 0, so fold its gradient into row 0 and continue on the even ring (kernels_bwd.hip: fold_phi_kernel).
   float* folded = nullptr;
@@ -849,19 +879,19 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
       ConvGeom gd{dout, din, kz, 4, 4, sz, 2, 2};
       ConvFusion fu;
       fu.wpk_bf16x3 = pre ? img->pk3 : wp3;
-      fu.in_absmax = launch_absmax_bits(dy, (size_t)r.B * dout.vox() * c, r.s);
+      dy_max = launch_absmax_bits(dy, (size_t)r.B * dout.vox() * c, &r.amax, r.s);
+      fu.in_absmax = dy_max;
       launch_conv_mfma(dy, c, nullptr, 0, pre ? img->pk : wp, nullptr, dx, r.B, c, gd, r.s, fu);
     }
     if (wp3) ws->release(wp3);
     if (wp) ws->release(wp);
   }
   // dw[ci][co][k] = sum_i x[i][ci] * dy[s*i + k - 1][co]: the strided-conv weight gradient with the two tensors' roles swapped
-  float* part = ws->get<float>(wgrad_partial_floats(din.vox(), r.B, false, c, c, T));
-  if (!r.dry()) {
-    launch_wgrad(x, c, din, dy, c, c, 0, dout, kz, 4, 4, sz, 2, r.B, false, part, dw, false, false, r.s);
-    absmax_note_drop();
-  }
-  ws->release(part);
+  float* part = r.wgrad_part(wgrad_partial_floats(din.vox(), r.B, false, c, c, T));
+  if (!r.dry())
+    launch_wgrad(x, c, din, dy, c, c, 0, dout, kz, 4, 4, sz, 2, r.B, false, part, dw, false, false, r.s, 0, 0, nullptr,
+                 r.wgrad_aux(nullptr, dy_max));
+  r.release_wgrad_part(part);
   if (db) bias_grad(r, dy_full, c, dout_full.vox(), db);
   if (folded) ws->release(folded);
 }
@@ -1259,8 +1289,7 @@ int cd_plan_destroy(CdPlan* plan) {
     if (plan->cap_stream) hipStreamDestroy(plan->cap_stream);
     if (plan->d_pack_jobs) hipFree(plan->d_pack_jobs);
     if (plan->d_dg_jobs) hipFree(plan->d_dg_jobs);
-    if (plan->dg_arena) hipFree(plan->dg_arena);
-    if (plan->wq_region) hipFree(plan->wq_region);
+    if (plan->d_attn_sync) hipFree(plan->d_attn_sync);
     if (plan->arena) hipFree(plan->arena);
     if (plan->d_embed_layers) hipFree(plan->d_embed_layers);
     if (plan->d_coords) hipFree(plan->d_coords);
@@ -1944,13 +1973,15 @@ int cd_plan_grad_layout(const CdPlan* plan, int idx, int64_t* offset, int64_t* t
 }
 
 // The weight images every convolution's INPUT gradient reads (the forward kernels run on channel-transposed, tap-flipped weights:
-// conv_backward / conv_transpose_backward), laid out once in a plan-owned arena and described by one job list whose sources are
-// the plan's own raw copies of the tensors -- stable pointers, so the list never changes; train_step_impl launches it once per
-// step.  dg_mode: 1 = 1x1 conv (f32 image, transposed), 2 = 3x3x3 stride 1 (f32 + split16 images, transposed + flipped),
-// 3 = strided down conv (f32 + f16x2 images, transposed: its adjoint is the up-conv gather kernel), 4 = up conv (f32 + split16
-// images of the tensor read as a plain conv: its adjoint is the strided conv).
+// conv_backward / conv_transpose_backward), laid out once per plan (dg_floats) and described by one job list whose sources are the
+// plan's own raw copies of the tensors; the images themselves go to a block of each step's workspace (train_step_impl re-points
+// the list when that block moves, and launches it once per step).  The packers write every float of every image, and the
+// alignment gaps between the images are never read: the block needs no clearing.  dg_mode: 1 = 1x1 conv (f32 image,
+// transposed), 2 = 3x3x3 stride 1 (f32 + split16 images, transposed + flipped), 3 = strided down conv (f32 + f16x2 images,
+// transposed: its adjoint is the up-conv gather kernel), 4 = up conv (f32 + split16 images of the tensor read as a plain conv:
+// its adjoint is the strided conv).
 static void dgrad_images(CdPlan* p) {
-  if (p->dg_arena) return;
+  if (p->d_dg_jobs) return;
   size_t off = 0;
   auto bump = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
   std::vector<PackJob> jobs;
@@ -1981,24 +2012,12 @@ static void dgrad_images(CdPlan* p) {
     else if (w.dg_mode == 3) j.n_f16 = n16;
     jobs.push_back(j);
   }
-  CD_HIP(hipMalloc((void**)&p->dg_arena, (off + 64) * sizeof(float)));
-  CD_HIP(hipMemset(p->dg_arena, 0, (off + 64) * sizeof(float)));
   size_t k = 0;
-  for (auto& w : p->weights) {
-    if (!w.dg_mode) continue;
-    PackJob& j = jobs[k++];
-    j.src = p->arena + w.raw_off;
-    j.pk = p->dg_arena + w.dg_pk_off;
-    if (w.dg_mode == 2 || w.dg_mode == 4) {
-      j.bf3 = p->dg_arena + w.dg_pk3_off;
-      j.f16 = (char*)(p->dg_arena + w.dg_pk3_off) + packed_bf16x3_bytes(j.cin, j.cout, w.taps);
-    } else if (w.dg_mode == 3) {
-      j.f16 = p->dg_arena + w.dg_pk3_off;
-    }
-  }
-  p->n_dg_jobs = (int)jobs.size();
+  for (auto& w : p->weights)
+    if (w.dg_mode) jobs[k++].src = p->arena + w.raw_off;
+  p->dg_floats = off;
+  p->dg_jobs = jobs;
   CD_HIP(hipMalloc((void**)&p->d_dg_jobs, sizeof(PackJob) * (jobs.size() + 1)));
-  CD_HIP(hipMemcpy(p->d_dg_jobs, jobs.data(), sizeof(PackJob) * jobs.size(), hipMemcpyHostToDevice));
 }
 
 int cd_plan_train_workspace_bytes(CdPlan* plan, int batch, size_t* bytes) {
@@ -2052,6 +2071,13 @@ int cd_loss_hybrid(CdPlan* plan, int batch, const float* data, const float* nois
 }
 
 // ---- primitives -----------------------------------------------------------------------------------------------
+// the zeroed max-|x| words of a primitive's convolution backward, from its own workspace (at most two measured tensors per source)
+static AbsmaxWords op_absmax_words(Arena& ws, hipStream_t s) {
+  constexpr size_t kWords = 8;
+  unsigned* w = ws.get<unsigned>(kWords);
+  CD_HIP(hipMemsetAsync(w, 0, sizeof(unsigned) * kWords, s));
+  return AbsmaxWords{w, w + kWords};
+}
 size_t cd_op_scratch_bytes(int batch, int max_channels, int64_t max_voxels) {
   // packed weights of the largest supported conv (256 x 256 x 64 taps) + norm partials + one activation
   return (size_t)256 * 256 * 64 * 4 * 4 + (size_t)batch * 64 * 64 * 16 + (size_t)batch * max_channels * max_voxels * 4 + (1 << 20);
@@ -2209,6 +2235,7 @@ int cd_op_conv_backward(const float* x0, int c0, const float* x1, int c1, const 
     Arena ws;
     ws.reset((char*)workspace, workspace_bytes, false);
     Run run{&ws, (hipStream_t)stream, batch, 8};
+    run.amax = op_absmax_words(ws, run.s);
     ConvGeom g;
     g.in = Dims3{dims_in[0], dims_in[1], dims_in[2]};
     g.kd = kernel[0]; g.kh = kernel[1]; g.kw = kernel[2]; g.sz = stride[0]; g.sh = stride[1]; g.sw = stride[2];
@@ -2226,6 +2253,7 @@ int cd_op_conv_transpose_backward(const float* x, const float* w, const float* d
     Arena ws;
     ws.reset((char*)workspace, workspace_bytes, false);
     Run run{&ws, (hipStream_t)stream, batch, 8};
+    run.amax = op_absmax_words(ws, run.s);
     const Dims3 din{dims_in[0], dims_in[1], dims_in[2]};
     const Dims3 dout{(din.d - 1) * stride_z - 2 + kernel_z, 2 * din.h + out_pad[1], 2 * din.w + out_pad[2]};
     conv_transpose_backward(run, x, w, dy, dx, dw, db, channels, din, dout, kernel_z, stride_z);

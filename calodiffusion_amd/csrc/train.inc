@@ -5,7 +5,7 @@
 // weight order (cd_plan_grad_layout) and are exposed to torch.optim through calodiffusion_amd.engine.
 //
 // Nothing is released between forward and backward (the tape owns the activations); temporaries of the backward are
-// released as soon as they are consumed.
+// released as soon as they are consumed, the weight gradients' partials once their queued reductions have been launched.
 
 struct ResTape {
   const ResW* w = nullptr;
@@ -233,9 +233,10 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
   float* scratch = ws->get<float>(gn_backward_scratch_floats(r.B, C, vox));
   // block2: y = silu(gn2(h2)) + shortcut
   float* dh2 = ws->get<float>((size_t)r.B * vox * C);
+  unsigned* dh2_max = r.amax_word();  // max |dh2|: left by the GroupNorm backward for the conv backward that consumes dh2
   if (!r.dry())
     launch_gn_backward(dy, t.h2, t.coef2, t.stat2, p->raw(W.n2g), dh2, G.at(W.n2g), G.at(W.n2b), nullptr, 0, r.B, C, vox, Gn, 1,
-                       scratch, false, r.s, G.at(W.c2b), W.has_res ? G.at(W.rb) : nullptr, r.gq);  // (+ the biases of conv2 and the shortcut)
+                       scratch, false, r.s, G.at(W.c2b), W.has_res ? G.at(W.rb) : nullptr, r.gq, dh2_max);  // (+ the biases of conv2 and the shortcut)
   // a1 = silu(gn1(h1)) + emb was only ever formed inside conv2's LDS staging: the weight gradient re-forms it the same way while
   // it stages h1 (round 4; a gn_apply pass and a tensor per block before), or it is recomputed here for the kernels that cannot
   static const bool no_xnorm = getenv("CD_NO_WGRAD_XNORM") != nullptr;
@@ -244,36 +245,44 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
   if (!r.dry() && a1) launch_gn_apply(t.h1, a1, t.coef1, r.B, C, vox, 1, nullptr, nullptr, 0, nullptr, r.s);
   float* da1 = ws->get<float>((size_t)r.B * vox * C);
   const DgImg i2 = p->dg(W.c2w), i1 = p->dg(W.c1w);
-  conv_backward(r, a1 ? a1 : t.h1, C, nullptr, 0, p->raw(W.c2w), dh2, da1, G.at(W.c2w), nullptr, C, g, &i2, xnorm ? t.coef1 : nullptr);
+  conv_backward(r, a1 ? a1 : t.h1, C, nullptr, 0, p->raw(W.c2w), dh2, da1, G.at(W.c2w), nullptr, C, g, &i2, xnorm ? t.coef1 : nullptr,
+                nullptr, nullptr, dh2_max);
   if (a1) ws->release(a1);
   ws->release(dh2);
   float* dh1 = ws->get<float>((size_t)r.B * vox * C);
+  unsigned* dh1_max = r.amax_word();
   if (!r.dry())
     launch_gn_backward(da1, t.h1, t.coef1, t.stat1, p->raw(W.n1g), dh1, G.at(W.n1g), G.at(W.n1b),
-                       W.has_mlp ? demb + W.emb_off : nullptr, p->emb_ld, r.B, C, vox, Gn, 1, scratch, false, r.s, G.at(W.c1b), nullptr, r.gq);
+                       W.has_mlp ? demb + W.emb_off : nullptr, p->emb_ld, r.B, C, vox, Gn, 1, scratch, false, r.s, G.at(W.c1b), nullptr, r.gq,
+                       dh1_max);
   ws->release(da1);
   float* dx = ws->get<float>((size_t)r.B * vox * cin);
   // identity shortcut: its share of the input gradient (dy itself) is added by the input-gradient conv where that kernel can
   static const bool no_dxadd = getenv("CD_NO_DGRAD_ADD") != nullptr;
   int added = 0;
   conv_backward(r, t.x0, t.c0, t.x1, t.c1, p->raw(W.c1w), dh1, dx, G.at(W.c1w), nullptr, C, g, &i1, nullptr,
-                (!W.has_res && !no_dxadd) ? dy : nullptr, &added);
+                (!W.has_res && !no_dxadd) ? dy : nullptr, &added, dh1_max);
   ws->release(dh1);
   ws->release(scratch);
   // shortcut
   if (W.has_res) {
     const DgImg ir = p->dg(W.rw);
     float* wp = ir.pk ? nullptr : ws->get<float>(packed_weight_floats(C, cin, 1));
-    float* part = ws->get<float>(wgrad_partial_floats(vox, r.B, false, C, t.c0 > t.c1 ? t.c0 : t.c1, 1));
     if (!r.dry()) {
       if (!ir.pk) launch_pack_weights(p->raw(W.rw), wp, cin, C, 1, true, r.s);
       PointwiseArgs a;
       a.in0 = dy; a.ld0 = C; a.c0 = C; a.wpk = ir.pk ? ir.pk : wp; a.out = dx; a.residual = dx; a.batch = r.B; a.cout = cin; a.vox = vox;
       launch_pointwise(a, r.s);
-      launch_wgrad(dy, C, t.dims, t.x0, t.c0, t.c0, 0, t.dims, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.rw), false, false, r.s, cin, 0);
-      if (t.c1) launch_wgrad(dy, C, t.dims, t.x1, t.c1, t.c1, 0, t.dims, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.rw), false, false, r.s, cin, t.c0);
     }
-    ws->release(part);
+    const float* xs[2] = {t.x0, t.x1};
+    const int cs[2] = {t.c0, t.c1};
+    for (int k = 0; k < 2 && cs[k]; ++k) {
+      float* part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, cs[k], 1));
+      if (!r.dry())
+        launch_wgrad(dy, C, t.dims, xs[k], cs[k], cs[k], 0, t.dims, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.rw), false, false, r.s, cin,
+                     k ? t.c0 : 0, nullptr, r.wgrad_aux());
+      r.release_wgrad_part(part);
+    }
     if (wp) ws->release(wp);
   } else {
     if (!r.dry() && !added) launch_add_slices(dx, cin, 0, dy, C, 0, dx, cin, (int64_t)r.B * vox, r.s);
@@ -300,15 +309,17 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   float* o = ws->get<float>((size_t)rows * 32);
   float* pk = ws->get<float>((size_t)r.B * 1024);
   float* pkT = ws->get<float>((size_t)r.B * 1024);
-  float* part = ws->get<float>(wgrad_partial_floats(vox, r.B, false, C > 96 ? C : 96, C > 32 ? C : 32, 1));
+  float* part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, 32, 1));
   if (!r.dry()) {
     launch_softmax32(t.qkv, qs, rows, r.s);
     launch_pack_sample32_pair(t.ctx, pk, pkT, r.B, scale, r.s);  // pk: W[co=e][ci=d] = scale*ctx[d][e]; pkT: W[co=d][ci=e] (used below)
     PointwiseArgs a;
     a.in0 = qs; a.ld0 = 32; a.c0 = 32; a.wpk = pk; a.w_batch_stride = 1024; a.out = o; a.batch = r.B; a.cout = 32; a.vox = vox;
     launch_pointwise(a, r.s);
-    launch_wgrad(dy0, C, d1, o, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.ow), false, false, r.s);
+    launch_wgrad(dy0, C, d1, o, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.ow), false, false, r.s, 0, 0, nullptr,
+                 r.wgrad_aux());
   }
+  r.release_wgrad_part(part);
   ws->release(o);
   // do = Wout^T dy0
   float* dO = ws->get<float>((size_t)rows * 32);
@@ -360,9 +371,11 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   float* dxn = ws->get<float>((size_t)rows * C);
   const DgImg iq = p->dg(W.qkv);
   float* wq = iq.pk ? nullptr : ws->get<float>(packed_weight_floats(96, C, 1));
+  part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, 96, C, 1));
   if (!r.dry()) {
     launch_gn_apply(t.x, xn, t.coefn, r.B, C, vox, 0, nullptr, nullptr, 0, nullptr, r.s);
-    launch_wgrad(dqkv, 96, d1, xn, C, C, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.qkv), false, false, r.s);
+    launch_wgrad(dqkv, 96, d1, xn, C, C, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.qkv), false, false, r.s, 0, 0, nullptr,
+                 r.wgrad_aux());
     if (!iq.pk) launch_pack_weights(p->raw(W.qkv), wq, C, 96, 1, true, r.s);
     PointwiseArgs a;
     a.in0 = dqkv; a.ld0 = 96; a.c0 = 96; a.wpk = iq.pk ? iq.pk : wq; a.out = dxn; a.batch = r.B; a.cout = C; a.vox = vox;
@@ -371,7 +384,7 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   if (wq) ws->release(wq);
   ws->release(xn);
   ws->release(dqkv);
-  ws->release(part);
+  r.release_wgrad_part(part);
   float* dx = ws->get<float>((size_t)rows * C);
   if (!r.dry()) {
     launch_gn_backward(dxn, t.x, t.coefn, t.statn, p->raw(W.ng), dx, G.at(W.ng), G.at(W.nb), nullptr, 0, r.B, C, vox, 1, 0, scratch,
@@ -381,6 +394,26 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   ws->release(dxn);
   ws->release(scratch);
   return dx;
+}
+
+// the device job list of dgrad_images (plan.hip) pointed at this step's images block `img`: a copy only when the block has moved
+// (the engine keeps one training workspace per batch size)
+void point_dgrad_jobs(CdPlan* p, float* img, hipStream_t s) {
+  if (p->dg_jobs_at == img) return;
+  size_t k = 0;
+  for (const auto& w : p->weights) {
+    if (!w.dg_mode) continue;
+    PackJob& j = p->dg_jobs[k++];
+    j.pk = img + w.dg_pk_off;
+    if (w.dg_mode == 2 || w.dg_mode == 4) {
+      j.bf3 = img + w.dg_pk3_off;
+      j.f16 = (char*)(img + w.dg_pk3_off) + packed_bf16x3_bytes(j.cin, j.cout, w.taps);
+    } else if (w.dg_mode == 3) {
+      j.f16 = img + w.dg_pk3_off;
+    }
+  }
+  CD_HIP(hipMemcpyAsync(p->d_dg_jobs, p->dg_jobs.data(), sizeof(PackJob) * p->dg_jobs.size(), hipMemcpyHostToDevice, s));
+  p->dg_jobs_at = img;
 }
 
 // loss + all parameter gradients.  Returns nothing; grads (flat) and loss_out are written on the stream.
@@ -396,6 +429,9 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   Arena* ws = r.ws;
   Grads G{p, grads};
   TrainTape T;
+  // this step's input-gradient weight images (plan.hip: dgrad_images), for the whole step
+  float* dg_img = ws->get<float>(p->dg_floats);
+  p->dg_images = dg_img;
   // ---- forward ----
   float* xn = ws->get<float>((size_t)n);
   T.x0 = ws->get<float>((size_t)n);
@@ -410,9 +446,10 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   ia.coord_table = p->d_init_table; ia.table_ready = true; ia.status = r.status;
   const EmbedArgs ea = embed_args(p, B, cond, sigma, d.time_embed_kind, T.emb, T.scal);
   if (!r.dry()) {
-    if (p->d_dg_jobs) {  // this step's input-gradient weight images, all convolutions in two launches (plan.hip: dgrad_images)
-      launch_pack_jobs(p->d_dg_jobs, p->n_dg_jobs, s);
-      launch_pack_jobs_f16x2(p->d_dg_jobs, p->n_dg_jobs, s);
+    if (!p->dg_jobs.empty()) {  // the images of all convolutions in two launches
+      point_dgrad_jobs(p, dg_img, s);
+      launch_pack_jobs(p->d_dg_jobs, (int)p->dg_jobs.size(), s);
+      launch_pack_jobs_f16x2(p->d_dg_jobs, (int)p->dg_jobs.size(), s);
     }
     launch_axpy_sigma(data, noise, sigma, xn, B, per, s);
     launch_embed(ea, s);
@@ -429,28 +466,29 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   }
   // ---- backward ----
   // the GroupNorm layers queue their parameter-gradient reductions (per-sample sums in `qsums`), one launch flushes them at the end
-  // ... and the weight gradients queue the reductions of their per-workgroup partials (65 launches of 4-7 us otherwise)
+  // ... and the weight gradients queue the reductions of their per-workgroup partials (65 launches of 4-7 us otherwise), each
+  // partial in a workspace block of its own until then (Run::wgrad_part)
   WgradReduceQueue wq;
-  struct WqScope {  // (no queue may stay current past this call, whatever leaves it)
-    ~WqScope() { wgrad_queue_set(nullptr); }
-  } wq_scope;
   static const bool no_wq = getenv("CD_NO_WGRAD_QUEUE") != nullptr;
-  if (!r.dry() && !no_wq) {
-    wq.base = p->wq_region;
-    wq.cap = p->wq_cap;
-    wgrad_queue_set(&wq);
-  }
+  if (!no_wq) r.wq = &wq;
   GnParamQueue gq;
   int cmax = 32;
   for (int i = 0; i <= nres; ++i) cmax = d.layer_sizes[i] > cmax ? d.layer_sizes[i] : cmax;
-  float* qsums = ws->get<float>((size_t)GnParamJobs::kMax * 2 * B * cmax * 4);
-  gq.next_sums = qsums;
+  const size_t nsums = (size_t)GnParamJobs::kMax * 2 * B * cmax * 4;
+  float* qsums = ws->get<float>(nsums);
+  gq.sums = gq.next_sums = qsums;
+  gq.sums_end = qsums + nsums;
   r.gq = &gq;
-  float* demb = ws->get<float>((size_t)B * p->emb_ld);
+  // demb, and behind it the step's max-|x| words (launch_absmax_bits, launch_gn_backward): one memset zeroes both.  A convolution's
+  // backward measures at most two tensors, a GroupNorm backward one: fewer words than weight tensors, twice that is plenty.  (The
+  // whole is a multiple of 64 floats: a fill of any other size is two launches.)
+  const size_t nemb = (size_t)B * p->emb_ld, nclear = (nemb + 2 * p->weights.size() + 63) & ~(size_t)63;
+  float* demb = ws->get<float>(nclear);
+  if (!r.dry()) r.amax = AbsmaxWords{(unsigned*)(demb + nemb), (unsigned*)(demb + nclear)};
   float* g = ws->get<float>((size_t)n * 32);
   float* hpart = ws->get<float>((size_t)head_bwd_blocks(B, per) * 33);
   if (!r.dry()) {
-    CD_HIP(hipMemsetAsync(demb, 0, sizeof(float) * (size_t)B * p->emb_ld, s));
+    CD_HIP(hipMemsetAsync(demb, 0, sizeof(float) * nclear, s));
     launch_head_loss_bwd(T.x0, data, noise, T.scal, hf, p->raw(p->head_w), g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
                          loss_type, d.objective);
   }
@@ -513,25 +551,17 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
     ws->release(ipart);
   } else {
     float* iscr = ws->get<float>(init_wgrad_mfma_floats(B, per, d.layer_sizes[0]));
-    if (!r.dry()) launch_init_wgrad_mfma(ia, g, iscr, G.at(p->init_w), s);
+    if (!r.dry()) launch_init_wgrad_mfma(ia, g, iscr, G.at(p->init_w), s, &r.amax);
     ws->release(iscr);
   }
   bias_grad(r, g, d.layer_sizes[0], per, G.at(p->init_b));
   ws->release(g);
   if (!r.dry()) launch_gn_param_jobs(gq.jobs, s);  // every GroupNorm layer's dgamma / dbeta / conv-bias gradient: one launch
   r.gq = nullptr;
-  if (!r.dry() && !no_wq) {
-    wgrad_queue_flush(&wq, s);  // every queued slot reduction: one launch
-    wgrad_queue_set(nullptr);
-    if (wq.need > p->wq_cap) {  // first step of this plan (or a larger batch than before): the NEXT step gets the region
-      CD_HIP(hipStreamSynchronize(s));
-      if (p->wq_region) CD_HIP(hipFree(p->wq_region));
-      p->wq_region = nullptr;
-      p->wq_cap = 0;
-      CD_HIP(hipMalloc((void**)&p->wq_region, wq.need * sizeof(float)));
-      p->wq_cap = wq.need;
-    }
-  }
+  if (!r.dry() && r.wq) wgrad_queue_flush(r.wq, s);  // every queued slot reduction: one launch
+  for (float* part : r.wq_held) ws->release(part);
+  r.wq_held.clear();
+  r.wq = nullptr;
   ws->release(qsums);
   // conditioning MLPs
   const int half = d.cond_dim / 2, hidden = d.cond_size > half / 2 ? d.cond_size : half / 2, q = half / 2;

@@ -213,7 +213,8 @@ int cd_loss_hybrid(CdPlan* plan, int batch, const float* data, const float* nois
  * (as cd_loss_hybrid: hybrid_weight / noise_pred / mean_pred, any CD_LOSS_* type) AND the gradient of that loss with respect to every parameter, written to `grads`, a flat fp32
  * buffer laid out as cd_plan_grad_layout reports (tensor idx of cd_plan_weight_name starts at *offset, torch layout;
  * *total_floats = size of the buffer).  Workspace: cd_plan_train_workspace_bytes (the forward's activations are kept
- * until the backward has consumed them). */
+ * until the backward has consumed them; the input-gradient weight images and the weight gradients' per-workgroup partials, held
+ * until their one reduction launch, live there too: the step allocates no device memory of its own). */
 int cd_plan_grad_layout(const CdPlan* plan, int idx, int64_t* offset, int64_t* total_floats);
 int cd_plan_train_workspace_bytes(CdPlan* plan, int batch, size_t* bytes);
 

@@ -41,9 +41,8 @@ def test_parameter_gradients_match_autograd(name, B):
     sd_cpu = {k[6:]: v.detach().cpu() for k, v in m.state_dict().items()}
     want_loss, want = _oracle_grads(cfg, sd_cpu, data, E, noise, layers, rnd, tsteps)
 
-    # Two identical steps: the plan's first training step reduces every weight gradient's partials where they arise and sizes the
-    # region for them; from the second step on the reductions are queued and run as one launch (WgradReduceQueue): both against
-    # the reference's gradients, and against each other.
+    # Two identical steps (the weight gradients' slot reductions queued and run as one launch, WgradReduceQueue): both against the
+    # reference's gradients, and against each other.
     got_steps = []
     for rep in range(2):
         m.zero_grad()
@@ -67,7 +66,7 @@ def test_parameter_gradients_match_autograd(name, B):
         print(f"[{name}] step {rep}: all gradients together: {rel_l2(got_all, want_all):.3e}")
         assert rel_l2(got_all, want_all) < 5e-6
         got_steps.append(got_all)
-    assert rel_l2(got_steps[1], got_steps[0]) < 1e-6  # (the queued reduction sums short slot lists in another order)
+    assert rel_l2(got_steps[1], got_steps[0]) < 1e-6
 
 
 def test_training_loop_protocol_one_adam_step():
@@ -124,10 +123,25 @@ def test_fused_adam_matches_torch_adam():
 
 
 def test_queued_weight_gradient_reductions_follow_the_batch_size():
-    """The region that holds the weight gradients' partials until their single reduction launch is sized by the first training step
-    of a plan and re-sized when a later step asks for more: batch 2, 2, 5, 5, 2 on one model -- the first step at each new, larger
-    batch reduces (partly) where the partials arise, the following ones from the queue -- every step against autograd through
-    the oracle."""
+    """The weight gradients' partials wait for their single reduction launch in blocks of the step's own workspace, which the
+    engine sizes per batch size: batch 2, 2, 5, 5, 2 on one model -- every step, the first at a new batch size included, queues
+    the same way -- every step against autograd through the oracle."""
+    _steps_across_batch_sizes()
+
+
+def test_immediate_weight_gradient_reductions_follow_the_batch_size():
+    """The same steps with every slot reduction launched where it arises (CD_NO_WGRAD_QUEUE=1), in a child process: the library
+    reads the switch once."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys; sys.path[:0] = [%r, %r]; from test_gpu_train import _steps_across_batch_sizes; _steps_across_batch_sizes()"
+    subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests"))], check=True,
+                   env=dict(os.environ, CD_NO_WGRAD_QUEUE="1"), timeout=900)
+
+
+def _steps_across_batch_sizes():
     m, cfg = _model("tiny")
     sd_cpu = {k[6:]: v.detach().cpu() for k, v in m.state_dict().items()}
     for step, B in enumerate((2, 2, 5, 5, 2)):
@@ -148,3 +162,53 @@ def test_queued_weight_gradient_reductions_follow_the_batch_size():
         got_all = np.concatenate([p.grad.cpu().numpy().ravel() for _, p in m.model.named_parameters()])
         want_all = np.concatenate([want[k].numpy().ravel() for k, _ in m.model.named_parameters()])
         assert rel_l2(got_all, want_all) < 5e-6, (step, B, rel_l2(got_all, want_all))
+
+
+def _dataset2_step(m, B, seed):
+    gen = torch.Generator().manual_seed(seed)
+    data = torch.randn((B, 1, 45, 16, 9), generator=gen)
+    noise = torch.randn(data.shape, generator=gen)
+    E, layers = torch.rand((B, 1), generator=gen), torch.randn((B, 46), generator=gen)
+    sigma = 0.05 + 30.0 * torch.rand((B,), generator=gen)
+    return data.cuda(), noise.cuda(), sigma.cuda(), m.cond_tensor(E.cuda(), layers.cuda())
+
+
+def test_a_training_step_allocates_no_device_memory_of_its_own():
+    """cd_train_step keeps all its scratch -- the queued weight gradients' partials, the input-gradient weight images, the max-|x|
+    words -- in the caller's workspace (include/calodiff.h): on a fresh Dataset-2 engine, steps at batch 1, 2, 1 take no device
+    memory besides what torch allocates (workspaces, gradient buffers).  Kernels and the autotune are warmed on a throwaway engine
+    first (code objects and the tuner's timing runs are the process's, not the step's)."""
+    warm, _ = _model("dataset2")
+    for B in (1, 2):
+        warm.engine().train_step(*_dataset2_step(warm, B, B))
+    torch.cuda.synchronize()
+    m, _ = _model("dataset2")
+    eng = m.engine()
+    torch.cuda.synchronize()
+    free0, reserved0 = torch.cuda.mem_get_info()[0], torch.cuda.memory_reserved()
+    for B in (1, 2, 1):
+        eng.train_step(*_dataset2_step(m, B, 10 + B))
+    torch.cuda.synchronize()
+    free1, reserved1 = torch.cuda.mem_get_info()[0], torch.cuda.memory_reserved()
+    own = (free0 - free1) - (reserved1 - reserved0)
+    print(f"device memory taken by the steps: {(free0 - free1) / 2**20:.1f} MiB, by torch: {(reserved1 - reserved0) / 2**20:.1f} MiB, "
+          f"by the library: {own / 2**20:.1f} MiB")
+    assert own < 64 << 20
+
+
+def test_the_first_training_step_equals_the_steady_state():
+    """A fresh plan's first cd_train_step takes the path of every later one (the reductions queued from the start): two steps on
+    identical inputs give bitwise-equal loss and gradients.  The autotune (per process, keyed by shape) is warmed on a throwaway
+    engine first, so that both steps run the same kernels."""
+    B = 2
+    warm, _ = _model("dataset2")
+    warm.engine().train_step(*_dataset2_step(warm, B, 21))
+    m, _ = _model("dataset2")
+    eng = m.engine()
+    args = _dataset2_step(m, B, 21)
+    steps = []
+    for _ in range(2):
+        loss, flat = eng.train_step(*args)
+        steps.append((float(loss), torch.cat([g.flatten() for g in eng.param_grads(flat)]).cpu()))
+    assert steps[0][0] == steps[1][0], (steps[0][0], steps[1][0])
+    assert torch.equal(steps[0][1], steps[1][1])
