@@ -101,10 +101,52 @@ class CaloDiffusion(Diffusion):
         return embed[self.time_embed](sigma)
 
     def denoise(self, x, E=None, sigma=None, layers=None, controls=None):
-        """EDM-preconditioned denoiser (calodiffusion.py:154-169): one C-ABI call."""
+        """EDM-preconditioned denoiser (calodiffusion.py:154-169): one C-ABI call.
+
+        Differentiable when ``torch.is_grad_enabled()`` and ``x.requires_grad``: backward then gives x its gradient and, if a
+        parameter requires grad, every parameter too (cd_denoise_vjp recomputes the forward on the device).  Any other call is
+        the plain call without a graph; a caller who wants only the parameter gradients sets ``x.requires_grad_()``.  sigma, E
+        and layers are constants of the graph: one that requires grad raises NotImplementedError.  Gradients stay local to
+        the process (no data-parallel all-reduce), as plain torch autograd gives them."""
         if controls is not None:
             raise NotImplementedError("ControlNet is dead code in the reference")
+        if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:
+            for name, t in (("sigma", sigma), ("E", E), ("layers", layers)):
+                if isinstance(t, torch.Tensor) and t.requires_grad:
+                    raise NotImplementedError(f"denoise: no gradient with respect to {name}; pass {name}.detach()")
+            params = list(self.model.parameters())
+            return _Denoise.apply(self.engine(), x, sigma.reshape(-1), self.cond_tensor(E, layers), *params)
         return self.engine().denoise(x, sigma.reshape(-1), self.cond_tensor(E, layers))
 
     def __call__(self, x, **kwargs):
         return self.denoise(x, **kwargs)
+
+
+class _Denoise(torch.autograd.Function):
+    """denoise with a backward: the forward is the plain engine call (same bits), the backward is one cd_denoise_vjp call that
+    recomputes the taped forward from the saved x, sigma and cond."""
+
+    @staticmethod
+    def forward(ctx, engine, x, sigma, cond, *params):
+        out = engine.denoise(x.detach(), sigma.detach(), cond.detach())
+        ctx.save_for_backward(x, sigma, cond)
+        ctx.engine, ctx.params = engine, params
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, sigma, cond = ctx.saved_tensors
+        want = any(p.requires_grad for p in ctx.params)
+        dx, flat = ctx.engine.denoise_vjp(x, sigma, cond, gy.contiguous(), param_grads=want)
+        if want:
+            # the parameters' gradients handed over as in _TrainStep.backward (loss.py): a view of the flat buffer on the first
+            # assignment, added to an existing gradient otherwise
+            for p, g in zip(ctx.params, ctx.engine.param_grads(flat)):
+                if not p.requires_grad:
+                    continue
+                if p.grad is None:
+                    p.grad = g
+                else:
+                    p.grad = p.grad + g if p.grad.requires_grad else p.grad.add_(g)
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None) + (None,) * len(ctx.params)

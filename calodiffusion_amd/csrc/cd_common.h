@@ -341,6 +341,13 @@ int head_bwd_blocks(int batch, int64_t vox);
 void launch_head_loss_bwd(const float* x0, const float* data, const float* noise, const float* scal, const float* h, const float* wh,
                           float* dh, float* part, float* dwh, float* dbh, int batch, int64_t vox, hipStream_t s, int loss_type = 0,
                           int objective = 0);
+// the head's backward from the caller's dL/dD (cd_denoise_vjp): dh always; dWh / dbh only when part != null
+void launch_head_vjp(const float* gy, const float* scal, const float* h, const float* wh, float* dh, float* part, float* dwh, float* dbh,
+                     int batch, int64_t vox, int objective, hipStream_t s);
+// input gradient of the init conv's data channel with the EDM preconditioning: g (B, vox, c0) channels-last, w_raw torch layout
+// (c0, cin, 3, 3, 3), scal the (B, 4) scalings {c_in, c_skip, c_out, sigma}; dx, gy (B, 1, D, H, W)
+void launch_init_dgrad(const float* g, const float* w_raw, int cin, int c0, const float* gy, const float* scal, int objective, float* dx,
+                       int batch, Dims3 dims, hipStream_t s);
 struct LinearWgradJob {
   const float* delta;  // (B, delta_ld) rows, nout used
   const float* in;     // (B, in_ld) rows, nin used
@@ -371,6 +378,7 @@ struct GnParamQueue {
   float* sums = nullptr;       // region of the jobs' per-sample sums, kept by the caller until the flush: [sums, sums_end)
   float* sums_end = nullptr;
   float* next_sums = nullptr;  // bump pointer into it (back to `sums` after a flush)
+  bool discard = false;        // input gradients only (cd_denoise_vjp without grads): the jobs are never run, a full queue rewinds
 };
 void launch_gn_param_jobs(const GnParamJobs& jobs, hipStream_t s);
 void launch_gn_backward(const float* dy, const float* h, const float* coef, const float* stat, const float* gamma, float* dh,

@@ -1366,7 +1366,7 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
   if (queue) {  // the per-sample sums go to the caller's persistent slot and the batch reduction joins the queue
     CD_REQUIRE(!accumulate_params, "gn backward: queued parameter gradients do not accumulate");
     if (queue->jobs.n == GnParamJobs::kMax) {  // (deeper networks than the shipped ones: flush and go on)
-      launch_gn_param_jobs(queue->jobs, s);
+      if (!queue->discard) launch_gn_param_jobs(queue->jobs, s);
       queue->jobs.n = 0;
       queue->next_sums = queue->sums;
     }
@@ -1753,6 +1753,226 @@ void launch_head_loss_bwd(const float* x0, const float* data, const float* noise
   hipLaunchKernelGGL(head_loss_bwd_kernel, dim3(nb), dim3(256), 0, s, x0, data, noise, scal, h, wh, dh, part, batch, vox, loss_type,
                      objective);
   hipLaunchKernelGGL(head_grad_reduce_kernel, dim3(1), dim3(256), 0, s, part, nb, dwh, dbh);
+  CD_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Head backward from a caller's gradient gy = dL/dD of the denoiser output (cd_denoise_vjp; D as in head_kernel):
+//   dF = coef_b gy,  coef_b = c_out (hybrid), -sigma (noise_pred), 1 (mean_pred);  dh[v][c] = dF*Wh[c]
+//   PARAMS: dWh[c] = sum dF*h[v][c], dbh = sum dF as [blocks][33] partials for head_grad_reduce_kernel
+// ------------------------------------------------------------------------------------------------------------
+template <bool PARAMS>
+__global__ void __launch_bounds__(256) head_vjp_kernel(const float* __restrict__ gy, const float* __restrict__ scal,
+                                                       const float* __restrict__ h, const float* __restrict__ wh, float* __restrict__ dh,
+                                                       float* __restrict__ part, int batch, int64_t vox, int objective) {
+  __shared__ float sW[32];
+  __shared__ float sAcc[4][33];
+  const int tid = threadIdx.x, sub = tid & 7, grp = tid >> 3;
+  if (tid < 32) sW[tid] = wh[tid];
+  __syncthreads();
+  const int64_t total = (int64_t)batch * vox;
+  f32x4 aw = {0.f, 0.f, 0.f, 0.f};
+  float ab = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 32 + grp; i < total; i += (int64_t)gridDim.x * 32) {
+    const int b = (int)(i / vox);
+    const float chain = objective == 0 ? scal[b * 4 + 2] : (objective == 1 ? -scal[b * 4 + 3] : 1.0f);
+    const float dF = chain * gy[i];
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = dF * sW[sub * 4 + e];
+    *(f32x4*)(dh + (size_t)i * 32 + sub * 4) = o;
+    if (PARAMS) {
+      const f32x4 hv = *(const f32x4*)(h + (size_t)i * 32 + sub * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) aw[e] += dF * hv[e];
+      if (sub == 0) ab += dF;
+    }
+  }
+  if (!PARAMS) return;
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) aw[e] += __shfl_xor(aw[e], o, 64);
+    ab += __shfl_xor(ab, o, 64);
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+  if (lane < 8) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sAcc[wave][lane * 4 + e] = aw[e];
+    if (lane == 0) sAcc[wave][32] = ab;
+  }
+  __syncthreads();
+  if (tid < 33) part[(size_t)blockIdx.x * 33 + tid] = sAcc[0][tid] + sAcc[1][tid] + sAcc[2][tid] + sAcc[3][tid];
+}
+void launch_head_vjp(const float* gy, const float* scal, const float* h, const float* wh, float* dh, float* part, float* dwh, float* dbh,
+                     int batch, int64_t vox, int objective, hipStream_t s) {
+  const int nb = head_bwd_blocks(batch, vox);
+  if (part) {
+    hipLaunchKernelGGL(head_vjp_kernel<true>, dim3(nb), dim3(256), 0, s, gy, scal, h, wh, dh, part, batch, vox, objective);
+    hipLaunchKernelGGL(head_grad_reduce_kernel, dim3(1), dim3(256), 0, s, part, nb, dwh, dbh);
+  } else {
+    hipLaunchKernelGGL(head_vjp_kernel<false>, dim3(nb), dim3(256), 0, s, gy, scal, h, wh, dh, part, batch, vox, objective);
+  }
+  CD_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Init conv input gradient of the data channel with the EDM preconditioning in its epilogue (cd_denoise_vjp):
+//   dx[b][v] = a_b gy[b][v] + c_in_b sum_{c,tap} W[c][0][tap] G[b][v - tap][c]
+//   a_b = c_skip (hybrid), 1 (noise_pred), 0 (mean_pred);  phi wraps, z and r are zero-padded (the forward's cyl_conv).
+// Channels first, stencil second: per staged voxel the 27 tap sums P[tap] = sum_c W[c][tap] G[v][c] (27 C0 FMAs on one 4 C0-byte
+// row of G), parked in LDS for one z-plane of a phi band; each output voxel then gathers its in-plane 3x3 neighbours' P for the
+// three z-taps and keeps three running plane sums in registers while the block walks its z-chunk, VZ planes per trip (each weight
+// read from LDS then serves VZ FMAs: with one plane per trip the broadcast weight reads bound the kernel).  G is read once per chunk
+// (+ one halo plane on either side, + one halo phi row on either side when a plane is split into bands); the next trip's rows are
+// loaded while the current ones are reduced.  Deterministic: every sum has a fixed order.
+// ------------------------------------------------------------------------------------------------------------
+template <int C0, int VZ>
+__global__ void __launch_bounds__(256) init_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ w_raw, int cin,
+                                                         const float* __restrict__ gy, const float* __restrict__ scal, int objective,
+                                                         float* __restrict__ dx, Dims3 dims, int band, int halo, int zc) {
+  constexpr int NQ = C0 / 4;
+  __shared__ __attribute__((aligned(16))) float sW[C0][28];  // W[c][0][tap], padded to 7 float4
+  __shared__ float sP[VZ][27][256];
+  const int tid = threadIdx.x;
+  const int chunk = blockIdx.x, bi = blockIdx.y, b = blockIdx.z;
+  const int D = dims.d, H = dims.h, W = dims.w;
+  const int64_t HW = (int64_t)H * W;
+  for (int i = tid; i < C0 * 28; i += blockDim.x) {
+    const int c = i / 28, tap = i % 28;
+    sW[c][tap] = tap < 27 ? w_raw[(size_t)c * cin * 27 + tap] : 0.f;
+  }
+  const int rows = band + 2 * halo;
+  const int lr = tid / W, w = tid % W;
+  const bool stage = lr < rows;  // this thread stages voxel (row lr of the band incl. halo, column w)
+  const int h0 = bi * band;
+  int hs = h0 - halo + lr;
+  hs = ((hs % H) + H) % H;
+  const int orow = lr - halo, ho = h0 + orow;
+  const bool out = stage && orow >= 0 && orow < band && ho < H;
+  const int z0 = chunk * zc, z1 = min(z0 + zc, D);
+  const float* gb = g + ((size_t)b * D * HW + (size_t)hs * W + w) * C0;
+  // planes z0 - 1 .. z1 are read (the halo planes included); others count as zero
+  auto live = [&](int z) { return z >= 0 && z < D && z <= z1; };
+  auto load = [&](int z, f32x4* v) {
+    const bool ok = stage && live(z);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = ok ? *(const f32x4*)(gb + (size_t)z * HW * C0 + q * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  f32x4 cur[VZ][NQ];
+#pragma unroll
+  for (int k = 0; k < VZ; ++k) load(z0 - 1 + k, cur[k]);
+  __syncthreads();
+  float am = 0.f, a0 = 0.f, ap = 0.f;  // running sums of output planes zi - 1, zi, zi + 1
+  // VZ input planes per trip: each weight read from LDS feeds VZ FMAs
+  for (int zb = z0 - 1; zb <= z1; zb += VZ) {
+    float sm[VZ][3];
+#pragma unroll
+    for (int k = 0; k < VZ; ++k) sm[k][0] = sm[k][1] = sm[k][2] = 0.f;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < VZ; ++k) any = any || live(zb + k);
+    if (any) {  // (block-uniform)
+      f32x4 nxt[VZ][NQ];
+#pragma unroll
+      for (int k = 0; k < VZ; ++k) load(zb + VZ + k, nxt[k]);
+      if (stage) {
+        float acc[VZ][27];
+#pragma unroll
+        for (int k = 0; k < VZ; ++k)
+#pragma unroll
+          for (int t = 0; t < 27; ++t) acc[k][t] = 0.f;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = q * 4 + e;
+#pragma unroll
+            for (int t4 = 0; t4 < 7; ++t4) {
+              const f32x4 wv = *(const f32x4*)&sW[c][t4 * 4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (t4 * 4 + j < 27)
+#pragma unroll
+                  for (int k = 0; k < VZ; ++k) acc[k][t4 * 4 + j] = fmaf(wv[j], cur[k][q][e], acc[k][t4 * 4 + j]);
+            }
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < VZ; ++k)
+#pragma unroll
+          for (int t = 0; t < 27; ++t) sP[k][t][tid] = acc[k][t];
+      }
+      __syncthreads();
+      if (out) {
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+          int nr = lr - kh + 1;  // staged row of the neighbour h - kh + 1 (a band's halo rows hold it; a whole plane wraps)
+          if (!halo) nr = nr < 0 ? nr + H : (nr >= H ? nr - H : nr);
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) {
+            const int ww = w - kw + 1;
+            if (ww < 0 || ww >= W) continue;
+            const int j = nr * W + ww, t = kh * 3 + kw;
+#pragma unroll
+            for (int k = 0; k < VZ; ++k) {
+              sm[k][0] += sP[k][t][j];
+              sm[k][1] += sP[k][9 + t][j];
+              sm[k][2] += sP[k][18 + t][j];
+            }
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < VZ; ++k)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) cur[k][q] = nxt[k][q];
+    }
+#pragma unroll
+    for (int k = 0; k < VZ; ++k) {
+      const int zi = zb + k;
+      if (zi > z1) break;
+      am += sm[k][0];
+      a0 += sm[k][1];
+      ap += sm[k][2];
+      const int u = zi - 1;  // complete: it has the contributions of planes u - 1, u, u + 1
+      if (out && u >= z0 && u < z1) {
+        const size_t o = (size_t)b * D * HW + (size_t)u * HW + (size_t)ho * W + w;
+        const float cin_b = scal[b * 4 + 0];
+        dx[o] = objective == 2 ? cin_b * am : fmaf(objective == 0 ? scal[b * 4 + 1] : 1.f, gy[o], cin_b * am);
+      }
+      am = a0;
+      a0 = ap;
+      ap = 0.f;
+    }
+  }
+}
+void launch_init_dgrad(const float* g, const float* w_raw, int cin, int c0, const float* gy, const float* scal, int objective, float* dx,
+                       int batch, Dims3 dims, hipStream_t s) {
+  CD_REQUIRE(c0 == 16 || c0 == 32 || c0 == 64, "init conv input gradient: 16, 32 or 64 output channels");
+  CD_REQUIRE(dims.w >= 1 && dims.w <= 64, "init conv input gradient: r extent up to 64");
+  // a whole phi ring per block where it fits the 256 threads, else bands of rows with one halo row on either side
+  int band = dims.h, halo = 0;
+  if ((int64_t)dims.h * dims.w > 256) {
+    band = 256 / dims.w - 2;
+    halo = 1;
+  }
+  const int nbands = (dims.h + band - 1) / band;
+  const int threads = ((band + 2 * halo) * dims.w + 63) / 64 * 64;
+  // enough workgroups for two per CU; a chunk keeps >= 3 planes so the two halo planes stay a minority of its reads
+  int nchunks = (512 + batch * nbands - 1) / (batch * nbands);
+  const int maxchunks = (dims.d + 2) / 3;
+  nchunks = nchunks < 1 ? 1 : (nchunks > maxchunks ? maxchunks : nchunks);
+  const int zc = (dims.d + nchunks - 1) / nchunks;
+  nchunks = (dims.d + zc - 1) / zc;
+  prof::Scope scope("init_dgrad", s, 2.0 * 27 * c0 * batch * (double)dims.vox(), 4.0 * batch * (double)dims.vox() * (c0 + 2));
+  const dim3 grid((unsigned)nchunks, (unsigned)nbands, (unsigned)batch);
+  switch (c0) {
+    case 16: hipLaunchKernelGGL((init_dgrad_kernel<16, 2>), grid, dim3(threads), 0, s, g, w_raw, cin, gy, scal, objective, dx, dims, band, halo, zc); break;
+    case 32: hipLaunchKernelGGL((init_dgrad_kernel<32, 2>), grid, dim3(threads), 0, s, g, w_raw, cin, gy, scal, objective, dx, dims, band, halo, zc); break;
+    default: hipLaunchKernelGGL((init_dgrad_kernel<64, 1>), grid, dim3(threads), 0, s, g, w_raw, cin, gy, scal, objective, dx, dims, band, halo, zc); break;
+  }
   CD_HIP(hipGetLastError());
 }
 

@@ -441,6 +441,8 @@ struct Run {
   WgradReduceQueue* wq = nullptr;
   std::vector<float*> wq_held;
   AbsmaxWords amax;  // zeroed words for max |x| (launch_absmax_bits, launch_gn_backward); none in a dry run
+  // backward passes: false = input gradients only (cd_denoise_vjp without grads): no weight / bias / GroupNorm-parameter work
+  bool param_grads = true;
   bool dry() const { return ws->dry(); }
   unsigned* amax_word() { return dry() ? nullptr : amax.take(); }
   // partial buffer of one launch_wgrad; with a queue it stays taken until the flush, so one buffer per queued reduction
@@ -836,6 +838,7 @@ void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, con
       if (wp) ws->release(wp);
     }
   }
+  if (!r.param_grads) return;
   CD_REQUIRE(!xcoef || !c1, "conv backward: a normalised input has one source");
   const float* xs[2] = {x0, x1};
   const int cs[2] = {c0, c1};
@@ -887,12 +890,14 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
     if (wp) ws->release(wp);
   }
   // dw[ci][co][k] = sum_i x[i][ci] * dy[s*i + k - 1][co]: the strided-conv weight gradient with the two tensors' roles swapped
-  float* part = r.wgrad_part(wgrad_partial_floats(din.vox(), r.B, false, c, c, T));
-  if (!r.dry())
-    launch_wgrad(x, c, din, dy, c, c, 0, dout, kz, 4, 4, sz, 2, r.B, false, part, dw, false, false, r.s, 0, 0, nullptr,
-                 r.wgrad_aux(nullptr, dy_max));
-  r.release_wgrad_part(part);
-  if (db) bias_grad(r, dy_full, c, dout_full.vox(), db);
+  if (r.param_grads) {
+    float* part = r.wgrad_part(wgrad_partial_floats(din.vox(), r.B, false, c, c, T));
+    if (!r.dry())
+      launch_wgrad(x, c, din, dy, c, c, 0, dout, kz, 4, 4, sz, 2, r.B, false, part, dw, false, false, r.s, 0, 0, nullptr,
+                   r.wgrad_aux(nullptr, dy_max));
+    r.release_wgrad_part(part);
+    if (db) bias_grad(r, dy_full, c, dout_full.vox(), db);
+  }
   if (folded) ws->release(folded);
 }
 
@@ -2040,6 +2045,29 @@ int cd_train_step(CdPlan* plan, int batch, const float* data, const float* noise
     dgrad_images(plan);
     plan->ws.reset((char*)workspace, workspace_bytes, false);
     train_step_impl(plan, batch, data, noise, sigma, cond, loss_out, grads, (hipStream_t)stream, loss_type);
+  });
+}
+
+int cd_plan_vjp_workspace_bytes(CdPlan* plan, int batch, int with_param_grads, size_t* bytes) {
+  return guarded([&] {
+    CD_REQUIRE(plan && bytes && batch > 0, "bad argument");
+    CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the training step needs the Linear time/cond embeddings");
+    dgrad_images(plan);
+    plan->ws.reset(nullptr, 0, true);
+    denoise_vjp_impl(plan, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, with_param_grads != 0, nullptr);
+    *bytes = plan->ws.high() + 4096;
+  });
+}
+
+int cd_denoise_vjp(CdPlan* plan, int batch, const float* x, const float* sigma, const float* cond, const float* gy, float* dx,
+                   float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan && x && sigma && cond && gy && dx && workspace && batch > 0, "bad argument");
+    CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the training step needs the Linear time/cond embeddings");
+    check_ready(plan, true);
+    dgrad_images(plan);
+    plan->ws.reset((char*)workspace, workspace_bytes, false);
+    denoise_vjp_impl(plan, batch, x, sigma, cond, gy, dx, grads, grads != nullptr, (hipStream_t)stream);
   });
 }
 

@@ -241,7 +241,7 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
   // it stages h1 (round 4; a gn_apply pass and a tensor per block before), or it is recomputed here for the kernels that cannot
   static const bool no_xnorm = getenv("CD_NO_WGRAD_XNORM") != nullptr;
   const bool xnorm = !no_xnorm && wgrad_x_norm_supported(t.dims, t.dims, 3, 3, 3, 1, 1);
-  float* a1 = xnorm ? nullptr : ws->get<float>((size_t)r.B * vox * C);
+  float* a1 = (xnorm || !r.param_grads) ? nullptr : ws->get<float>((size_t)r.B * vox * C);
   if (!r.dry() && a1) launch_gn_apply(t.h1, a1, t.coef1, r.B, C, vox, 1, nullptr, nullptr, 0, nullptr, r.s);
   float* da1 = ws->get<float>((size_t)r.B * vox * C);
   const DgImg i2 = p->dg(W.c2w), i1 = p->dg(W.c1w);
@@ -276,7 +276,7 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
     }
     const float* xs[2] = {t.x0, t.x1};
     const int cs[2] = {t.c0, t.c1};
-    for (int k = 0; k < 2 && cs[k]; ++k) {
+    for (int k = 0; k < 2 && cs[k] && r.param_grads; ++k) {
       float* part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, cs[k], 1));
       if (!r.dry())
         launch_wgrad(dy, C, t.dims, xs[k], cs[k], cs[k], 0, t.dims, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.rw), false, false, r.s, cin,
@@ -305,22 +305,27 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
     launch_gn_backward(dy, t.y0, t.coefg, t.statg, p->raw(W.gg), dy0, G.at(W.gg), G.at(W.gb), nullptr, 0, r.B, C, vox, 1, 0, scratch,
                        false, r.s, G.at(W.ob), nullptr, r.gq);  // (+ the bias of to_out's conv, which produced y0)
   // y0 = Wout o + b,  o[n][e] = sum_d (scale*ctx[d][e]) qs[n][d]
+  const bool pg = r.param_grads;
   float* qs = ws->get<float>((size_t)rows * 32);
-  float* o = ws->get<float>((size_t)rows * 32);
+  float* o = pg ? ws->get<float>((size_t)rows * 32) : nullptr;  // (o only feeds the weight gradient of to_out)
   float* pk = ws->get<float>((size_t)r.B * 1024);
   float* pkT = ws->get<float>((size_t)r.B * 1024);
-  float* part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, 32, 1));
+  float* part = pg ? r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, 32, 1)) : nullptr;
   if (!r.dry()) {
     launch_softmax32(t.qkv, qs, rows, r.s);
     launch_pack_sample32_pair(t.ctx, pk, pkT, r.B, scale, r.s);  // pk: W[co=e][ci=d] = scale*ctx[d][e]; pkT: W[co=d][ci=e] (used below)
-    PointwiseArgs a;
-    a.in0 = qs; a.ld0 = 32; a.c0 = 32; a.wpk = pk; a.w_batch_stride = 1024; a.out = o; a.batch = r.B; a.cout = 32; a.vox = vox;
-    launch_pointwise(a, r.s);
-    launch_wgrad(dy0, C, d1, o, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.ow), false, false, r.s, 0, 0, nullptr,
-                 r.wgrad_aux());
+    if (pg) {
+      PointwiseArgs a;
+      a.in0 = qs; a.ld0 = 32; a.c0 = 32; a.wpk = pk; a.w_batch_stride = 1024; a.out = o; a.batch = r.B; a.cout = 32; a.vox = vox;
+      launch_pointwise(a, r.s);
+      launch_wgrad(dy0, C, d1, o, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.ow), false, false, r.s, 0, 0, nullptr,
+                   r.wgrad_aux());
+    }
   }
-  r.release_wgrad_part(part);
-  ws->release(o);
+  if (pg) {
+    r.release_wgrad_part(part);
+    ws->release(o);
+  }
   // do = Wout^T dy0
   float* dO = ws->get<float>((size_t)rows * 32);
   const DgImg io = p->dg(W.ow);
@@ -367,24 +372,26 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   ws->release(pkT);
   ws->release(qs);
   // qkv = Wqkv xn
-  float* xn = ws->get<float>((size_t)rows * C);
+  float* xn = pg ? ws->get<float>((size_t)rows * C) : nullptr;
   float* dxn = ws->get<float>((size_t)rows * C);
   const DgImg iq = p->dg(W.qkv);
   float* wq = iq.pk ? nullptr : ws->get<float>(packed_weight_floats(96, C, 1));
-  part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, 96, C, 1));
+  part = pg ? r.wgrad_part(wgrad_partial_floats(vox, r.B, false, 96, C, 1)) : nullptr;
   if (!r.dry()) {
-    launch_gn_apply(t.x, xn, t.coefn, r.B, C, vox, 0, nullptr, nullptr, 0, nullptr, r.s);
-    launch_wgrad(dqkv, 96, d1, xn, C, C, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.qkv), false, false, r.s, 0, 0, nullptr,
-                 r.wgrad_aux());
+    if (pg) {
+      launch_gn_apply(t.x, xn, t.coefn, r.B, C, vox, 0, nullptr, nullptr, 0, nullptr, r.s);
+      launch_wgrad(dqkv, 96, d1, xn, C, C, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.qkv), false, false, r.s, 0, 0, nullptr,
+                   r.wgrad_aux());
+    }
     if (!iq.pk) launch_pack_weights(p->raw(W.qkv), wq, C, 96, 1, true, r.s);
     PointwiseArgs a;
     a.in0 = dqkv; a.ld0 = 96; a.c0 = 96; a.wpk = iq.pk ? iq.pk : wq; a.out = dxn; a.batch = r.B; a.cout = C; a.vox = vox;
     launch_pointwise(a, r.s);
   }
   if (wq) ws->release(wq);
-  ws->release(xn);
+  if (pg) ws->release(xn);
   ws->release(dqkv);
-  r.release_wgrad_part(part);
+  if (pg) r.release_wgrad_part(part);
   float* dx = ws->get<float>((size_t)rows * C);
   if (!r.dry()) {
     launch_gn_backward(dxn, t.x, t.coefn, t.statn, p->raw(W.ng), dx, G.at(W.ng), G.at(W.nb), nullptr, 0, r.B, C, vox, 1, 0, scratch,
@@ -416,82 +423,100 @@ void point_dgrad_jobs(CdPlan* p, float* img, hipStream_t s) {
   p->dg_jobs_at = img;
 }
 
-// loss + all parameter gradients.  Returns nothing; grads (flat) and loss_out are written on the stream.
-void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, const float* sigma, const float* cond, double* loss_out,
-                     float* grads, hipStream_t s, int loss_type = 0) {
+// What the taped forward leaves for the backward pass: the tape, the network input and the arguments of its first launches.
+struct TapedForward {
+  TrainTape T;
+  InitConvArgs ia;
+  EmbedArgs ea;
+  const float* xn = nullptr;  // network input before c_in (data + sigma noise, or the caller's x)
+  double* lpart = nullptr;    // training: the loss partials
+  float* hf = nullptr;        // the head's input (the last ResnetBlock's output)
+};
+
+// Taped forward shared by cd_train_step (training: the input is data + sigma * noise, formed here) and cd_denoise_vjp (the
+// caller's x; no head output, no loss buffers).  Also packs this call's input-gradient weight images.
+void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const float* noise, const float* x, const float* sigma,
+                   const float* cond, TapedForward& f) {
   const CdUnetDesc& d = p->desc;
-  const int nres = p->nres;
-  const int zs = d.compress_z ? 2 : 1;
+  const int B = r.B;
   const Dims3 dims = p->shapes[0];
   const int64_t per = dims.vox(), n = (int64_t)B * per;
-  Run r{&p->ws, s, B, d.groups};
-  r.status = p->status_word;
   Arena* ws = r.ws;
-  Grads G{p, grads};
-  TrainTape T;
-  // this step's input-gradient weight images (plan.hip: dgrad_images), for the whole step
+  hipStream_t s = r.s;
+  TrainTape& T = f.T;
+  // this call's input-gradient weight images (plan.hip: dgrad_images), for the whole call
   float* dg_img = ws->get<float>(p->dg_floats);
   p->dg_images = dg_img;
-  // ---- forward ----
-  float* xn = ws->get<float>((size_t)n);
-  T.x0 = ws->get<float>((size_t)n);
-  double* lpart = ws->get<double>((size_t)B + 8);
+  float* xn = training ? ws->get<float>((size_t)n) : nullptr;
+  f.xn = training ? xn : x;
+  if (training) {
+    T.x0 = ws->get<float>((size_t)n);
+    f.lpart = ws->get<double>((size_t)B + 8);
+  }
   T.emb = ws->get<float>((size_t)B * p->emb_ld);
   T.scal = ws->get<float>((size_t)B * 4);
   T.h0 = ws->get<float>((size_t)n * d.layer_sizes[0]);
-  InitConvArgs ia;
-  ia.x = xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = T.scal; ia.scale_stride = 4; ia.use_rz = d.rz_input; ia.use_phi = d.phi_input;
+  InitConvArgs& ia = f.ia;
+  ia.x = f.xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = T.scal; ia.scale_stride = 4; ia.use_rz = d.rz_input; ia.use_phi = d.phi_input;
   ia.r_w = p->d_coords; ia.z_d = p->d_coords + d.grid[2]; ia.phi_h = p->d_coords + d.grid[2] + d.grid[0];
   ia.wpk = p->packed(p->init_w); ia.bias = p->raw(p->init_b); ia.out = T.h0; ia.batch = B; ia.cout = d.layer_sizes[0]; ia.dims = dims;
   ia.coord_table = p->d_init_table; ia.table_ready = true; ia.status = r.status;
-  const EmbedArgs ea = embed_args(p, B, cond, sigma, d.time_embed_kind, T.emb, T.scal);
+  f.ea = embed_args(p, B, cond, sigma, d.time_embed_kind, T.emb, T.scal);
   if (!r.dry()) {
     if (!p->dg_jobs.empty()) {  // the images of all convolutions in two launches
       point_dgrad_jobs(p, dg_img, s);
       launch_pack_jobs(p->d_dg_jobs, (int)p->dg_jobs.size(), s);
       launch_pack_jobs_f16x2(p->d_dg_jobs, (int)p->dg_jobs.size(), s);
     }
-    launch_axpy_sigma(data, noise, sigma, xn, B, per, s);
-    launch_embed(ea, s);
+    if (training) launch_axpy_sigma(data, noise, sigma, xn, B, per, s);
+    launch_embed(f.ea, s);
     launch_init_conv(ia, s);
   }
-  float* hf = unet_body_train(p, r, T.emb, T.h0, T);
-  if (!r.dry()) {
-    HeadArgs ha;
-    ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = T.x0; ha.batch = B; ha.vox = per;
-    ha.x = xn; ha.scal = T.scal; ha.objective = d.objective;
-    launch_head(ha, s);
-    launch_loss_partial(T.x0, data, noise, sigma, lpart, B, per, s, loss_type, d.objective);
-    launch_loss_final(lpart, sigma, loss_out, B, per, s, loss_type, d.objective);
-  }
-  // ---- backward ----
-  // the GroupNorm layers queue their parameter-gradient reductions (per-sample sums in `qsums`), one launch flushes them at the end
-  // ... and the weight gradients queue the reductions of their per-workgroup partials (65 launches of 4-7 us otherwise), each
-  // partial in a workspace block of its own until then (Run::wgrad_part)
+  f.hf = unet_body_train(p, r, T.emb, T.h0, T);
+}
+
+// State of one backward pass: the GroupNorm layers queue their parameter-gradient reductions (per-sample sums in `qsums`), one
+// launch flushes them at the end; the weight gradients queue the reductions of their per-workgroup partials (65 launches of 4-7 us
+// otherwise), each partial in a workspace block of its own until then (Run::wgrad_part).
+struct BackwardState {
   WgradReduceQueue wq;
-  static const bool no_wq = getenv("CD_NO_WGRAD_QUEUE") != nullptr;
-  if (!no_wq) r.wq = &wq;
   GnParamQueue gq;
+  float* qsums = nullptr;
+  float* demb = nullptr;  // gradient of the (B, emb_ld) block embeddings
+  float* g = nullptr;     // (B, vox, 32) gradient at the head input, for the head's backward to fill
+};
+void begin_backward(CdPlan* p, Run& r, BackwardState& bs) {
+  const CdUnetDesc& d = p->desc;
+  const int nres = p->nres, B = r.B;
+  const int64_t n = (int64_t)B * p->shapes[0].vox();
+  Arena* ws = r.ws;
+  static const bool no_wq = getenv("CD_NO_WGRAD_QUEUE") != nullptr;
+  if (!no_wq && r.param_grads) r.wq = &bs.wq;
   int cmax = 32;
   for (int i = 0; i <= nres; ++i) cmax = d.layer_sizes[i] > cmax ? d.layer_sizes[i] : cmax;
   const size_t nsums = (size_t)GnParamJobs::kMax * 2 * B * cmax * 4;
-  float* qsums = ws->get<float>(nsums);
-  gq.sums = gq.next_sums = qsums;
-  gq.sums_end = qsums + nsums;
-  r.gq = &gq;
+  bs.qsums = ws->get<float>(nsums);
+  bs.gq.sums = bs.gq.next_sums = bs.qsums;
+  bs.gq.sums_end = bs.qsums + nsums;
+  bs.gq.discard = !r.param_grads;  // (the GroupNorm input gradient still needs its per-sample sums: only their reduction goes)
+  r.gq = &bs.gq;
   // demb, and behind it the step's max-|x| words (launch_absmax_bits, launch_gn_backward): one memset zeroes both.  A convolution's
   // backward measures at most two tensors, a GroupNorm backward one: fewer words than weight tensors, twice that is plenty.  (The
   // whole is a multiple of 64 floats: a fill of any other size is two launches.)
   const size_t nemb = (size_t)B * p->emb_ld, nclear = (nemb + 2 * p->weights.size() + 63) & ~(size_t)63;
-  float* demb = ws->get<float>(nclear);
-  if (!r.dry()) r.amax = AbsmaxWords{(unsigned*)(demb + nemb), (unsigned*)(demb + nclear)};
-  float* g = ws->get<float>((size_t)n * 32);
-  float* hpart = ws->get<float>((size_t)head_bwd_blocks(B, per) * 33);
-  if (!r.dry()) {
-    CD_HIP(hipMemsetAsync(demb, 0, sizeof(float) * nclear, s));
-    launch_head_loss_bwd(T.x0, data, noise, T.scal, hf, p->raw(p->head_w), g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
-                         loss_type, d.objective);
-  }
+  bs.demb = ws->get<float>(nclear);
+  if (!r.dry()) r.amax = AbsmaxWords{(unsigned*)(bs.demb + nemb), (unsigned*)(bs.demb + nclear)};
+  bs.g = ws->get<float>((size_t)n * 32);
+  if (!r.dry()) CD_HIP(hipMemsetAsync(bs.demb, 0, sizeof(float) * nclear, r.s));
+}
+
+// The body's backward: from the gradient at the head input (consumed) down to the gradient at the init conv's output (returned)
+float* body_backward(CdPlan* p, Run& r, const TrainTape& T, float* g, const Grads& G, float* demb) {
+  const CdUnetDesc& d = p->desc;
+  const int nres = p->nres, B = r.B;
+  const int zs = d.compress_z ? 2 : 1;
+  Arena* ws = r.ws;
+  hipStream_t s = r.s;
   auto step = [&](float* ng, float*& cur) {  // replace the running gradient
     ws->release(cur);
     cur = ng;
@@ -543,32 +568,43 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
     step(res_block_bwd(r, p, T.down_r2[i], g, G, demb), g);
     step(res_block_bwd(r, p, T.down_r1[i], g, G, demb), g);
   }
-  // init conv: weight and bias gradients only (its input is data)
+  return g;
+}
+
+// The init conv's weight and bias gradients from g (its output gradient, released here), then every queued reduction and the
+// conditioning MLPs' backward
+void finish_param_grads(CdPlan* p, Run& r, const TapedForward& f, float* g, const Grads& G, BackwardState& bs) {
+  const CdUnetDesc& d = p->desc;
+  const int B = r.B;
+  const int64_t per = p->shapes[0].vox();
+  Arena* ws = r.ws;
+  hipStream_t s = r.s;
+  float* demb = bs.demb;
   static const bool init_scalar = getenv("CD_INIT_WGRAD_SCALAR") != nullptr;
   if (init_scalar) {
     float* ipart = ws->get<float>(init_wgrad_partial_floats(B, per, d.in_channels, d.layer_sizes[0]));
-    if (!r.dry()) launch_init_wgrad(ia, g, ipart, G.at(p->init_w), s);
+    if (!r.dry()) launch_init_wgrad(f.ia, g, ipart, G.at(p->init_w), s);
     ws->release(ipart);
   } else {
     float* iscr = ws->get<float>(init_wgrad_mfma_floats(B, per, d.layer_sizes[0]));
-    if (!r.dry()) launch_init_wgrad_mfma(ia, g, iscr, G.at(p->init_w), s, &r.amax);
+    if (!r.dry()) launch_init_wgrad_mfma(f.ia, g, iscr, G.at(p->init_w), s, &r.amax);
     ws->release(iscr);
   }
   bias_grad(r, g, d.layer_sizes[0], per, G.at(p->init_b));
   ws->release(g);
-  if (!r.dry()) launch_gn_param_jobs(gq.jobs, s);  // every GroupNorm layer's dgamma / dbeta / conv-bias gradient: one launch
+  if (!r.dry()) launch_gn_param_jobs(bs.gq.jobs, s);  // every GroupNorm layer's dgamma / dbeta / conv-bias gradient: one launch
   r.gq = nullptr;
   if (!r.dry() && r.wq) wgrad_queue_flush(r.wq, s);  // every queued slot reduction: one launch
   for (float* part : r.wq_held) ws->release(part);
   r.wq_held.clear();
   r.wq = nullptr;
-  ws->release(qsums);
+  ws->release(bs.qsums);
   // conditioning MLPs
   const int half = d.cond_dim / 2, hidden = d.cond_size > half / 2 ? d.cond_size : half / 2, q = half / 2;
   const EmbedTapeLayout L = embed_tape_layout(d.cond_size, hidden, half);
   float* etape = ws->get<float>((size_t)B * L.total);
   if (!r.dry()) {
-    launch_embed_bwd(ea, demb, etape, s);
+    launch_embed_bwd(f.ea, demb, etape, s);
     std::vector<LinearWgradJob>& jobs = p->lin_jobs_host;
     jobs.clear();
     auto add = [&](int off_delta, int off_in, int widx, int bidx, int nout, int nin) {
@@ -591,5 +627,69 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
     CD_REQUIRE(jobs.size() <= 64, "too many linear layers");
     CD_HIP(hipMemcpyAsync(p->d_lin_jobs, jobs.data(), sizeof(LinearWgradJob) * jobs.size(), hipMemcpyHostToDevice, s));
     launch_linear_wgrad(p->d_lin_jobs, (int)jobs.size(), max_elems, B, s);
+  }
+}
+
+// loss + all parameter gradients.  Returns nothing; grads (flat) and loss_out are written on the stream.
+void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, const float* sigma, const float* cond, double* loss_out,
+                     float* grads, hipStream_t s, int loss_type = 0) {
+  const CdUnetDesc& d = p->desc;
+  const int64_t per = p->shapes[0].vox();
+  Run r{&p->ws, s, B, d.groups};
+  r.status = p->status_word;
+  Grads G{p, grads};
+  TapedForward f;
+  taped_forward(p, r, true, data, noise, nullptr, sigma, cond, f);
+  const TrainTape& T = f.T;
+  if (!r.dry()) {
+    HeadArgs ha;
+    ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = T.x0; ha.batch = B; ha.vox = per;
+    ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective;
+    launch_head(ha, s);
+    launch_loss_partial(T.x0, data, noise, sigma, f.lpart, B, per, s, loss_type, d.objective);
+    launch_loss_final(f.lpart, sigma, loss_out, B, per, s, loss_type, d.objective);
+  }
+  BackwardState bs;
+  begin_backward(p, r, bs);
+  float* hpart = r.ws->get<float>((size_t)head_bwd_blocks(B, per) * 33);
+  if (!r.dry())
+    launch_head_loss_bwd(T.x0, data, noise, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
+                         loss_type, d.objective);
+  float* g = body_backward(p, r, T, bs.g, G, bs.demb);
+  // init conv: weight and bias gradients only (its input is data)
+  finish_param_grads(p, r, f, g, G, bs);
+}
+
+// Vector-Jacobian product of cd_denoise: dx = (dD/dx)^T gy and, with grads, every parameter's gradient (the taped forward is
+// recomputed from x).  Without grads (param_grads false) no weight, bias, GroupNorm-parameter or embedding work is launched; the
+// input-gradient path is the same launches either way, so dx is the same bits.
+void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,
+                      bool param_grads, hipStream_t s) {
+  const CdUnetDesc& d = p->desc;
+  const Dims3 dims = p->shapes[0];
+  const int64_t per = dims.vox();
+  Run r{&p->ws, s, B, d.groups};
+  r.status = p->status_word;
+  r.param_grads = param_grads;
+  Grads G{p, grads};
+  TapedForward f;
+  taped_forward(p, r, false, nullptr, nullptr, x, sigma, cond, f);
+  const TrainTape& T = f.T;
+  BackwardState bs;
+  begin_backward(p, r, bs);
+  float* hpart = param_grads ? r.ws->get<float>((size_t)head_bwd_blocks(B, per) * 33) : nullptr;
+  if (!r.dry())
+    launch_head_vjp(gy, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, param_grads ? G.at(p->head_w) : nullptr,
+                    param_grads ? G.at(p->head_b) : nullptr, B, per, d.objective, s);
+  float* g = body_backward(p, r, T, bs.g, G, bs.demb);
+  // init conv: the data channel's input gradient, the preconditioning folded in (the coordinate channels are constants)
+  if (!r.dry())
+    launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], gy, T.scal, d.objective, dx, B, dims, s);
+  if (param_grads) {
+    finish_param_grads(p, r, f, g, G, bs);
+  } else {
+    r.ws->release(g);
+    r.gq = nullptr;
+    r.ws->release(bs.qsums);
   }
 }

@@ -101,6 +101,8 @@ _SIGNATURES = {
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "cd_plan_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cd_denoise_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),
@@ -489,6 +491,41 @@ class UnetEngine:
         _check(self.lib.cd_train_step(self.plan, B, data.data_ptr(), noise.data_ptr(), sigma.data_ptr(), cond.data_ptr(),
                                       LOSS_TYPES[loss_type], loss.data_ptr(), flat.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return loss, flat
+
+    def vjp_workspace(self, batch: int, with_param_grads: bool) -> torch.Tensor:
+        """Workspace of cd_denoise_vjp (one kept: the last batch size and mode asked for)."""
+        key = (int(batch), bool(with_param_grads))
+        ws = getattr(self, "_vws", {}).get(key)
+        if ws is None:
+            nbytes = C.c_size_t()
+            _check(self.lib.cd_plan_vjp_workspace_bytes(self.plan, batch, int(bool(with_param_grads)), C.byref(nbytes)))
+            self._vws = {}  # (release the previous one before allocating the next)
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            self._vws = {key: ws}
+        return ws
+
+    def denoise_vjp(self, x, sigma, cond, gy, param_grads: bool):
+        """Vector-Jacobian product of denoise (cd_denoise_vjp): dx = dL/dx for gy = dL/dD, and with ``param_grads`` the
+        gradient of every parameter as a flat fp32 buffer (see grad_layout), else None.  sigma and cond are constants."""
+        x, cond, gy = _dev32(x, "x"), _dev32(cond, "cond"), _dev32(gy, "gy")
+        B = x.shape[0]
+        sigma = _dev32(sigma, "sigma").reshape(-1)
+        if sigma.numel() == 1 and B > 1:
+            sigma = sigma.expand(B).contiguous()
+        if (tuple(x.shape[1:]) != (1,) + self.grid or gy.shape != x.shape or sigma.numel() != B
+                or cond.shape != (B, self.unet.cond_size)):
+            raise ValueError(f"denoise_vjp shapes: x {tuple(x.shape)}, gy {tuple(gy.shape)}, sigma {tuple(sigma.shape)}, "
+                             f"cond {tuple(cond.shape)}")
+        self.sync_weights()
+        ws = self.vjp_workspace(B, param_grads)
+        dx = torch.empty_like(x)
+        flat = None
+        if param_grads:
+            _, total = self.grad_layout()
+            flat = torch.empty(total, dtype=torch.float32, device=x.device)
+        _check(self.lib.cd_denoise_vjp(self.plan, B, x.data_ptr(), sigma.data_ptr(), cond.data_ptr(), gy.data_ptr(), dx.data_ptr(),
+                                       _ptr(flat), ws.data_ptr(), ws.numel(), _stream()))
+        return dx, flat
 
     def param_grads(self, flat):
         """Views of the flat gradient buffer, one per parameter of the bound CondUnet, in .parameters() order."""

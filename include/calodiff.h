@@ -229,6 +229,20 @@ int cd_train_step(CdPlan* plan, int batch, const float* data, const float* noise
                   int loss_type /* CD_LOSS_* */, double* loss_out, float* grads, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* ---- differentiable denoise ------------------------------------------------------------------------------------------ */
+/* Workspace of cd_denoise_vjp at this batch: with_param_grads 0 sizes the input-gradient-only call (grads == NULL), which needs
+ * less; 1 sizes the call that also writes grads.  Same restrictions as cd_plan_train_workspace_bytes. */
+int cd_plan_vjp_workspace_bytes(CdPlan* plan, int batch, int with_param_grads, size_t* bytes);
+/* Vector-Jacobian product of cd_denoise (the reference's CaloDiffusion.denoise, models/calodiffusion.py:154-169, under
+ * torch autograd): given D = denoise(x, sigma, cond) and an upstream gradient gy = dL/dD (B,1,D,H,W), writes dx = dL/dx
+ * (B,1,D,H,W) and, when grads is not NULL, dL/dW of every parameter into the flat buffer laid out as cd_plan_grad_layout says
+ * (overwritten, not accumulated).  sigma and cond are constants: no gradient is formed for them.  The forward is recomputed
+ * (taped) inside the call; arithmetic, range flag and restrictions are those of cd_train_step (Linear time/cond embeddings).
+ * With grads == NULL no parameter-gradient work is launched and dx is bitwise the dx of the call with grads.  All scratch is
+ * in `workspace` (cd_plan_vjp_workspace_bytes); nothing is allocated and the stream is not synchronised. */
+int cd_denoise_vjp(CdPlan* plan, int batch, const float* x, const float* sigma, const float* cond, const float* gy,
+                   float* dx, float* grads /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* torch.optim.Adam step (train/train.py:144: Adam(model.parameters(), lr); no amsgrad) over n tensors in ceil(n / 48)
  * launches: params / grads / exp_avg / exp_avg_sq are HOST arrays of n DEVICE pointers, numel their lengths.  step is the
  * 1-based step count after this update (torch's state['step']).  Same element-wise formulas as torch:
