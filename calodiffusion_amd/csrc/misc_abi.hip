@@ -1,0 +1,167 @@
+// Entry points outside the plan: the layer-energy MLP (forward, denoise, sampler, training step), the fused Adam step, the
+// reverse normalisation, the convolution precision switch and the per-launch profiler.
+#include "plan_internal.h"
+
+#include <cstring>
+
+extern "C" {
+
+int cd_adam_step(int n, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                 const int64_t* numel, double lr, double beta1, double beta2, float eps, float weight_decay, int step, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(n >= 0 && (n == 0 || (params && grads && exp_avg && exp_avg_sq && numel)) && step >= 1, "bad argument");
+    for (int i0 = 0; i0 < n; i0 += 48) {
+      AdamChunk c{};
+      const int k = n - i0 < 48 ? n - i0 : 48;
+      int64_t mx = 0;
+      for (int j = 0; j < k; ++j) {
+        c.p[j] = params[i0 + j]; c.g[j] = grads[i0 + j]; c.m[j] = exp_avg[i0 + j]; c.v[j] = exp_avg_sq[i0 + j]; c.n[j] = numel[i0 + j];
+        CD_REQUIRE(c.p[j] && c.g[j] && c.m[j] && c.v[j] && c.n[j] >= 0, "adam: null tensor pointer");
+        if (c.n[j] > mx) mx = c.n[j];
+      }
+      launch_adam(c, k, mx, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+    }
+  });
+}
+
+int cd_reverse_norm(const float* voxels, const float* energy, const float* layerE, float* out, int batch, const int32_t dims[3],
+                    const float consts[6], float max_deposit, float ecut, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(voxels && energy && out && dims && consts && batch > 0, "bad argument");
+    ReverseNormArgs a;
+    a.voxels = voxels; a.energy = energy; a.layerE = layerE; a.out = out; a.batch = batch;
+    a.D = dims[0]; a.H = dims[1]; a.W = dims[2]; a.layer_mode = layerE ? 1 : 0;
+    a.logit_mean = consts[0]; a.logit_std = consts[1]; a.totalE_mean = consts[2]; a.totalE_std = consts[3];
+    a.layers_mean = consts[4]; a.layers_std = consts[5]; a.max_deposit = max_deposit; a.ecut = ecut;
+    launch_reverse_norm(a, (hipStream_t)stream);
+  });
+}
+
+int cd_reverse_norm_staged(const float* voxels, const float* energy, const float* layerE, float* out, int batch,
+                           const int32_t dims[3], const float consts[6], float max_deposit, float ecut, float alpha, float layer_eps,
+                           int stage, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(voxels && out && dims && consts && batch > 0 && stage >= 0 && stage <= 2, "bad argument");
+    CD_REQUIRE(stage == 1 || energy, "cd_reverse_norm_staged: stages 0 and 2 scale by the incident energies");
+    ReverseNormArgs a;
+    a.voxels = voxels; a.energy = energy; a.layerE = stage == 1 ? nullptr : layerE; a.out = out; a.batch = batch;
+    a.D = dims[0]; a.H = dims[1]; a.W = dims[2]; a.layer_mode = a.layerE ? 1 : 0;
+    a.logit_mean = consts[0]; a.logit_std = consts[1]; a.totalE_mean = consts[2]; a.totalE_std = consts[3];
+    a.layers_mean = consts[4]; a.layers_std = consts[5]; a.max_deposit = max_deposit; a.ecut = ecut;
+    a.stage = stage; a.alpha = alpha; a.layer_eps = layer_eps;
+    launch_reverse_norm(a, (hipStream_t)stream);
+  });
+}
+
+static void layer_mlp_call(const CdLayerMlpDesc* d, const float* const* weights, int n_weights, int batch, int mode,
+                           const float* x, const float* cond, const float* tsig, const float* table, int n_steps,
+                           const float* noise, float* out, float* xs, float* x0s, void* stream) {
+  CD_REQUIRE(d && weights && x && cond && out && batch > 0, "bad argument");
+  CD_REQUIRE(d->struct_size == sizeof(CdLayerMlpDesc), "CdLayerMlpDesc.struct_size does not match this library's calodiff.h");
+  CD_REQUIRE(d->n_res >= 0 && d->n_res <= 8 && n_weights == 2 * (8 + 3 * d->n_res),
+             "layer MLP: n_weights must be 2*(8 + 3*n_res) (time_mlp, cond_mlp, in_lay, blocks, out_lay)");
+  CD_REQUIRE(d->time_embed_kind >= 0 && d->time_embed_kind <= 2 && d->objective >= 0 && d->objective <= 2, "bad descriptor");
+  LayerMlpArgs a{};
+  for (int i = 0; i < n_weights; ++i) {
+    CD_REQUIRE(weights[i], "null weight pointer");
+    a.w[i] = weights[i];
+  }
+  a.dim_in = d->dim_in; a.hidden = d->hidden; a.cond_emb = d->cond_emb; a.cond_size = d->cond_size; a.n_res = d->n_res;
+  a.time_kind = d->time_embed_kind; a.objective = d->objective; a.mode = mode; a.batch = batch; a.n_steps = n_steps;
+  a.sigma_data = d->sigma_data;
+  a.x = x; a.cond = cond; a.tsig = tsig; a.table = table; a.noise = noise; a.out = out; a.xs = xs; a.x0s = x0s;
+  launch_layer_mlp(a, (hipStream_t)stream);
+}
+
+int cd_layer_forward(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* x,
+                     const float* cond, const float* time, float* out, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(time, "bad argument");
+    layer_mlp_call(desc, weights, n_weights, batch, 0, x, cond, time, nullptr, 1, nullptr, out, nullptr, nullptr, stream);
+  });
+}
+int cd_layer_denoise(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* x,
+                     const float* sigma, const float* cond, float* out, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(sigma, "bad argument");
+    layer_mlp_call(desc, weights, n_weights, batch, 1, x, cond, sigma, nullptr, 1, nullptr, out, nullptr, nullptr, stream);
+  });
+}
+int cd_layer_sample(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* start,
+                    const float* cond, const CdStep* steps_dev, int n_steps, const float* step_noise, float* x_out, float* xs,
+                    float* x0s, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(steps_dev && n_steps > 0, "bad argument");
+    layer_mlp_call(desc, weights, n_weights, batch, 2, start, cond, nullptr, (const float*)steps_dev, n_steps, step_noise,
+                   x_out, xs, x0s, stream);
+  });
+}
+
+static LayerMlpTrainArgs layer_train_args(const CdLayerMlpDesc* d, int batch) {
+  CD_REQUIRE(d && batch > 0, "bad argument");
+  CD_REQUIRE(d->struct_size == sizeof(CdLayerMlpDesc), "CdLayerMlpDesc.struct_size does not match this library's calodiff.h");
+  CD_REQUIRE(d->n_res >= 0 && d->n_res <= 8 && d->time_embed_kind >= 0 && d->time_embed_kind <= 2, "bad descriptor");
+  LayerMlpTrainArgs a{};
+  a.dim_in = d->dim_in; a.hidden = d->hidden; a.cond_emb = d->cond_emb; a.cond_size = d->cond_size; a.n_res = d->n_res;
+  a.time_kind = d->time_embed_kind; a.batch = batch; a.sigma_data = d->sigma_data;
+  a.layout = layer_tape_layout(a.dim_in, a.hidden, a.cond_emb, a.cond_size, a.n_res);
+  return a;
+}
+int cd_layer_train_workspace_bytes(const CdLayerMlpDesc* desc, int batch, size_t* bytes) {
+  return guarded([&] {
+    CD_REQUIRE(bytes, "bad argument");
+    *bytes = layer_train_workspace_bytes(layer_train_args(desc, batch));
+  });
+}
+int cd_layer_train_step(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
+                        const float* noise, const float* sigma, const float* cond, double* loss_out, float* grads,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return cd_layer_train_step_loss(desc, weights, n_weights, batch, data, noise, sigma, cond, CD_LOSS_L2, loss_out, grads, workspace,
+                                  workspace_bytes, stream);
+}
+
+int cd_layer_train_step_loss(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
+                             const float* noise, const float* sigma, const float* cond, int loss_type, double* loss_out,
+                             float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(weights && data && noise && sigma && cond && loss_out && grads && workspace, "bad argument");
+    CD_REQUIRE(loss_type >= CD_LOSS_L2 && loss_type <= CD_LOSS_HUBER, "loss_type must be one of CD_LOSS_L2 / L1 / MSE / HUBER");
+    LayerMlpTrainArgs a = layer_train_args(desc, batch);
+    a.loss_type = loss_type;
+    CD_REQUIRE(desc->objective == CD_OBJ_HYBRID, "cd_layer_train_step implements the hybrid_weight objective");
+    CD_REQUIRE(n_weights == 2 * (8 + 3 * desc->n_res), "layer MLP: n_weights must be 2*(8 + 3*n_res)");
+    CD_REQUIRE(workspace_bytes >= layer_train_workspace_bytes(a), "workspace too small: call cd_layer_train_workspace_bytes");
+    for (int i = 0; i < n_weights; ++i) {
+      CD_REQUIRE(weights[i], "null weight pointer");
+      a.w[i] = weights[i];
+    }
+    a.data = data; a.noise = noise; a.sigma = sigma; a.cond = cond;
+    launch_layer_mlp_train(a, grads, loss_out, workspace, (hipStream_t)stream);
+  });
+}
+
+int cd_set_conv_precision(const char* mode) {
+  return guarded([&] {
+    CD_REQUIRE(mode, "null argument");
+    if (!std::strcmp(mode, "f16x2")) set_conv_precision(PREC_F16X2);
+    else if (!std::strcmp(mode, "bf16x3")) set_conv_precision(PREC_BF16X3);
+    else if (!std::strcmp(mode, "f32")) set_conv_precision(PREC_F32);
+    else throw Fail{CD_EINVAL, std::string("unknown convolution precision '") + mode + "' (f16x2, bf16x3, f32)"};
+  });
+}
+const char* cd_get_conv_precision(void) {
+  static const char* names[3] = {"f16x2", "bf16x3", "f32"};
+  return names[conv_precision()];
+}
+
+int cd_profile_begin(void) {
+  return guarded([&] { prof::begin(); });
+}
+int cd_profile_end(char* json, int cap) {
+  return guarded([&] {
+    CD_REQUIRE(json && cap > 2, "bad argument");
+    if (prof::end(json, cap) < 0) throw Fail{CD_EINVAL, "profile buffer too small"};
+  });
+}
+
+}  // extern "C"

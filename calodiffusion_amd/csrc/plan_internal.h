@@ -1,0 +1,384 @@
+// Internal interface of the library's host units (plan.hip, forward.hip, sampler.hip, train.hip, ops.hip, misc_abi.hip): the
+// plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
+// every C-ABI entry point runs in.  The public ABI is include/calodiff.h.
+#pragma once
+#include "../../include/calodiff.h"
+#include "cd_common.h"
+
+#include <map>
+#include <string>
+#include <vector>
+
+namespace cd {
+
+// ------------------------------------------------------------------------------------------------------------
+// weight registry
+// ------------------------------------------------------------------------------------------------------------
+enum PackKind { PK_NONE = 0, PK_CONV = 1, PK_CONVT = 2, PK_INIT = 3 };
+struct WeightEntry {
+  std::string name;
+  int64_t numel = 0;
+  size_t raw_off = 0;   // floats into the arena
+  PackKind pack = PK_NONE;
+  int cin = 0, cout = 0, taps = 0;
+  size_t pk_off = 0;
+  size_t pk3_off = 0;  // split-bf16 image of 3x3x3 convs (floats into the arena; 0 = none)
+  size_t grad_off = 0; // floats into the flat gradient buffer of cd_train_step
+  bool set = false;
+  // input-gradient images of the training step (dgrad_images below), floats into the step's image block; dg_mode 0 = none
+  int dg_mode = 0;
+  size_t dg_pk_off = 0, dg_pk3_off = 0;
+  bool dg_1x1 = false;  // a 1x1 conv kept raw for the forward (attention to_out: folded per sample) whose backward wants the image
+};
+// packed images a convolution's input gradient reads (conv_backward / conv_transpose_backward); null members: pack on the fly
+struct DgImg {
+  const float* pk = nullptr;
+  const void* pk3 = nullptr;
+};
+
+struct ResW {
+  int cin = 0, cout = 0;
+  bool has_mlp = false, has_res = false;
+  int c1w = -1, c1b = -1, n1g = -1, n1b = -1, c2w = -1, c2b = -1, n2g = -1, n2b = -1, mw = -1, mb = -1, rw = -1, rb = -1;
+  int emb_off = 0;
+};
+struct AttnW {
+  int c = 0;
+  int ng = -1, nb = -1, qkv = -1, ow = -1, ob = -1, gg = -1, gb = -1;
+};
+struct LevelW {
+  ResW r1, r2;
+  AttnW attn;
+  int sw = -1, sb = -1;  // down / up sampling conv
+};
+
+// ------------------------------------------------------------------------------------------------------------
+// workspace allocator: deterministic first-fit over the caller's workspace, replayed identically by a dry run
+// (to size the workspace) and by every real call (so captured graphs see stable addresses).
+// ------------------------------------------------------------------------------------------------------------
+class Arena {
+ public:
+  void reset(char* base, size_t cap, bool dry) {
+    base_ = base; cap_ = cap; dry_ = dry; high_ = 0;
+    blocks_.clear();
+    blocks_.push_back({0, (size_t)1 << 60, true});
+  }
+  void* alloc(size_t bytes) {
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (bytes == 0) bytes = 256;
+    for (size_t i = 0; i < blocks_.size(); ++i) {
+      if (blocks_[i].free && blocks_[i].size >= bytes) {
+        const size_t off = blocks_[i].off;
+        if (blocks_[i].size > bytes) {
+          Block rest{off + bytes, blocks_[i].size - bytes, true};
+          blocks_[i].size = bytes;
+          blocks_.insert(blocks_.begin() + i + 1, rest);
+        }
+        blocks_[i].free = false;
+        if (off + bytes > high_) high_ = off + bytes;
+        if (!dry_ && off + bytes > cap_) throw Fail{CD_EWORKSPACE, "workspace too small: call cd_plan_workspace_bytes for this batch size"};
+        return dry_ ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base_ + off);
+      }
+    }
+    throw Fail{CD_EWORKSPACE, "workspace allocator exhausted"};
+  }
+  template <typename T>
+  T* get(size_t count) { return (T*)alloc(count * sizeof(T)); }
+  void release(const void* p) {
+    if (!p) return;
+    const size_t off = dry_ ? (size_t)((uintptr_t)p - 0x1000) : (size_t)((const char*)p - base_);
+    for (size_t i = 0; i < blocks_.size(); ++i) {
+      if (blocks_[i].off == off && !blocks_[i].free) {
+        blocks_[i].free = true;
+        if (i + 1 < blocks_.size() && blocks_[i + 1].free) {
+          blocks_[i].size += blocks_[i + 1].size;
+          blocks_.erase(blocks_.begin() + i + 1);
+        }
+        if (i > 0 && blocks_[i - 1].free) {
+          blocks_[i - 1].size += blocks_[i].size;
+          blocks_.erase(blocks_.begin() + i);
+        }
+        return;
+      }
+    }
+    throw Fail{CD_EINVAL, "internal: release of unknown workspace block"};
+  }
+  size_t high() const { return high_; }
+  bool dry() const { return dry_; }
+
+ private:
+  struct Block { size_t off, size; bool free; };
+  std::vector<Block> blocks_;
+  char* base_ = nullptr;
+  size_t cap_ = 0, high_ = 0;
+  bool dry_ = false;
+};
+
+// A sampler entry point's cached step graph (cd_ddim_sample, cd_sampler_run: one each), valid while the call's key matches the
+// one it was captured under
+struct StepGraph {
+  struct Key {
+    int batch = 0, n_coef = 0, n_bufs = 0, noisy = 0; const void* ws = nullptr; const void* cond = nullptr; const void* x = nullptr;
+    const void* xs = nullptr; const void* x0s = nullptr; uint64_t ops_hash = 0;
+    int precision = 0;  // the captured kernels are those of the convolution precision in force at capture time
+    bool operator==(const Key& o) const {
+      return precision == o.precision && batch == o.batch && n_coef == o.n_coef && n_bufs == o.n_bufs && noisy == o.noisy && ws == o.ws &&
+             cond == o.cond && x == o.x && xs == o.xs && x0s == o.x0s && ops_hash == o.ops_hash;
+    }
+  } key;
+  hipGraphExec_t exec = nullptr;
+  hipGraphExec_t chunk = nullptr;  // several consecutive steps as ONE graph (same key): no gap between their launches
+  bool valid_for(const Key& k) const { return exec && key == k; }
+  void destroy() {
+    if (exec) {
+      hipGraphExecDestroy(exec);
+      exec = nullptr;
+    }
+    if (chunk) {
+      hipGraphExecDestroy(chunk);
+      chunk = nullptr;
+    }
+  }
+};
+
+}  // namespace cd
+
+using namespace cd;
+
+struct CdPlan {
+  CdUnetDesc desc{};
+  int nres = 0;
+  std::vector<Dims3> shapes;           // per level
+  std::vector<int> up_kz;              // per up step (i = 0 .. nres-2)
+  std::vector<Dims3> up_out;           // expected output dims of each up step
+  std::vector<WeightEntry> weights;
+  std::map<std::string, int> index;
+  float* arena = nullptr;
+  size_t arena_floats = 0;
+
+  int init_w = -1, init_b = -1, head_w = -1, head_b = -1;
+  int tw[3] = {-1, -1, -1}, tb[3] = {-1, -1, -1}, cw[3] = {-1, -1, -1}, cb[3] = {-1, -1, -1};
+  std::vector<LevelW> downs, ups;
+  ResW mid1, mid2, fin;
+  AttnW mid_attn;
+  int emb_ld = 0;
+  EmbedLayer* d_embed_layers = nullptr;
+  int n_embed_layers = 0;
+  std::vector<std::pair<int, int>> embed_list;  // (weight idx of mlp w, emb offset) in ResW order
+
+  float* d_coords = nullptr;  // r[W], z[D], phi[H]
+  float* d_init_table = nullptr;  // (vox, C0): coordinate-channel part + bias of the init conv (refresh_init_table)
+  bool coords_set = false;
+
+  // sampler state (device): step table, counter, stepvals
+  static constexpr int kMaxSteps = 4096;
+  static constexpr int kEmbedChunk = 16;  // sampler steps whose embeddings one launch computes ahead (cd_ddim_sample)
+  float* d_table = nullptr;
+  int* d_counter = nullptr;
+  float* d_stepvals = nullptr;
+  // device word the f16x2 kernels of the current call OR their range flag into: d_counter + 2 (the sticky word cd_plan_status
+  // reports) or, inside an entry point with its own bf16x3 fallback, d_counter + 3 (that call's private word)
+  int* status_word = nullptr;
+
+  // the samplers' step graphs are captured on a private stream (the caller's may be the legacy null stream, which cannot capture)
+  hipStream_t cap_stream = nullptr;
+  // job list of cd_plan_set_weights: host copy (with the callers' pointers of the last call) and device copy
+  std::vector<PackJob> pack_jobs;
+  PackJob* d_pack_jobs = nullptr;
+  // training: the re-packed (channel-transposed, tap-flipped) weight images of every convolution's input gradient, made by ONE
+  // job list per step (two launches) instead of two or three pack launches inside each conv_backward (118 launches per step).
+  // The images live in a block of the step's workspace (dg_floats, at dg_images during a step); the device job list points into
+  // the block at dg_jobs_at and is re-pointed when a step's block lies elsewhere (dg_jobs: host copy)
+  size_t dg_floats = 0;
+  std::vector<PackJob> dg_jobs;
+  PackJob* d_dg_jobs = nullptr;
+  const float* dg_jobs_at = nullptr;
+  const float* dg_images = nullptr;
+  DgImg dg(int i) const {
+    DgImg g;
+    const WeightEntry& w = weights[i];
+    if (dg_images && w.dg_mode) {
+      g.pk = dg_images + w.dg_pk_off;
+      if (w.dg_mode != 1) g.pk3 = dg_images + w.dg_pk3_off;
+    }
+    return g;
+  }
+  // barrier words of the co-operative attention (launch_attn_small, CD_ATTN_COOP): [kAttnCoopSamples][2]
+  unsigned* d_attn_sync = nullptr;
+  // the samplers' cached step graphs: cd_ddim_sample's (with a chunk graph of kEmbedChunk steps) and that of a uniform sampler
+  // program (cd_sampler_run; one-step graph only)
+  StepGraph ddim_graph, prog_graph;
+
+  // training: flat gradient layout and the device job list of the small Linear weight gradients
+  size_t grad_floats = 0;
+  std::vector<LinearWgradJob> lin_jobs_host;
+  LinearWgradJob* d_lin_jobs = nullptr;
+
+  Arena ws;
+
+  const float* raw(int i) const { return arena + weights[i].raw_off; }
+  const float* packed(int i) const { return arena + weights[i].pk_off; }
+  const void* packed3(int i) const { return weights[i].pk3_off ? (const void*)(arena + weights[i].pk3_off) : nullptr; }
+};
+
+namespace cd {
+
+// ------------------------------------------------------------------------------------------------------------
+// launch sequences
+// ------------------------------------------------------------------------------------------------------------
+struct Run {
+  Arena* ws;
+  hipStream_t s;
+  int B;
+  int groups;
+  int* status = nullptr;  // device word for sticky range flags (cd_plan_status), or null
+  GnParamQueue* gq = nullptr;  // training step: the GroupNorm layers' parameter-gradient reductions, flushed once at the end
+  // training step: the weight gradients' slot reductions, flushed once at the end (null: each runs where it arises), and the
+  // workspace blocks of their partials, held until that flush
+  WgradReduceQueue* wq = nullptr;
+  std::vector<float*> wq_held;
+  AbsmaxWords amax;  // zeroed words for max |x| (launch_absmax_bits, launch_gn_backward); none in a dry run
+  // backward passes: false = input gradients only (cd_denoise_vjp without grads): no weight / bias / GroupNorm-parameter work
+  bool param_grads = true;
+  bool dry() const { return ws->dry(); }
+  unsigned* amax_word() { return dry() ? nullptr : amax.take(); }
+  // partial buffer of one launch_wgrad; with a queue it stays taken until the flush, so one buffer per queued reduction
+  float* wgrad_part(size_t floats) {
+    float* part = ws->get<float>(floats);
+    if (wq) wq_held.push_back(part);
+    return part;
+  }
+  void release_wgrad_part(float* part) {
+    if (!wq) ws->release(part);
+  }
+  WgradAux wgrad_aux(const unsigned* gmax = nullptr, const unsigned* xmax = nullptr) {
+    WgradAux a;
+    a.queue = wq; a.words = &amax; a.gmax = gmax; a.xmax = xmax;
+    return a;
+  }
+};
+
+// weights of one block resolved to device pointers (conv weights in packed MFMA layout)
+struct ResP {
+  int cin = 0, cout = 0;
+  bool has_res = false;
+  const float *c1w = nullptr, *c1b = nullptr, *n1g = nullptr, *n1b = nullptr;
+  const void *c1w3 = nullptr, *c2w3 = nullptr;  // split-bf16 images of the two 3x3x3 convs
+  const float *c2w = nullptr, *c2b = nullptr, *n2g = nullptr, *n2b = nullptr;
+  const float *rw = nullptr, *rb = nullptr;
+  const void* rw16 = nullptr;  // f16x2 image of the 1x1 shortcut conv
+  const float* emb = nullptr;  // (B, emb_ld) slice for this block, or null
+  int emb_ld = 0;
+};
+struct AttnP {
+  int c = 0;
+  const float *ng = nullptr, *nb = nullptr, *qkv = nullptr, *ow = nullptr, *ob = nullptr, *gg = nullptr, *gb = nullptr;
+  const void* qkv16 = nullptr;  // f16x2 image of to_qkv (fused attention kernels)
+  unsigned* coop_sync = nullptr;  // the plan's barrier words of the co-operative form (launch_attn_small), or null
+};
+
+ResP resolve(const CdPlan* p, const ResW& w, const float* emb);
+AttnP resolve(const CdPlan* p, const AttnW& w);
+
+// Options of the sampler loop (cd_ddim_sample): embeddings / scalings already in place (computed a chunk of steps ahead), and the
+// sampler's update of the running sample fused into the head kernel.
+struct FwdOpts {
+  float* emb_pre = nullptr;   // (B, emb_ld) ready-made: no embedding launch
+  float* scal_pre = nullptr;  // (B, 4)
+  const HeadArgs* upd = nullptr;  // only the upd_* fields are read
+};
+
+// forward.hip
+struct LazyClose;
+float* stats_pass(Run& r, const float* x, int C, int64_t vox, int* units);
+float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1, const float* wpk, const void* wpk3,
+                        const float* bias, float* out, int cout, Dims3 dims, const float* coef_in, int* units,
+                        const GnDefer* defer_in = nullptr, float* coef_buf = nullptr, const ConvFusion::GnOut* gn_out = nullptr);
+float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
+                 float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr);
+float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpart = nullptr, int xunits = 0);
+void bias_grad(Run& r, const float* dy, int C, int64_t vox, float* db);
+void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, const float* w_raw, const float* dy, float* dx,
+                   float* dw, float* db, int cout, const ConvGeom& g, const DgImg* img = nullptr, const float* xcoef = nullptr,
+                   const float* dx_add = nullptr, int* dx_added = nullptr, const unsigned* dy_max = nullptr);
+void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const float* dy, float* dx, float* dw, float* db, int c,
+                             Dims3 din, Dims3 dout, int kz, int sz, const DgImg* img = nullptr);
+EmbedArgs embed_args(CdPlan* p, int B, const float* cond, const float* t, int kind, float* emb, float* scal);
+void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const float* t, float* out, bool raw, hipStream_t s,
+                  const FwdOpts* opt = nullptr);
+// plan.hip
+void check_ready(CdPlan* p, bool need_coords);
+
+// Every C-ABI entry point runs inside guarded().  The launchers check `hipGetLastError()` after each launch, and that call
+// reports the thread's LAST error whoever set it -- a HIP call that failed earlier in the process (another library's, the
+// caller's own, or a previous entry point of this one) would otherwise fail the first unrelated launch here (round 3:
+// a refused hipEventElapsedTime surfaced as "cd_randn: invalid resource handle").  So the error state is cleared on the way
+// in, and again on the way out of a failed call.
+template <typename F>
+int guarded(F&& f) {
+  (void)hipGetLastError();
+  try {
+    f();
+    return CD_OK;
+  } catch (const Fail& e) {
+    (void)hipGetLastError();
+    set_error(e.msg);
+    return e.code;
+  } catch (const std::exception& e) {
+    (void)hipGetLastError();
+    set_error(std::string("internal error: ") + e.what());
+    return CD_EINVAL;
+  }
+}
+
+// High-water mark of a dry run of the forward's allocation sequence (after `front`, the caller's own blocks).  The sequence
+// depends on the convolution precision (whole-block launches, fused / unfused attention), and a range fallback re-runs a call
+// in bf16x3 on the SAME workspace: the answer is the larger of the precision in force and the fallback's.
+template <typename F>
+size_t dry_forward_bytes(CdPlan* plan, int batch, F&& front) {
+  struct Restore {
+    ~Restore() { set_conv_precision_override(-1); }
+  } restore;
+  size_t need = 0;
+  // (all three arithmetic modes, not only the one in force and the fallback's: cd_set_conv_precision may switch after the caller
+  // sized -- and cached -- its workspace)
+  for (int mode : {(int)PREC_F16X2, (int)PREC_BF16X3, (int)PREC_F32}) {
+    set_conv_precision_override(mode);
+    plan->ws.reset(nullptr, 0, true);
+    front();
+    forward_impl(plan, batch, nullptr, nullptr, nullptr, nullptr, false, nullptr);
+    need = plan->ws.high() > need ? plan->ws.high() : need;
+  }
+  return need;
+}
+
+// Range fallback of the entry points that promise finite results (the samplers, cd_denoise_safe): `run(eager)` enqueues the
+// whole call.  The f16x2 kernels of THIS call raise bit 0 of a private word (d_counter + 3, cleared first), so a flag left in
+// the sticky word by an earlier, un-queried cd_denoise / cd_unet_forward / cd_train_step is neither mistaken for this call's
+// overflow nor lost.  If the call left the fp16 range it is run again with the exact bf16x3 convolutions (full fp32 range;
+// eagerly, a cached step graph holds the f16x2 kernels) -- the precision is overridden for THIS THREAD only, other plans /
+// threads of the process keep their kernels -- and bit 1 is OR-ed into the sticky word.  Returns whether the fallback ran.
+template <typename F>
+bool run_with_range_fallback(CdPlan* plan, hipStream_t s, F&& run, bool report_sticky = true) {
+  struct Restore {
+    CdPlan* p;
+    ~Restore() {
+      p->status_word = p->d_counter + 2;
+      set_conv_precision_override(-1);
+    }
+  } restore{plan};
+  plan->status_word = plan->d_counter + 3;
+  CD_HIP(hipMemsetAsync(plan->d_counter + 3, 0, sizeof(int), s));
+  run(false);
+  if (conv_precision() != PREC_F16X2) return false;
+  int flags = 0;
+  CD_HIP(hipMemcpyAsync(&flags, plan->d_counter + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+  CD_HIP(hipStreamSynchronize(s));
+  if (!(flags & 1)) return false;
+  set_conv_precision_override(PREC_BF16X3);
+  run(true);
+  if (report_sticky) launch_or_word(plan->d_counter + 2, 2, s);
+  return true;
+}
+
+}  // namespace cd

@@ -1,11 +1,16 @@
-// Training step: forward with a tape of saved activations, then the backward pass (textually included by plan.hip, inside
-// its anonymous namespace).  Reference: TrainDiffusion.training_loop body (train/train_diffusion.py:52-63) =
+// Training step and the denoise VJP (cd_train_step, cd_denoise_vjp): forward with a tape of saved activations, then the
+// backward pass.  Reference: TrainDiffusion.training_loop body (train/train_diffusion.py:52-63) =
 // Diffusion.compute_loss -> hybrid_weight.loss_function (loss.py:163-179) -> denoise -> CondUnet.forward, then
 // loss.backward().  torch autograd is replaced by the explicit chain below; gradients land in a flat buffer in the plan's
 // weight order (cd_plan_grad_layout) and are exposed to torch.optim through calodiffusion_amd.engine.
 //
 // Nothing is released between forward and backward (the tape owns the activations); temporaries of the backward are
 // released as soon as they are consumed, the weight gradients' partials once their queued reductions have been launched.
+#include "plan_internal.h"
+
+#include <cstdlib>
+
+namespace cd {
 
 struct ResTape {
   const ResW* w = nullptr;
@@ -403,7 +408,7 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   return dx;
 }
 
-// the device job list of dgrad_images (plan.hip) pointed at this step's images block `img`: a copy only when the block has moved
+// the device job list of dgrad_images (below) pointed at this step's images block `img`: a copy only when the block has moved
 // (the engine keeps one training workspace per batch size)
 void point_dgrad_jobs(CdPlan* p, float* img, hipStream_t s) {
   if (p->dg_jobs_at == img) return;
@@ -444,7 +449,7 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
   Arena* ws = r.ws;
   hipStream_t s = r.s;
   TrainTape& T = f.T;
-  // this call's input-gradient weight images (plan.hip: dgrad_images), for the whole call
+  // this call's input-gradient weight images (dgrad_images below), for the whole call
   float* dg_img = ws->get<float>(p->dg_floats);
   p->dg_images = dg_img;
   float* xn = training ? ws->get<float>((size_t)n) : nullptr;
@@ -693,3 +698,103 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
     r.ws->release(bs.qsums);
   }
 }
+
+// The weight images every convolution's INPUT gradient reads (the forward kernels run on channel-transposed, tap-flipped weights:
+// conv_backward / conv_transpose_backward), laid out once per plan (dg_floats) and described by one job list whose sources are the
+// plan's own raw copies of the tensors; the images themselves go to a block of each step's workspace (train_step_impl re-points
+// the list when that block moves, and launches it once per step).  The packers write every float of every image, and the
+// alignment gaps between the images are never read: the block needs no clearing.  dg_mode: 1 = 1x1 conv (f32 image,
+// transposed), 2 = 3x3x3 stride 1 (f32 + split16 images, transposed + flipped), 3 = strided down conv (f32 + f16x2 images,
+// transposed: its adjoint is the up-conv gather kernel), 4 = up conv (f32 + split16 images of the tensor read as a plain conv:
+// its adjoint is the strided conv).
+static void dgrad_images(CdPlan* p) {
+  if (p->d_dg_jobs) return;
+  size_t off = 0;
+  auto bump = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
+  std::vector<PackJob> jobs;
+  for (auto& w : p->weights) {
+    if (w.pack != PK_CONV && w.pack != PK_CONVT && !w.dg_1x1) continue;
+    PackJob j{};
+    j.kind = 1;
+    j.taps = w.taps;
+    if (w.pack == PK_CONVT) {
+      w.dg_mode = 4;
+      j.cout = w.cout; j.cin = w.cin;
+    } else {
+      w.dg_mode = w.taps == 1 ? 1 : (w.taps == 27 ? 2 : 3);
+      j.cout = w.cin; j.cin = w.cout;  // the gradient's convolution maps the conv's output channels back to its input channels
+      j.tr = 1;
+      j.flip = w.dg_mode == 2 ? 1 : 0;
+    }
+    if (j.cin % 32 || j.cout % 32) {  // (the init conv's 3 / 4 input channels never need an input gradient)
+      w.dg_mode = 0;
+      continue;
+    }
+    w.dg_pk_off = bump(packed_weight_floats(j.cin, j.cout, w.taps));
+    const unsigned long long n16 = (unsigned long long)(j.cin / 16) * w.taps * ((j.cout + 31) / 32) * 64;
+    if (w.dg_mode == 2 || w.dg_mode == 4) w.dg_pk3_off = bump(packed_split16_bytes(j.cin, j.cout, w.taps) / 4);
+    else if (w.dg_mode == 3) w.dg_pk3_off = bump(packed_f16x2_bytes(j.cin, j.cout, w.taps) / 4 + 64);
+    j.n_pk = packed_weight_floats(j.cin, j.cout, w.taps);
+    if (w.dg_mode == 2 || w.dg_mode == 4) j.n_bf3 = j.n_f16 = n16;
+    else if (w.dg_mode == 3) j.n_f16 = n16;
+    jobs.push_back(j);
+  }
+  size_t k = 0;
+  for (auto& w : p->weights)
+    if (w.dg_mode) jobs[k++].src = p->arena + w.raw_off;
+  p->dg_floats = off;
+  p->dg_jobs = jobs;
+  CD_HIP(hipMalloc((void**)&p->d_dg_jobs, sizeof(PackJob) * (jobs.size() + 1)));
+}
+
+}  // namespace cd
+
+extern "C" {
+
+int cd_plan_train_workspace_bytes(CdPlan* plan, int batch, size_t* bytes) {
+  return guarded([&] {
+    CD_REQUIRE(plan && bytes && batch > 0, "bad argument");
+    CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the training step needs the Linear time/cond embeddings");
+    dgrad_images(plan);
+    plan->ws.reset(nullptr, 0, true);
+    train_step_impl(plan, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    *bytes = plan->ws.high() + 4096;
+  });
+}
+
+int cd_train_step(CdPlan* plan, int batch, const float* data, const float* noise, const float* sigma, const float* cond,
+                  int loss_type, double* loss_out, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan && data && noise && sigma && cond && loss_out && grads && workspace && batch > 0, "bad argument");
+    CD_REQUIRE(loss_type >= CD_LOSS_L2 && loss_type <= CD_LOSS_HUBER, "loss_type must be one of CD_LOSS_L2 / L1 / MSE / HUBER");
+    check_ready(plan, true);
+    dgrad_images(plan);
+    plan->ws.reset((char*)workspace, workspace_bytes, false);
+    train_step_impl(plan, batch, data, noise, sigma, cond, loss_out, grads, (hipStream_t)stream, loss_type);
+  });
+}
+
+int cd_plan_vjp_workspace_bytes(CdPlan* plan, int batch, int with_param_grads, size_t* bytes) {
+  return guarded([&] {
+    CD_REQUIRE(plan && bytes && batch > 0, "bad argument");
+    CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the training step needs the Linear time/cond embeddings");
+    dgrad_images(plan);
+    plan->ws.reset(nullptr, 0, true);
+    denoise_vjp_impl(plan, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, with_param_grads != 0, nullptr);
+    *bytes = plan->ws.high() + 4096;
+  });
+}
+
+int cd_denoise_vjp(CdPlan* plan, int batch, const float* x, const float* sigma, const float* cond, const float* gy, float* dx,
+                   float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan && x && sigma && cond && gy && dx && workspace && batch > 0, "bad argument");
+    CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the training step needs the Linear time/cond embeddings");
+    check_ready(plan, true);
+    dgrad_images(plan);
+    plan->ws.reset((char*)workspace, workspace_bytes, false);
+    denoise_vjp_impl(plan, batch, x, sigma, cond, gy, dx, grads, grads != nullptr, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"
