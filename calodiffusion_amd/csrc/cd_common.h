@@ -8,6 +8,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+struct CdSamplerOp;  // include/calodiff.h
+
 namespace cd {
 
 // ---- error plumbing ---------------------------------------------------------------------------------
@@ -624,6 +626,29 @@ struct LayerMlpArgs {
   float* x0s;
 };
 void launch_layer_mlp(const LayerMlpArgs& a, hipStream_t s);
+
+// a sampler step program (CdSamplerOp lists, include/calodiff.h) on the layer MLP, the whole trajectory in one launch
+// (cd_layer_sampler_run); ops / op_begin / coefs are device arrays the host has validated
+struct LayerProgArgs {
+  const float* w[64];
+  int dim_in, hidden, cond_emb, cond_size, n_res, time_kind, objective, batch;
+  float sigma_data;
+  const float* start;        // (B, dim_in): buffer 0 = start * start_scale
+  float start_scale;
+  const float* cond;         // (B, cond_size)
+  int n_bufs, n_steps, n_ops, n_coef;
+  const ::CdSamplerOp* ops;  // n_ops entries
+  const int32_t* op_begin;   // n_steps + 1 entries, or null: every step runs ops[0, n_ops)
+  const float* coefs;        // (n_steps, n_coef)
+  const float* step_noise;   // (RANDN ops executed, B, dim_in), or null: the Philox stream
+  uint64_t seed, offset, stride;  // RANDN number k takes stream elements offset + k stride + b dim_in + i
+  float* out;                // (B, dim_in)
+  float* xs;                 // (n_steps, B, dim_in) or null
+  float* x0s;
+};
+constexpr int LAYER_PROG_MAX_BUFS = 10;
+// n_denoise: DENOISE ops the program executes (the profiler's algorithmic flops)
+void launch_layer_program(const LayerProgArgs& a, int64_t n_denoise, hipStream_t s);
 
 // training step of the layer-energy MLP (kernels_mlp_train.hip)
 struct LayerTapeLayout {

@@ -2,6 +2,7 @@
 // loss reduction and layout transposes.
 #include "cd_common.h"
 #include "gn_defer.h"
+#include "philox.h"
 
 #include <cmath>
 
@@ -394,25 +395,8 @@ void launch_scale_imm(const float* x, float* y, float scale, int64_t n, hipStrea
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller unit normals.  Element i of a stream is a pure function of (seed, offset + i):
-// counter = (offset+i)/4, lane = (offset+i)%4, so batch shards on different GPUs draw disjoint slices of one stream.
-// (The reference's torch.randn CPU stream (mt19937) cannot be reproduced on device; parity tests pass noise in.)
+// Unit normals of the device Philox stream (philox.h).
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 // dev (optional): {seed, base offset, stride} in device memory and the sampler's step counter -- the stream position then is
 // base + ((step - 1) * per_step + index) * stride, so that one captured step graph serves every step and every trajectory of a
 // stochastic sampler
@@ -425,19 +409,8 @@ __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int
   }
   const uint64_t first = offset >> 2, last = (offset + (uint64_t)n + 3) >> 2;  // counter range [first, last)
   for (uint64_t ctr = first + (uint64_t)blockIdx.x * 256 + threadIdx.x; ctr < last; ctr += (uint64_t)gridDim.x * 256) {
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     float z[4];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const float u1 = ((float)(c[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
-      const float u2 = ((float)(c[2 * p + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float rad = sqrtf(-2.f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      z[2 * p] = rad * cs;
-      z[2 * p + 1] = rad * sn;
-    }
+    philox_normals4(ctr, seed, z);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const uint64_t g = ctr * 4 + e;

@@ -3,6 +3,7 @@
 #include "plan_internal.h"
 
 #include <cstring>
+#include <vector>
 
 extern "C" {
 
@@ -94,6 +95,64 @@ int cd_layer_sample(const CdLayerMlpDesc* desc, const float* const* weights, int
     CD_REQUIRE(steps_dev && n_steps > 0, "bad argument");
     layer_mlp_call(desc, weights, n_weights, batch, 2, start, cond, nullptr, (const float*)steps_dev, n_steps, step_noise,
                    x_out, xs, x0s, stream);
+  });
+}
+
+int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* start,
+                         float start_scale, const float* cond, int n_bufs, int n_steps, const CdSamplerOp* ops_dev, int n_ops,
+                         const int32_t* op_begin_dev, const float* coefs_dev, int n_coef, const float* step_noise, uint64_t seed,
+                         uint64_t offset, uint64_t noise_stride, float* x_out, float* xs, float* x0s, void* stream) {
+  return guarded([&] {
+    const CdLayerMlpDesc* d = desc;
+    CD_REQUIRE(d && weights && start && cond && ops_dev && coefs_dev && x_out && batch > 0, "bad argument");
+    CD_REQUIRE(d->struct_size == sizeof(CdLayerMlpDesc), "CdLayerMlpDesc.struct_size does not match this library's calodiff.h");
+    CD_REQUIRE(d->n_res >= 0 && d->n_res <= 8 && n_weights == 2 * (8 + 3 * d->n_res),
+               "layer MLP: n_weights must be 2*(8 + 3*n_res) (time_mlp, cond_mlp, in_lay, blocks, out_lay)");
+    CD_REQUIRE(d->time_embed_kind >= 0 && d->time_embed_kind <= 2 && d->objective >= 0 && d->objective <= 2, "bad descriptor");
+    CD_REQUIRE(n_bufs >= 2 && n_bufs <= LAYER_PROG_MAX_BUFS && n_steps >= 1 && n_steps <= 1 << 20 && n_ops >= 1 && n_coef >= 1,
+               "bad program size (2..10 buffers)");
+    hipStream_t s = (hipStream_t)stream;
+    // validate the program before anything is enqueued: an index out of range would address outside the on-chip buffers
+    std::vector<CdSamplerOp> ops((size_t)n_ops);
+    std::vector<int32_t> begin(op_begin_dev ? (size_t)n_steps + 1 : 0);
+    CD_HIP(hipMemcpyAsync(ops.data(), ops_dev, sizeof(CdSamplerOp) * ops.size(), hipMemcpyDeviceToHost, s));
+    if (op_begin_dev) CD_HIP(hipMemcpyAsync(begin.data(), op_begin_dev, sizeof(int32_t) * begin.size(), hipMemcpyDeviceToHost, s));
+    CD_HIP(hipStreamSynchronize(s));
+    if (op_begin_dev) {
+      CD_REQUIRE(begin[0] == 0 && begin[n_steps] == n_ops, "op_begin must run from 0 to n_ops");
+      for (int i = 0; i < n_steps; ++i) CD_REQUIRE(begin[i] <= begin[i + 1], "op_begin must be non-decreasing");
+    }
+    int64_t n_denoise = 0;
+    for (int k = 0; k < n_ops; ++k) {
+      const CdSamplerOp& o = ops[k];
+      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_LINDIV, "sampler op: unknown kind");
+      const bool lin = o.kind == CD_SOP_LINCOMB || o.kind == CD_SOP_LINDIV;
+      const int ns = lin ? o.nsrc : (o.kind == CD_SOP_RANDN ? 0 : 1);
+      CD_REQUIRE(ns >= 0 && ns <= 6 && (!lin || ns >= 1), "sampler op: 1..6 sources");
+      for (int j = 0; j < ns; ++j) CD_REQUIRE(o.src[j] >= 0 && o.src[j] < n_bufs, "sampler op: source buffer out of range");
+      if (o.kind == CD_SOP_RECORD) CD_REQUIRE(o.dst == 0 || o.dst == 1, "record op: dst is 0 (xs) or 1 (x0s)");
+      else CD_REQUIRE(o.dst >= 0 && o.dst < n_bufs, "sampler op: destination buffer out of range");
+      if (lin) CD_REQUIRE(o.col >= 0 && o.col + ns + (o.kind == CD_SOP_LINDIV ? 1 : 0) <= n_coef, "lincomb op: coefficient columns out of range");
+      if (o.kind == CD_SOP_DENOISE) {
+        CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
+        CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
+        // DENOISE ops executed: once per step of a uniform program, once otherwise
+        n_denoise += op_begin_dev ? 1 : n_steps;
+      }
+    }
+    LayerProgArgs a{};
+    for (int i = 0; i < n_weights; ++i) {
+      CD_REQUIRE(weights[i], "null weight pointer");
+      a.w[i] = weights[i];
+    }
+    a.dim_in = d->dim_in; a.hidden = d->hidden; a.cond_emb = d->cond_emb; a.cond_size = d->cond_size; a.n_res = d->n_res;
+    a.time_kind = d->time_embed_kind; a.objective = d->objective; a.batch = batch; a.sigma_data = d->sigma_data;
+    a.start = start; a.start_scale = start_scale; a.cond = cond;
+    a.n_bufs = n_bufs; a.n_steps = n_steps; a.n_ops = n_ops; a.n_coef = n_coef;
+    a.ops = ops_dev; a.op_begin = op_begin_dev; a.coefs = coefs_dev; a.step_noise = step_noise;
+    a.seed = seed; a.offset = offset; a.stride = noise_stride ? noise_stride : (uint64_t)batch * (uint64_t)d->dim_in;
+    a.out = x_out; a.xs = xs; a.x0s = x0s;
+    launch_layer_program(a, n_denoise, s);
   });
 }
 

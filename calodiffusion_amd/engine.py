@@ -91,6 +91,8 @@ _SIGNATURES = {
     "cd_layer_forward": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "cd_layer_denoise": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "cd_layer_sample": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "cd_layer_sampler_run": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, _P, C.c_int,
+                                       _P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
     "cd_layer_train_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_layer_train_step": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_layer_train_step_loss": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t,
@@ -552,7 +554,8 @@ class UnetEngine:
 
 
 class LayerMlpEngine:
-    """The layer-energy MLP of LayerDiffusion on the HIP library (cd_layer_forward / cd_layer_denoise / cd_layer_sample).
+    """The layer-energy MLP of LayerDiffusion on the HIP library (cd_layer_forward / cd_layer_denoise / cd_layer_sample /
+    cd_layer_sampler_run).
     Stateless on the library side: the parameters are read in place from the torch storage."""
 
     def __init__(self, resnet, time_kind="raw", objective="hybrid", sigma_data=1.0):
@@ -649,6 +652,43 @@ class LayerMlpEngine:
 
     def loss_hybrid_l2(self, data, noise, sigma, cond):
         return self.loss_hybrid(data, noise, sigma, cond, "l2")
+
+    def sampler_run(self, start, cond, program, step_noise=None, seed=0, offset=0, noise_stride=0, debug=False, use_graph=True):
+        """Same contract as UnetEngine.sampler_run on (B, dim) vectors (cd_layer_sampler_run): the whole program is one launch
+        (use_graph is irrelevant).  The k-th RANDN op executed takes the Philox stream elements offset + k * stride + row * dim
+        + i, stride = noise_stride or B * dim, so batch shards are slices of one global stream; step_noise: one (B, dim) tensor
+        per RANDN op executed instead.  Returns (x, xs, x0s); the trajectories (n_steps, B, dim) only when ``debug`` and the
+        program records them."""
+        start, cond, B = self._io(start, cond)
+        coefs = np.ascontiguousarray(program.coefs, dtype=np.float32)
+        n_steps, n_coef = coefs.shape
+        ops = np.zeros((len(program.ops), C.sizeof(CdSamplerOp) // 4), dtype=np.int32)  # rows in CdSamplerOp's field order
+        for row, (kind, dst, src, col) in zip(ops, program.ops):
+            row[0], row[1], row[2], row[9] = kind, dst, len(src), col
+            row[3:3 + len(src)] = src
+        ops_dev = torch.from_numpy(ops).to(start.device)
+        coefs_dev = torch.from_numpy(coefs).to(start.device)
+        op_begin = None
+        if program.op_begin is not None:
+            assert len(program.op_begin) == n_steps + 1
+            op_begin = torch.tensor(program.op_begin, dtype=torch.int32, device=start.device)
+        x_out = torch.empty_like(start)
+        xs = x0s = None
+        if debug:
+            kinds = [(k, d) for k, d, _, _ in program.ops if k == SOP_RECORD]
+            if (SOP_RECORD, 0) in kinds:
+                xs = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
+            if (SOP_RECORD, 1) in kinds:
+                x0s = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
+        if step_noise is not None:
+            step_noise = _dev32(step_noise, "step_noise")
+            assert step_noise.numel() == program.n_randn * start.numel(), "step_noise: one (B, dim) tensor per RANDN op executed"
+        w, n = self._weights()
+        _check(self.lib.cd_layer_sampler_run(C.byref(self.desc), w, n, B, start.data_ptr(), float(program.start_scale),
+                                             cond.data_ptr(), program.n_bufs, n_steps, ops_dev.data_ptr(), len(program.ops),
+                                             _ptr(op_begin), coefs_dev.data_ptr(), n_coef, _ptr(step_noise), int(seed), int(offset),
+                                             int(noise_stride), x_out.data_ptr(), _ptr(xs), _ptr(x0s), _stream()))
+        return x_out, xs, x0s
 
     def ddim_sample(self, start, cond, steps: np.ndarray, step_noise=None, seed=0, offset=0, debug=False, use_graph=True,
                     out=None, noise_stride=0):

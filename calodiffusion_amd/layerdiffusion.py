@@ -1,8 +1,9 @@
 """LayerDiffusion: two-stage generation -- a small MLP diffusion model draws the (B, D+1) {total, per-layer} energies, the
 U-Net then generates the shower conditioned on them (mirror of reference calodiffusion/models/layerdiffusion.py:12-235).
 
-Both stages run on the HIP library: the layer stage is ONE launch for the whole trajectory (``cd_layer_sample``), the shower
-stage is the U-Net sampler loop of ``CaloDiffusion``.
+Both stages run on the HIP library: the layer stage is ONE launch for the whole trajectory (``cd_layer_sample`` for DDim / DDPM /
+Euler without churn, ``cd_layer_sampler_run`` for every other LAYER_SAMPLER with a step program), the shower stage is the
+U-Net sampler loop of ``CaloDiffusion``.
 """
 from __future__ import annotations
 
@@ -122,13 +123,18 @@ class LayerDiffusion(CaloDiffusion):
         return super().denoise(x, E=E, sigma=sigma, layers=layers, controls=controls)
 
     def sample_layers(self, energy, layers=None, debug=False, sample_offset=None, start: Optional[torch.Tensor] = None):
-        """layerdiffusion.py:114-132: the (B, D+1) layer energies, one launch for the whole trajectory."""
+        """layerdiffusion.py:114-132: the (B, D+1) layer energies, one launch for the whole trajectory: DDim / DDPM / Euler
+        without churn on cd_layer_sample, every step-program sampler of sample.py on cd_layer_sampler_run."""
         self.set_layer_state(is_layer=True)
         try:
             if start is None:
                 start = self.noise_generation((energy.shape[0], self.shape_pad[2] + 1)).to(torch.float32)
             x, _, _ = self.layer_sampler(self, start, energy, layers, self.layer_steps, sample_offset, debug)
-            self.noise_offset += start.numel() * self.layer_steps
+            if getattr(self.layer_sampler, "ran_program", False):
+                # a step program (cd_layer_sampler_run) drew its noise tensors one global (B, dim) tensor apart behind the start
+                self.noise_offset += self._shard_geometry(start.shape)[2] * self.layer_sampler.noise_tensors_drawn
+            else:
+                self.noise_offset += start.numel() * self.layer_steps
         finally:
             self.set_layer_state(is_layer=False)
         return x

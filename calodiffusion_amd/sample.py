@@ -10,7 +10,8 @@ host<->device ``extract`` round trips) in between.  Here every sampler is ONE C-
   linear combinations of a few (B,1,D,H,W) buffers, denoise calls, noise draws, trajectory records -- whose scalars are the
   columns of that step's row of a host table.  All of these samplers are exactly that: their updates are linear in
   {x, denoised, noise, history} with coefficients that depend on the step only.  Uniform programs replay one captured step
-  graph; the others (Restart's nested loops, DPM-Solver-fast's changing orders) run their steps eagerly.
+  graph; the others (Restart's nested loops, DPM-Solver-fast's changing orders) run their steps eagerly.  On LayerDiffusion's
+  layer model the same programs run through ``cd_layer_sampler_run``: one launch interprets the whole program.
 
 ``DPMAdaptive`` decides every step on the host from a norm of the state: it is a host loop around ``denoise`` (one
 ``cd_denoise_safe`` call per model evaluation), not a step program.  ``DPMPPSDE`` / ``DPMPP2MSDE`` / ``DPMPP3MSDE`` are step
@@ -37,6 +38,7 @@ class Sample:
         self.seed = int(self.sample_config.get("SEED", 0))
         self.step_noise = None  # parity hook: the noise tensors to use, in draw order, instead of the device Philox stream
         self.noise_tensors_drawn = 0  # (B,1,D,H,W) tensors the last call took from the stream (Diffusion.sample advances by it)
+        self.ran_program = False  # the last call ran a step program (engine.sampler_run), not the DDIM-table loop
 
     def __call__(self, model, start, energy, layers, num_steps, sample_offset, debug) -> Any:
         raise NotImplementedError
@@ -67,6 +69,7 @@ class DDim(Sample):
             start, model.cond_tensor(energy, layers), table, step_noise=self.step_noise, seed=getattr(model, "noise_seed", self.seed),
             offset=offset, debug=debug, use_graph=self.use_graph, noise_stride=stride)
         self.noise_tensors_drawn = table.shape[0] if self.ddim_eta else 0
+        self.ran_program = False
         if debug:
             return x, list(xs.unbind(0)), list(x0s.unbind(0))
         return x, [], []
@@ -155,16 +158,14 @@ class _ProgramSampler(Sample):
 
     @torch.no_grad()
     def __call__(self, model, start, energy, layers, num_steps, sample_offset=0, debug=False) -> Any:
-        eng = model.engine()
-        if not hasattr(eng, "sampler_run"):
-            raise NotImplementedError(f"{type(self).__name__} runs on the U-Net engine; the layer model's one-launch sampler "
-                                      "offers DDim / DDPM / Euler")
+        eng = model.engine()  # UnetEngine (cd_sampler_run) or, in LayerDiffusion's layer state, LayerMlpEngine (cd_layer_sampler_run)
         prog = self.build(model, num_steps, sample_offset or 0).finalize()
         offset, stride = self._stream(model, start)
         x, xs, x0s = eng.sampler_run(start, model.cond_tensor(energy, layers), prog, step_noise=self.step_noise,
                                      seed=getattr(model, "noise_seed", self.seed), offset=offset, noise_stride=stride,
                                      debug=debug and self.returns_trajectories, use_graph=self.use_graph)
         self.noise_tensors_drawn = prog.n_randn
+        self.ran_program = True
         return self.finish(x, xs, x0s, debug)
 
     def finish(self, x, xs, x0s, debug):
@@ -258,6 +259,7 @@ class Euler(EDMAbstract):
         x, xs, x0s = model.engine().ddim_sample(start, model.cond_tensor(energy, layers), table, debug=debug,
                                                 use_graph=self.use_graph)
         self.noise_tensors_drawn = 0
+        self.ran_program = False
         if debug:
             return x, list(xs.unbind(0)), list(x0s.unbind(0))
         return x, [], []

@@ -174,7 +174,8 @@ typedef struct CdSamplerOp {
 int cd_plan_sampler_workspace_bytes(CdPlan* plan, int batch, int n_bufs, int n_steps, int n_coef, size_t* bytes);
 /* start: (B,1,D,H,W) unit normal, x = start * start_scale first.  coefs: HOST (n_steps, n_coef) fp32.  ops: n_ops entries
  * (op_begin == NULL: the one list of every step; else op_begin has n_steps + 1 entries).  step_noise: NULL or DEVICE
- * (number of RANDN ops executed, B,1,D,H,W), consumed in execution order.  xs / x0s: NULL or (n_steps, B,1,D,H,W). */
+ * (number of RANDN ops executed, B,1,D,H,W), consumed in execution order.  xs / x0s: NULL or (n_steps, B,1,D,H,W).
+ * The same programs run on LayerDiffusion's layer model through cd_layer_sampler_run (below, after CdLayerMlpDesc). */
 int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scale, const float* cond, int n_bufs, int n_steps,
                    const CdSamplerOp* ops, int n_ops, const int32_t* op_begin, const float* coefs, int n_coef,
                    const float* step_noise, uint64_t seed, uint64_t offset, uint64_t noise_stride, float* x_out, float* xs,
@@ -300,6 +301,23 @@ int cd_layer_denoise(const CdLayerMlpDesc* desc, const float* const* weights, in
 int cd_layer_sample(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* start,
                     const float* cond, const CdStep* steps_dev, int n_steps, const float* step_noise, float* x_out, float* xs,
                     float* x0s, void* stream);
+/* A sampler step program (CdSamplerOp, as cd_sampler_run) on the layer model: the whole trajectory in ONE launch, one workgroup
+ * per sample with the n_bufs (2..10) state vectors on chip.  Every sampler class of calodiffusion_amd/sample.py that builds a
+ * program runs on the layer stage through it.
+ * start (B, dim_in): buffer 0 = start * start_scale, the others start at zero.  DENOISE is cd_layer_denoise at
+ * sigma = coefs[step][col]; LINCOMB / LINDIV round as cd_sampler_run's.  ops (n_ops), op_begin (NULL, or n_steps + 1 entries)
+ * and coefs (n_steps, n_coef) are DEVICE arrays.  The k-th RANDN op executed takes the Philox stream elements
+ * offset + k * stride + b * dim_in + i, stride = noise_stride ? noise_stride : B * dim_in (cd_sampler_run's convention, so batch
+ * shards are slices of one global stream); step_noise, when given: DEVICE (RANDN ops executed, B, dim_in), tensor k instead.
+ * x_out (B, dim_in); xs / x0s: NULL or (n_steps, B, dim_in), written by RECORD.
+ * The op list and op_begin are checked on the host before anything is launched (kinds, 1..6 sources, buffer indices below
+ * n_bufs, coefficient columns below n_coef, op_begin from 0 to n_ops and non-decreasing): a bad program is an error return.
+ * That check reads them back (a few hundred bytes), so the call synchronises with `stream` once and cannot be captured into a
+ * graph; it allocates nothing. */
+int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* start,
+                         float start_scale, const float* cond, int n_bufs, int n_steps, const CdSamplerOp* ops_dev, int n_ops,
+                         const int32_t* op_begin_dev, const float* coefs_dev, int n_coef, const float* step_noise, uint64_t seed,
+                         uint64_t offset, uint64_t noise_stride, float* x_out, float* xs, float* x0s, void* stream);
 
 /* Training step of the layer model (LayerDiffusion.compute_loss in the layer state, models/layerdiffusion.py:52-57, with
  * the hybrid_weight / l2 loss of models/loss.py:103-104,118-142,163-179): data = layer energies (B, dim_in), noise (B, dim_in),
