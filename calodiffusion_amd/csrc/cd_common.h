@@ -558,6 +558,9 @@ void launch_randn_step(float* out, int64_t n, const uint64_t* seed_offset_stride
 void launch_step_advance(int* counter, hipStream_t s);  // (*counter)++
 void launch_or_word(int* word, int bits, hipStream_t s);  // *word |= bits
 void launch_fill_from_table(float* dst, int count, const float* table, int ncol, int col, const int* step_counter, hipStream_t s);
+// dst[b] = table[row][col + b], b < count (CD_SOP_DENOISE_PS: a sigma per sample)
+void launch_fill_row_from_table(float* dst, int count, const float* table, int ncol, int col, const int* step_counter,
+                                hipStream_t s);
 // out[i] = sum_k table[row][col + k] * src[k][i]   (nsrc <= 6; out may alias a source)
 void launch_lincomb(float* out, const float* const* src, int nsrc, const float* table, int ncol, int col, const int* step_counter,
                     int64_t n, hipStream_t s);
@@ -565,6 +568,20 @@ void launch_lincomb_div(float* out, const float* const* src, int nsrc, const flo
                     int64_t n, hipStream_t s);
 // traj[(*step_counter - 1) * n + i] = src[i]
 void launch_record_step(float* traj, const float* src, const int* step_counter, int64_t n, hipStream_t s);
+// BespokeNonStationary theta gradient (cd_bns_theta_grad).  theta (2, n_steps) device; partial: 2 * kBnsMaxBlocks doubles.
+constexpr int kBnsMaxBlocks = 1024;
+// x_next = x * a_i + u * b_i (products and sum rounded on their own, as the reference's torch ops)
+void launch_bns_step(float* x_next, const float* x, const float* u, const float* theta, int n_steps, int i, int64_t n,
+                     hipStream_t s);
+// rowmax (n / w floats) = maxima of data over its last axis (width w); *loss_out = the reference's PSNR loss; scal[0] = the seed
+// coefficient of g_N = scal[0] * (x_N - data)
+void launch_bns_loss(const float* data, const float* x_n, int64_t n, int w, float* rowmax, double* partial, double* loss_out,
+                     float* scal, hipStream_t s);
+void launch_bns_seed(float* g, const float* x_n, const float* data, const float* scal, int64_t n, hipStream_t s);
+// dtheta[0][i] = <g, x>, dtheta[1][i] = <g, u>; with chain, gy = b_i g and g = a_i g
+void launch_bns_dtheta(float* g, const float* x, const float* u, const float* theta, int n_steps, int i, float* gy, bool chain,
+                       int64_t n, double* partial, float* dtheta, hipStream_t s);
+void launch_bns_accum(float* g, const float* dx, int64_t n, hipStream_t s);  // g += dx
 void launch_axpy_sigma(const float* data, const float* noise, const float* sigma_b, float* out, int batch, int64_t per,
                        hipStream_t s);
 // The training objectives of models/loss.py on top of the denoiser's output `out` (calodiffusion.py:161-169), objective =

@@ -258,8 +258,9 @@ __global__ void __launch_bounds__(512) layer_program_kernel(LayerProgArgs a) {
           }
           break;
         }
-        case CD_SOP_DENOISE: {
-          const float sigma = row[o.col];
+        case CD_SOP_DENOISE:
+        case CD_SOP_DENOISE_PS: {  // (DENOISE_PS: this workgroup's shower at its own column)
+          const float sigma = row[o.col + (o.kind == CD_SOP_DENOISE_PS ? b : 0)];
           const EdmScal e = edm_scalings(sigma, a.sigma_data, a.time_kind);
           if (tid == 0) tb0[0] = e.t_in;
           if (mine) xin[tid] = s0[tid] * e.c_in;

@@ -125,7 +125,7 @@ int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights
     int64_t n_denoise = 0;
     for (int k = 0; k < n_ops; ++k) {
       const CdSamplerOp& o = ops[k];
-      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_LINDIV, "sampler op: unknown kind");
+      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_DENOISE_PS, "sampler op: unknown kind");
       const bool lin = o.kind == CD_SOP_LINCOMB || o.kind == CD_SOP_LINDIV;
       const int ns = lin ? o.nsrc : (o.kind == CD_SOP_RANDN ? 0 : 1);
       CD_REQUIRE(ns >= 0 && ns <= 6 && (!lin || ns >= 1), "sampler op: 1..6 sources");
@@ -133,8 +133,9 @@ int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights
       if (o.kind == CD_SOP_RECORD) CD_REQUIRE(o.dst == 0 || o.dst == 1, "record op: dst is 0 (xs) or 1 (x0s)");
       else CD_REQUIRE(o.dst >= 0 && o.dst < n_bufs, "sampler op: destination buffer out of range");
       if (lin) CD_REQUIRE(o.col >= 0 && o.col + ns + (o.kind == CD_SOP_LINDIV ? 1 : 0) <= n_coef, "lincomb op: coefficient columns out of range");
-      if (o.kind == CD_SOP_DENOISE) {
-        CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
+      if (o.kind == CD_SOP_DENOISE || o.kind == CD_SOP_DENOISE_PS) {
+        if (o.kind == CD_SOP_DENOISE) CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
+        else CD_REQUIRE(o.col >= 0 && o.col + batch <= n_coef, "per-sample denoise op: sigma columns out of range (col + batch > n_coef)");
         CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
         // DENOISE ops executed: once per step of a uniform program, once otherwise
         n_denoise += op_begin_dev ? 1 : n_steps;

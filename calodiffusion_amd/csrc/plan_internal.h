@@ -308,6 +308,10 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
                   const FwdOpts* opt = nullptr);
 // plan.hip
 void check_ready(CdPlan* p, bool need_coords);
+// train.hip
+void dgrad_images(CdPlan* p);  // lays out the input-gradient weight images once per plan (before any backward pass)
+void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,
+                      bool param_grads, hipStream_t s);
 
 // Every C-ABI entry point runs inside guarded().  The launchers check `hipGetLastError()` after each launch, and that call
 // reports the thread's LAST error whoever set it -- a HIP call that failed earlier in the process (another library's, the

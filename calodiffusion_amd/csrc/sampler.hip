@@ -226,7 +226,7 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
     int randn_per_step = 0;
     for (int k = 0; k < n_ops; ++k) {
       const CdSamplerOp& o = ops[k];
-      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_LINDIV, "sampler op: unknown kind");
+      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_DENOISE_PS, "sampler op: unknown kind");
       const bool lin = o.kind == CD_SOP_LINCOMB || o.kind == CD_SOP_LINDIV;
       const int ns = lin ? o.nsrc : (o.kind == CD_SOP_RANDN ? 0 : 1);
       CD_REQUIRE(ns >= 0 && ns <= 6 && (!lin || ns >= 1), "sampler op: 1..6 sources");
@@ -236,6 +236,10 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
       if (lin) CD_REQUIRE(o.col >= 0 && o.col + ns + (o.kind == CD_SOP_LINDIV ? 1 : 0) <= n_coef, "lincomb op: coefficient columns out of range");
       if (o.kind == CD_SOP_DENOISE) {
         CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
+        CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
+      }
+      if (o.kind == CD_SOP_DENOISE_PS) {
+        CD_REQUIRE(o.col >= 0 && o.col + batch <= n_coef, "per-sample denoise op: sigma columns out of range (col + batch > n_coef)");
         CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
       }
       if (o.kind == CD_SOP_RANDN) ++randn_per_step;
@@ -273,6 +277,11 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
         }
         case CD_SOP_DENOISE:
           launch_fill_from_table(sigma_b, batch, table, n_coef, o.col, counter, st);
+          plan->ws.reset(sub, sub_bytes, false);
+          forward_impl(plan, batch, bufs[o.src[0]], cond, sigma_b, bufs[o.dst], false, st);
+          break;
+        case CD_SOP_DENOISE_PS:  // the step's `batch` sigma columns, read through the device counter (eager and captured alike)
+          launch_fill_row_from_table(sigma_b, batch, table, n_coef, o.col, counter, st);
           plan->ws.reset(sub, sub_bytes, false);
           forward_impl(plan, batch, bufs[o.src[0]], cond, sigma_b, bufs[o.dst], false, st);
           break;
@@ -317,9 +326,10 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
           graph.destroy();
           // one eager denoise first (kernel tuning / lazy function attributes cannot happen during capture): x -> buffer 1
           for (int k = 0; k < n_ops; ++k)
-            if (ops[k].kind == CD_SOP_DENOISE) {
+            if (ops[k].kind == CD_SOP_DENOISE || ops[k].kind == CD_SOP_DENOISE_PS) {
               launch_step_advance(counter, s);
-              launch_fill_from_table(sigma_b, batch, table, n_coef, ops[k].col, counter, s);
+              if (ops[k].kind == CD_SOP_DENOISE) launch_fill_from_table(sigma_b, batch, table, n_coef, ops[k].col, counter, s);
+              else launch_fill_row_from_table(sigma_b, batch, table, n_coef, ops[k].col, counter, s);
               plan->ws.reset(sub, sub_bytes, false);
               forward_impl(plan, batch, x_out, cond, sigma_b, bufs[1], false, s);
               CD_HIP(hipMemsetAsync(counter, 0, sizeof(int), s));

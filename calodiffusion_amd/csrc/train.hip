@@ -707,7 +707,7 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
 // transposed), 2 = 3x3x3 stride 1 (f32 + split16 images, transposed + flipped), 3 = strided down conv (f32 + f16x2 images,
 // transposed: its adjoint is the up-conv gather kernel), 4 = up conv (f32 + split16 images of the tensor read as a plain conv:
 // its adjoint is the strided conv).
-static void dgrad_images(CdPlan* p) {
+void dgrad_images(CdPlan* p) {
   if (p->d_dg_jobs) return;
   size_t off = 0;
   auto bump = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };

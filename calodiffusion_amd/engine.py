@@ -45,7 +45,7 @@ class CdUnetDesc(C.Structure):
     ]
 
 
-SOP_LINCOMB, SOP_DENOISE, SOP_RANDN, SOP_RECORD, SOP_LINDIV = 0, 1, 2, 3, 4
+SOP_LINCOMB, SOP_DENOISE, SOP_RANDN, SOP_RECORD, SOP_LINDIV, SOP_DENOISE_PS = 0, 1, 2, 3, 4, 5
 
 
 class CdSamplerOp(C.Structure):
@@ -105,6 +105,8 @@ _SIGNATURES = {
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "cd_plan_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_denoise_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cd_plan_bns_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cd_bns_theta_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),
@@ -528,6 +530,38 @@ class UnetEngine:
         _check(self.lib.cd_denoise_vjp(self.plan, B, x.data_ptr(), sigma.data_ptr(), cond.data_ptr(), gy.data_ptr(), dx.data_ptr(),
                                        _ptr(flat), ws.data_ptr(), ws.numel(), _stream()))
         return dx, flat
+
+    def bns_workspace(self, batch: int, n_steps: int) -> torch.Tensor:
+        """Workspace of cd_bns_theta_grad (one kept: the last shape asked for)."""
+        key = (int(batch), int(n_steps))
+        ws = getattr(self, "_bws", {}).get(key)
+        if ws is None:
+            nbytes = C.c_size_t()
+            _check(self.lib.cd_plan_bns_workspace_bytes(self.plan, batch, n_steps, C.byref(nbytes)))
+            self._bws = {}  # (release the previous one before allocating the next)
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            self._bws = {key: ws}
+        return ws
+
+    def bns_theta_grad(self, data, cond, theta, sigma):
+        """BespokeNonStationary training loss and its gradient with respect to theta (cd_bns_theta_grad): the chain
+        x_0 = data, x_{i+1} = x_i a_i + denoise(x_i, sigma_i) b_i, loss = mean(20 log10(max(data, -1) / sqrt(mse(data, x_N)))).
+        theta (2, N); sigma (N, B).  Returns (loss: 0-d fp64 tensor, dtheta: (2, N) fp32), both on the device."""
+        data, cond = _dev32(data, "data"), _dev32(cond, "cond")
+        theta, sigma = _dev32(theta.detach(), "theta"), _dev32(sigma, "sigma")
+        B = data.shape[0]
+        N = theta.shape[1] if theta.dim() == 2 else -1
+        if (tuple(data.shape[1:]) != (1,) + self.grid or theta.shape != (2, N) or tuple(sigma.shape) != (N, B)
+                or cond.shape != (B, self.unet.cond_size)):
+            raise ValueError(f"bns_theta_grad shapes: data {tuple(data.shape)}, theta {tuple(theta.shape)}, sigma {tuple(sigma.shape)}, "
+                             f"cond {tuple(cond.shape)}")
+        self.sync_weights()
+        ws = self.bns_workspace(B, N)
+        loss = torch.empty((), dtype=torch.float64, device=data.device)
+        dtheta = torch.empty((2, N), dtype=torch.float32, device=data.device)
+        _check(self.lib.cd_bns_theta_grad(self.plan, B, N, data.data_ptr(), cond.data_ptr(), theta.data_ptr(), sigma.data_ptr(),
+                                          loss.data_ptr(), dtheta.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return loss, dtheta
 
     def param_grads(self, flat):
         """Views of the flat gradient buffer, one per parameter of the bound CondUnet, in .parameters() order."""

@@ -16,18 +16,20 @@ host<->device ``extract`` round trips) in between.  Here every sampler is ONE C-
 ``DPMAdaptive`` decides every step on the host from a norm of the state: it is a host loop around ``denoise`` (one
 ``cd_denoise_safe`` call per model evaluation), not a step program.  ``DPMPPSDE`` / ``DPMPP2MSDE`` / ``DPMPP3MSDE`` are step
 programs whose Brownian-tree noise (``torchsde`` in the reference) is drawn with the same law from the device Philox stream
-(``_BrownianSDE``).  Not provided: ``BespokeNonStationary`` (needs a trained theta file); asking for it raises.
+(``_BrownianSDE``).  ``BespokeNonStationary`` is a uniform step program whose denoiser runs every sample at its own sigma
+(``DENOISE_PS``); its theta is trained by ``optimize_sampler``, one ``cd_bns_theta_grad`` call per batch.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import schedule
-from .engine import SOP_DENOISE, SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD
+from .engine import SOP_DENOISE, SOP_DENOISE_PS, SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD
 
 
 class Sample:
@@ -583,14 +585,6 @@ class Consistency(_ProgramSampler):
         return x, [], None
 
 
-def _unavailable(name, why):
-    class _Missing(Sample):
-        def __init__(self, config):
-            raise NotImplementedError(f"sampler {name!r} is not provided on the HIP path: {why}")
-    _Missing.__name__ = name
-    return _Missing
-
-
 class DPMAdaptive(DPM):
     """DPM-Solver-12 / -23 with an error test per step (models/sample.py:188-309) as a host loop around the denoiser: every step
     the host compares the lower- and the higher-order estimate and decides, so it cannot be a device step program.
@@ -834,4 +828,176 @@ class DPMPP3MSDE(_BrownianSDE):
         return prog
 
 
-BespokeNonStationary = _unavailable("BespokeNonStationary", "needs a trained theta file (SAMPLER_PATH)")
+_BNS_LOG_EMBED = ("BespokeNonStationary draws sigma ~ N(0, 1) per sample and step (models/sample.py:1107-1109); with TIME_EMBED "
+                  "'log' the time input 0.5 log(sigma) is NaN for every sigma <= 0, so the reference returns NaN for about half "
+                  "the showers (and a NaN theta gradient).  Not provided: use a model with TIME_EMBED 'sigma'")
+
+
+class BespokeNonStationary(Sample):
+    """Bespoke non-stationary solver (models/sample.py:1013-1122, arXiv:2403.01329): per step i, with theta = (a; b) of shape
+    (2, N) read from SAMPLER_PATH, ``U_i = denoise(x_i, sigma_i)`` and ``x_{i+1} = x_i a_i + U_i b_i`` from ``x_0 = start``
+    (unit normal, not scaled).  sigma_i is a fresh standard normal draw per sample and step, as the reference's ``model_fn``
+    draws it.
+
+    On the device this is a uniform step program -- DENOISE_PS (a sigma per sample), LINCOMB, RECORD -- so the trajectory replays
+    one captured step graph (cd_sampler_run; on LayerDiffusion's layer stage cd_layer_sampler_run).  The sigma of step k and
+    global row r is element ``offset + k * B_global + r`` of the device Philox stream (offset: right behind the start tensor),
+    so batch shards (``set_noise_shard``) draw slices of one stream; ``noise_tensors_drawn`` counts the N * B_global draws
+    rounded up to whole (B_global, ...) tensors.  ``step_sigma`` (parity hook): an (N - sample_offset, B) tensor instead.
+
+    Where the reference's code fails, this class says so instead:
+      * TIME_EMBED 'log': ValueError (the reference's showers are NaN for sigma <= 0); any embedding other than 'sigma' / 'log'
+        (the default 'sin', whose reference denoise raises KeyError): NotImplementedError at construction, like ORG_SCHEDULE;
+      * ``debug``: returns (x, xs, x0s) -- the states after every step and the denoiser outputs U_i -- as the other samplers do
+        (the reference returns a 4-tuple that Diffusion.sample cannot unpack);
+      * TRAIN_SAMPLER: the reference trains on ``load_data(flags)`` inside the call; dataset IO is not part of this package, so
+        the call raises until ``optimize_sampler(model, loader, num_steps)`` has trained theta on a loader of its caller's.
+
+    ``optimize_sampler`` is the reference's training loop (theta = ones, Adam(LR), MAX_ITER epochs, the chain started from the
+    data batch, the PSNR loss of its ``loss_function``), each batch one cd_bns_theta_grad call.  It forms the gradient of theta
+    only: the reference's ``loss.backward()`` also accumulates ``.grad`` of every model parameter, which nothing reads; here
+    the model's ``.grad`` are left untouched.  When mse == 0 the reference's loss is the int 100, on which its ``torch.mean``
+    raises: here the loss is 100 and the gradient zero."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        embed = self.config.get("TIME_EMBED", "sin")
+        if embed not in ("sigma", "log"):  # ('log' is refused when sampling or training: _BNS_LOG_EMBED)
+            raise NotImplementedError(f"BespokeNonStationary needs a model with TIME_EMBED 'sigma', not {embed!r}: the reference's "
+                                      "denoise raises KeyError for the sinusoidal embedding (calodiffusion.py:148-152), so no "
+                                      "BNS trajectory exists to reproduce")
+        self.theta: Optional[torch.Tensor] = None
+        self.trained = False  # theta comes from optimize_sampler in this process
+        self.step_sigma = None  # parity hook: (N - sample_offset, B) sigmas; optimize_sampler: one (N, B) tensor, or a list per batch
+        self.losses: List[float] = []  # optimize_sampler: the loss of every batch
+        self.last_sigma: Optional[torch.Tensor] = None  # the (N - sample_offset, B) sigmas of the last call
+
+    def _data_folder_path(self, name: str) -> Optional[str]:
+        flags = self.config.get("flags")
+        folder = getattr(flags, "data_folder", None)
+        return None if folder is None else folder.rstrip("/") + "/" + name
+
+    def sampler_path(self) -> Optional[str]:
+        """Where theta is loaded from: SAMPLER_PATH, else flags.data_folder + '/bns_sampler.pth' (models/sample.py:1043)."""
+        return self.sample_config.get("SAMPLER_PATH", self._data_folder_path("bns_sampler.pth"))
+
+    def save_path(self) -> Optional[str]:
+        """Where optimize_sampler saves theta: SAMPLER_PATH, else flags.data_folder + '/bns_sampler.pt' (:1087-1089; note .pt
+        against the .pth it loads by default)."""
+        path = self.sample_config.get("SAMPLER_PATH")
+        return path if path is not None else self._data_folder_path("bns_sampler.pt")
+
+    def load_sampler(self, num_steps: int) -> torch.Tensor:
+        path = self.sampler_path()
+        if path is None or not os.path.exists(path):
+            raise ValueError("No sampler path provided, set it with 'SAMPLER_PATH' in the config")
+        theta = torch.load(path, map_location="cpu")
+        self.theta = theta.detach().to(torch.float32)
+        return self.theta
+
+    @staticmethod
+    def check_embedding(model, config):
+        if getattr(model, "time_embed", config.get("TIME_EMBED", "sin")) == "log":
+            raise ValueError(_BNS_LOG_EMBED)
+
+    def _draw_sigma(self, model, start, n_run: int) -> torch.Tensor:
+        """(n_run, B) unit normals: element (k, b) at offset + k * B_global + lo + b of the stream behind the start tensor."""
+        from .engine import randn
+        B, per = start.shape[0], start[0].numel()
+        lo, gb = getattr(model, "noise_shard", None) or (0, B)
+        off, _ = self._stream(model, start)  # offset + lo * per (Diffusion.step_noise_stream)
+        base = off - lo * per
+        full = randn((n_run, gb), start.device, getattr(model, "noise_seed", self.seed), base)
+        return full[:, lo:lo + B].contiguous()
+
+    @staticmethod
+    def build_program(theta_run: torch.Tensor, sigma: torch.Tensor) -> Program:
+        """The step program: per step DENOISE_PS(U <- x) at the columns 2 .. 2 + B - 1 (sigma of every sample), RECORD(x0s <- U),
+        LINCOMB(x <- a x + b U) at columns 0, 1, RECORD(xs <- x)."""
+        th = theta_run.detach().to(torch.float32).cpu()
+        sg = sigma.detach().to(torch.float32).cpu()
+        assert sg.shape[0] == th.shape[1], "one sigma row per step"
+        U = 1
+        prog = Program(2, 1.0)
+        for i in range(th.shape[1]):
+            st = prog.step()
+            st.coefs = [float(th[0, i]), float(th[1, i])] + [float(v) for v in sg[i]]
+            st.ops = [(SOP_DENOISE_PS, U, (X,), 2), (SOP_RECORD, 1, (U,), 0), (SOP_LINCOMB, X, (X, U), 0), (SOP_RECORD, 0, (X,), 0)]
+        return prog
+
+    @torch.no_grad()
+    def __call__(self, model, start, energy, layers, num_steps, sample_offset=0, debug=False) -> Any:
+        self.check_embedding(model, self.config)
+        if self.sample_config.get("TRAIN_SAMPLER", False):
+            if not self.trained:
+                raise RuntimeError("BespokeNonStationary: TRAIN_SAMPLER trains theta on load_data(flags) in the reference, and "
+                                   "dataset loading is not part of this package: call optimize_sampler(model, loader, num_steps) "
+                                   "with a loader of (E, layers, data) batches first")
+        else:
+            self.load_sampler(num_steps)
+        if num_steps != self.theta.shape[1]:
+            raise ValueError("Number of steps must match the number of steps in the theta parameterization")
+        theta_run = self.theta[:, (sample_offset or 0):]
+        n_run = theta_run.shape[1]
+        B = start.shape[0]
+        self.ran_program = True
+        self.noise_tensors_drawn = -(-n_run // start[0].numel()) if n_run else 0
+        if n_run == 0:
+            return start.clone(), [], []
+        if self.step_sigma is not None:
+            sigma = torch.as_tensor(self.step_sigma, dtype=torch.float32)
+            if tuple(sigma.shape) != (n_run, B):
+                raise ValueError(f"step_sigma: one row of {B} sigmas per step run ({n_run}), got {tuple(sigma.shape)}")
+        else:
+            sigma = self._draw_sigma(model, start, n_run)
+        self.last_sigma = sigma
+        prog = self.build_program(theta_run, sigma).finalize()
+        offset, stride = self._stream(model, start)
+        x, xs, x0s = model.engine().sampler_run(start, model.cond_tensor(energy, layers), prog, seed=getattr(model, "noise_seed", self.seed),
+                                                offset=offset, noise_stride=stride, debug=debug, use_graph=self.use_graph)
+        if debug:
+            return x, list(xs.unbind(0)), list(x0s.unbind(0))
+        return x, [], []
+
+    def optimize_sampler(self, model, loader, num_steps: int) -> torch.Tensor:
+        """Train theta (models/sample.py:1051-1093) on `loader`, an iterable of (E, layers, data) batches; saves it to
+        save_path() and returns it.  sigma: fresh from the model's device Philox stream for every batch (N x B draws at its
+        running offset, which advances), or the step_sigma hook."""
+        from .engine import randn
+        self.check_embedding(model, self.config)
+        eng = model.engine()
+        if not hasattr(eng, "bns_theta_grad"):
+            raise NotImplementedError("BespokeNonStationary: theta training on the layer stage is not provided (the layer model "
+                                      "has no input-gradient VJP)")
+        path = self.save_path()
+        if path is None:
+            raise ValueError("No sampler path provided, set it with 'SAMPLER_PATH' in the config")
+        dev = eng.device
+        theta = torch.nn.Parameter(torch.ones(2, num_steps, device=dev))
+        opt = torch.optim.Adam([theta], lr=self.sample_config.get("LR", 1e-3))
+        hook = self.step_sigma
+        k = 0
+        self.losses = []
+        for _ in range(int(self.sample_config.get("MAX_ITER", 30))):
+            for E, layers, data in loader:
+                data = data.to(dev, torch.float32)
+                B = data.shape[0]
+                if hook is None:
+                    sigma = randn((num_steps, B), dev, getattr(model, "noise_seed", self.seed), getattr(model, "noise_offset", 0))
+                    if hasattr(model, "noise_offset"):
+                        model.noise_offset += num_steps * B
+                else:
+                    sigma = (hook[k] if isinstance(hook, (list, tuple)) else hook).to(dev, torch.float32)
+                k += 1
+                loss, dtheta = eng.bns_theta_grad(data, model.cond_tensor(E, layers), theta, sigma)
+                opt.zero_grad()
+                theta.grad = dtheta
+                opt.step()
+                self.losses.append(float(loss))
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        self.theta = theta.detach().cpu()
+        self.trained = True
+        torch.save(torch.nn.Parameter(self.theta.clone(), requires_grad=True), path)
+        return self.theta

@@ -166,6 +166,8 @@ int cd_ddim_sample(CdPlan* plan, int batch, const float* start, const float* con
                             LINCOMB, but in the operation order of a chain of torch elementwise ops -- every product, sum and the \
                             final division rounded to fp32 on its own, no fused multiply-add (DPM-Solver's eps = (x - D) / sigma \
                             and its cancelling updates, utils/sampling.py:402-456) */
+#define CD_SOP_DENOISE_PS 5 /* buf[dst] = denoise(buf[src[0]]) with row b at sigma_b = coef[col + b], b < batch: a sigma per \
+                               sample (BespokeNonStationary's model_fn, models/sample.py:1107-1109); needs col + batch <= n_coef */
 typedef struct CdSamplerOp {
   int32_t kind, dst, nsrc;
   int32_t src[6];
@@ -244,6 +246,24 @@ int cd_plan_vjp_workspace_bytes(CdPlan* plan, int batch, int with_param_grads, s
 int cd_denoise_vjp(CdPlan* plan, int batch, const float* x, const float* sigma, const float* cond, const float* gy,
                    float* dx, float* grads /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- BespokeNonStationary theta training --------------------------------------------------------------------------- */
+/* One batch of BespokeNonStationary.optimize_sampler (models/sample.py:1060-1085) up to loss.backward(), for theta only:
+ *   x_0 = data;  U_i = denoise(x_i, sigma_i, cond);  x_{i+1} = x_i * a_i + U_i * b_i  (i < n_steps, theta = (a; b), (2, N));
+ *   mse = mean((data - x_N)^2);  loss = mean(20 log10(max(data, axis=-1) / sqrt(mse)))   (every row of the last axis)
+ * loss_out: one double (the reference's value: NaN if a row maximum is negative, -inf if one is 0; 100 if mse == 0, where the
+ * reference's torch.mean raises).  dtheta (2, N): d loss / d theta, as torch autograd forms it: the seed at x_N is
+ * -20 / (ln 10 * mse * numel) * (x_N - data), independent of the maxima -- except that a row maximum of exactly 0 makes torch's
+ * whole gradient NaN (log10's backward divides by 0), and so it is here; mse == 0 gives a zero gradient.  Then for i = N-1 .. 0:
+ * dtheta[0][i] = <g_{i+1}, x_i>, dtheta[1][i] = <g_{i+1}, U_i> (fp64, fixed order: repeated calls are bitwise equal) and
+ * g_i = a_i g_{i+1} + VJP of denoise at (x_i, sigma_i) applied to b_i g_{i+1} (cd_denoise_vjp without grads; skipped at i = 0).
+ * data / cond / theta / sigma are DEVICE arrays; sigma (n_steps, batch): row i holds the sigma of every sample at step i.
+ * Parameter gradients are not formed.  Every x_i and U_i is kept in `workspace` (cd_plan_bns_workspace_bytes: 2 N B voxels
+ * floats plus the input-only VJP's scratch); nothing is allocated and the stream is not synchronised.  Restrictions and the
+ * range flag are those of cd_train_step. */
+int cd_plan_bns_workspace_bytes(CdPlan* plan, int batch, int n_steps, size_t* bytes);
+int cd_bns_theta_grad(CdPlan* plan, int batch, int n_steps, const float* data, const float* cond, const float* theta,
+                      const float* sigma, double* loss_out, float* dtheta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* torch.optim.Adam step (train/train.py:144: Adam(model.parameters(), lr); no amsgrad) over n tensors in ceil(n / 48)
  * launches: params / grads / exp_avg / exp_avg_sq are HOST arrays of n DEVICE pointers, numel their lengths.  step is the
  * 1-based step count after this update (torch's state['step']).  Same element-wise formulas as torch:
@@ -305,7 +325,7 @@ int cd_layer_sample(const CdLayerMlpDesc* desc, const float* const* weights, int
  * per sample with the n_bufs (2..10) state vectors on chip.  Every sampler class of calodiffusion_amd/sample.py that builds a
  * program runs on the layer stage through it.
  * start (B, dim_in): buffer 0 = start * start_scale, the others start at zero.  DENOISE is cd_layer_denoise at
- * sigma = coefs[step][col]; LINCOMB / LINDIV round as cd_sampler_run's.  ops (n_ops), op_begin (NULL, or n_steps + 1 entries)
+ * sigma = coefs[step][col] (DENOISE_PS: sample b at coefs[step][col + b]); LINCOMB / LINDIV round as cd_sampler_run's.  ops (n_ops), op_begin (NULL, or n_steps + 1 entries)
  * and coefs (n_steps, n_coef) are DEVICE arrays.  The k-th RANDN op executed takes the Philox stream elements
  * offset + k * stride + b * dim_in + i, stride = noise_stride ? noise_stride : B * dim_in (cd_sampler_run's convention, so batch
  * shards are slices of one global stream); step_noise, when given: DEVICE (RANDN ops executed, B, dim_in), tensor k instead.
