@@ -678,14 +678,25 @@ struct LayerMlpTrainArgs {
   const float* w[64];
   int dim_in, hidden, cond_emb, cond_size, n_res, time_kind, batch;
   int loss_type = 0;  // CD_LOSS_* (Loss._loss, models/loss.py:97-116): 0 l2 (weighted), 1 l1, 2 mse, 3 huber
+  int objective = 0;  // CD_OBJ_* (objective_residual / objective_weight above)
   float sigma_data;
   const float *data, *noise, *sigma, *cond;  // (B, dim), (B, dim), (B), (B, cond_size)
   LayerTapeLayout layout;
   float* tape;        // [B][layout.total]
   double* loss_part;  // [B]
+  // weight / bias gradients: the kernel that writes the tape also writes linear_wgrad_kernel's job table (workspace)
+  float* grads;
+  LinearWgradJob* jobs;
+  // cd_layer_denoise_vjp: the state x and the upstream gradient gy = dL/dD, both (B, dim); dx = dL/dx
+  const float *x, *gy;
+  float* dx;
 };
 size_t layer_train_workspace_bytes(const LayerMlpTrainArgs& a);
+// loss and, with grads, every parameter gradient; grads == null: the forward and the loss only (cd_layer_loss)
 void launch_layer_mlp_train(LayerMlpTrainArgs a, float* grads, double* loss_out, void* workspace, hipStream_t s);
+size_t layer_vjp_workspace_bytes(const LayerMlpTrainArgs& a, bool with_param_grads);
+// dx and, with grads, every parameter gradient from the caller's gy (cd_layer_denoise_vjp)
+void launch_layer_mlp_vjp(LayerMlpTrainArgs a, float* grads, void* workspace, hipStream_t s);
 
 // fused Adam over up to 48 tensors per launch (kernel-argument table)
 struct AdamChunk {

@@ -1,4 +1,4 @@
-// Entry points outside the plan: the layer-energy MLP (forward, denoise, sampler, training step), the fused Adam step, the
+// Entry points outside the plan: the layer-energy MLP (forward, denoise, sampler, training step, loss, VJP), the fused Adam step, the
 // reverse normalisation, the convolution precision switch and the per-launch profiler.
 #include "plan_internal.h"
 
@@ -160,12 +160,21 @@ int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights
 static LayerMlpTrainArgs layer_train_args(const CdLayerMlpDesc* d, int batch) {
   CD_REQUIRE(d && batch > 0, "bad argument");
   CD_REQUIRE(d->struct_size == sizeof(CdLayerMlpDesc), "CdLayerMlpDesc.struct_size does not match this library's calodiff.h");
-  CD_REQUIRE(d->n_res >= 0 && d->n_res <= 8 && d->time_embed_kind >= 0 && d->time_embed_kind <= 2, "bad descriptor");
+  CD_REQUIRE(d->n_res >= 0 && d->n_res <= 8 && d->time_embed_kind >= 0 && d->time_embed_kind <= 2 && d->objective >= 0 &&
+                 d->objective <= 2,
+             "bad descriptor");
   LayerMlpTrainArgs a{};
   a.dim_in = d->dim_in; a.hidden = d->hidden; a.cond_emb = d->cond_emb; a.cond_size = d->cond_size; a.n_res = d->n_res;
-  a.time_kind = d->time_embed_kind; a.batch = batch; a.sigma_data = d->sigma_data;
+  a.time_kind = d->time_embed_kind; a.objective = d->objective; a.batch = batch; a.sigma_data = d->sigma_data;
   a.layout = layer_tape_layout(a.dim_in, a.hidden, a.cond_emb, a.cond_size, a.n_res);
   return a;
+}
+static void layer_train_weights(LayerMlpTrainArgs& a, const CdLayerMlpDesc* desc, const float* const* weights, int n_weights) {
+  CD_REQUIRE(n_weights == 2 * (8 + 3 * desc->n_res), "layer MLP: n_weights must be 2*(8 + 3*n_res)");
+  for (int i = 0; i < n_weights; ++i) {
+    CD_REQUIRE(weights[i], "null weight pointer");
+    a.w[i] = weights[i];
+  }
 }
 int cd_layer_train_workspace_bytes(const CdLayerMlpDesc* desc, int batch, size_t* bytes) {
   return guarded([&] {
@@ -180,23 +189,54 @@ int cd_layer_train_step(const CdLayerMlpDesc* desc, const float* const* weights,
                                   workspace_bytes, stream);
 }
 
+// the training step (grads) or the loss alone (grads == null) of the descriptor's objective
+static void layer_loss_call(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
+                            const float* noise, const float* sigma, const float* cond, int loss_type, double* loss_out,
+                            float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  CD_REQUIRE(weights && data && noise && sigma && cond && loss_out && workspace, "bad argument");
+  CD_REQUIRE(loss_type >= CD_LOSS_L2 && loss_type <= CD_LOSS_HUBER, "loss_type must be one of CD_LOSS_L2 / L1 / MSE / HUBER");
+  LayerMlpTrainArgs a = layer_train_args(desc, batch);
+  a.loss_type = loss_type;
+  layer_train_weights(a, desc, weights, n_weights);
+  CD_REQUIRE(workspace_bytes >= layer_train_workspace_bytes(a), "workspace too small: call cd_layer_train_workspace_bytes");
+  a.data = data; a.noise = noise; a.sigma = sigma; a.cond = cond;
+  launch_layer_mlp_train(a, grads, loss_out, workspace, (hipStream_t)stream);
+}
 int cd_layer_train_step_loss(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
                              const float* noise, const float* sigma, const float* cond, int loss_type, double* loss_out,
                              float* grads, void* workspace, size_t workspace_bytes, void* stream) {
   return guarded([&] {
-    CD_REQUIRE(weights && data && noise && sigma && cond && loss_out && grads && workspace, "bad argument");
-    CD_REQUIRE(loss_type >= CD_LOSS_L2 && loss_type <= CD_LOSS_HUBER, "loss_type must be one of CD_LOSS_L2 / L1 / MSE / HUBER");
+    CD_REQUIRE(grads, "bad argument");
+    layer_loss_call(desc, weights, n_weights, batch, data, noise, sigma, cond, loss_type, loss_out, grads, workspace, workspace_bytes,
+                    stream);
+  });
+}
+int cd_layer_loss(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
+                  const float* noise, const float* sigma, const float* cond, int loss_type, double* loss_out, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    layer_loss_call(desc, weights, n_weights, batch, data, noise, sigma, cond, loss_type, loss_out, nullptr, workspace,
+                    workspace_bytes, stream);
+  });
+}
+
+int cd_layer_vjp_workspace_bytes(const CdLayerMlpDesc* desc, int batch, int with_param_grads, size_t* bytes) {
+  return guarded([&] {
+    CD_REQUIRE(bytes, "bad argument");
+    *bytes = layer_vjp_workspace_bytes(layer_train_args(desc, batch), with_param_grads != 0);
+  });
+}
+int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* x,
+                         const float* sigma, const float* cond, const float* gy, float* dx, float* grads, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(weights && x && sigma && cond && gy && dx && workspace, "bad argument");
     LayerMlpTrainArgs a = layer_train_args(desc, batch);
-    a.loss_type = loss_type;
-    CD_REQUIRE(desc->objective == CD_OBJ_HYBRID, "cd_layer_train_step implements the hybrid_weight objective");
-    CD_REQUIRE(n_weights == 2 * (8 + 3 * desc->n_res), "layer MLP: n_weights must be 2*(8 + 3*n_res)");
-    CD_REQUIRE(workspace_bytes >= layer_train_workspace_bytes(a), "workspace too small: call cd_layer_train_workspace_bytes");
-    for (int i = 0; i < n_weights; ++i) {
-      CD_REQUIRE(weights[i], "null weight pointer");
-      a.w[i] = weights[i];
-    }
-    a.data = data; a.noise = noise; a.sigma = sigma; a.cond = cond;
-    launch_layer_mlp_train(a, grads, loss_out, workspace, (hipStream_t)stream);
+    layer_train_weights(a, desc, weights, n_weights);
+    CD_REQUIRE(workspace_bytes >= layer_vjp_workspace_bytes(a, grads != nullptr),
+               "workspace too small: call cd_layer_vjp_workspace_bytes");
+    a.x = x; a.gy = gy; a.dx = dx; a.sigma = sigma; a.cond = cond;
+    launch_layer_mlp_vjp(a, grads, workspace, (hipStream_t)stream);
   });
 }
 

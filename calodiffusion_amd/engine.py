@@ -97,6 +97,9 @@ _SIGNATURES = {
     "cd_layer_train_step": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_layer_train_step_loss": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t,
                                            _P]),
+    "cd_layer_loss": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "cd_layer_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cd_layer_denoise_vjp": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_reverse_norm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float, _P]),
     "cd_reverse_norm_staged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_int, _P]),
@@ -589,7 +592,7 @@ class UnetEngine:
 
 class LayerMlpEngine:
     """The layer-energy MLP of LayerDiffusion on the HIP library (cd_layer_forward / cd_layer_denoise / cd_layer_sample /
-    cd_layer_sampler_run).
+    cd_layer_sampler_run; cd_layer_train_step_loss / cd_layer_loss / cd_layer_denoise_vjp).
     Stateless on the library side: the parameters are read in place from the torch storage."""
 
     def __init__(self, resnet, time_kind="raw", objective="hybrid", sigma_data=1.0):
@@ -655,18 +658,31 @@ class LayerMlpEngine:
             off += p.numel()
         return lay, off
 
-    def train_step(self, data, noise, sigma, cond, loss_type="l2"):
-        """hybrid_weight loss (LOSS_TYPE l2 / l1 / mse / huber) and the gradient of every parameter of the layer model
-        (cd_layer_train_step_loss)."""
+    def train_workspace(self, batch: int) -> torch.Tensor:
+        """Workspace of cd_layer_train_step_loss / cd_layer_loss (one kept: the last batch size asked for)."""
+        ws = getattr(self, "_tws", {}).get(int(batch))
+        if ws is None:
+            nbytes = C.c_size_t()
+            _check(self.lib.cd_layer_train_workspace_bytes(C.byref(self.desc), batch, C.byref(nbytes)))
+            self._tws = {}
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=next(self.net.parameters()).device)
+            self._tws = {int(batch): ws}
+        return ws
+
+    def _loss_io(self, data, noise, sigma, cond):
         data, cond, B = self._io(data, cond)
         noise = _dev32(noise, "noise")
         sigma = _dev32(sigma, "sigma").reshape(-1)
         if noise.shape != data.shape or sigma.numel() != B:
             raise ValueError("noise must have the shape of data and sigma must be (B,)")
+        return data, noise, sigma, cond, B
+
+    def train_step(self, data, noise, sigma, cond, loss_type="l2"):
+        """The loss of the engine's objective (hybrid / noise_pred / mean_pred; LOSS_TYPE l2 / l1 / mse / huber) and the gradient
+        of every parameter of the layer model (cd_layer_train_step_loss)."""
+        data, noise, sigma, cond, B = self._loss_io(data, noise, sigma, cond)
         w, n = self._weights()
-        nbytes = C.c_size_t()
-        _check(self.lib.cd_layer_train_workspace_bytes(C.byref(self.desc), B, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=data.device)
+        ws = self.train_workspace(B)
         _, total = self.grad_layout()
         flat = torch.empty(total, dtype=torch.float32, device=data.device)
         loss = torch.empty((), dtype=torch.float64, device=data.device)
@@ -675,6 +691,49 @@ class LayerMlpEngine:
                                                  ws.data_ptr(), ws.numel(), _stream()))
         return loss, flat
 
+    def loss(self, data, noise, sigma, cond, loss_type="l2"):
+        """The same loss without any gradient work (cd_layer_loss): a 0-d fp64 tensor, bitwise train_step's value."""
+        data, noise, sigma, cond, B = self._loss_io(data, noise, sigma, cond)
+        w, n = self._weights()
+        ws = self.train_workspace(B)
+        loss = torch.empty((), dtype=torch.float64, device=data.device)
+        _check(self.lib.cd_layer_loss(C.byref(self.desc), w, n, B, data.data_ptr(), noise.data_ptr(), sigma.data_ptr(),
+                                      cond.data_ptr(), LOSS_TYPES[loss_type], loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return loss
+
+    def vjp_workspace(self, batch: int, with_param_grads: bool) -> torch.Tensor:
+        """Workspace of cd_layer_denoise_vjp (one kept: the last batch size and mode asked for)."""
+        key = (int(batch), bool(with_param_grads))
+        ws = getattr(self, "_vws", {}).get(key)
+        if ws is None:
+            nbytes = C.c_size_t()
+            _check(self.lib.cd_layer_vjp_workspace_bytes(C.byref(self.desc), batch, int(bool(with_param_grads)), C.byref(nbytes)))
+            self._vws = {}  # (release the previous one before allocating the next)
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=next(self.net.parameters()).device)
+            self._vws = {key: ws}
+        return ws
+
+    def denoise_vjp(self, x, sigma, cond, gy, param_grads: bool):
+        """Vector-Jacobian product of denoise (cd_layer_denoise_vjp): dx = dL/dx for gy = dL/dD, and with ``param_grads`` the
+        gradient of every parameter as a flat fp32 buffer (see grad_layout), else None.  sigma and cond are constants."""
+        x, cond, B = self._io(x, cond)
+        gy = _dev32(gy, "gy")
+        sigma = _dev32(sigma, "sigma").reshape(-1)
+        if sigma.numel() == 1 and B > 1:
+            sigma = sigma.expand(B).contiguous()
+        if gy.shape != x.shape or sigma.numel() != B:
+            raise ValueError(f"denoise_vjp shapes: x {tuple(x.shape)}, gy {tuple(gy.shape)}, sigma {tuple(sigma.shape)}")
+        w, n = self._weights()
+        ws = self.vjp_workspace(B, param_grads)
+        dx = torch.empty_like(x)
+        flat = None
+        if param_grads:
+            _, total = self.grad_layout()
+            flat = torch.empty(total, dtype=torch.float32, device=x.device)
+        _check(self.lib.cd_layer_denoise_vjp(C.byref(self.desc), w, n, B, x.data_ptr(), sigma.data_ptr(), cond.data_ptr(),
+                                             gy.data_ptr(), dx.data_ptr(), _ptr(flat), ws.data_ptr(), ws.numel(), _stream()))
+        return dx, flat
+
     def param_grads(self, flat):
         """Views of the flat gradient buffer, one per parameter of the bound ResNet, in .parameters() order."""
         lay, _ = self.grad_layout()
@@ -682,7 +741,7 @@ class LayerMlpEngine:
         return [flat[lay[names[id(p)]][0]: lay[names[id(p)]][0] + p.numel()].view_as(p) for p in self.net.parameters()]
 
     def loss_hybrid(self, data, noise, sigma, cond, loss_type="l2"):
-        return self.train_step(data, noise, sigma, cond, loss_type)[0].to(torch.float32)
+        return self.loss(data, noise, sigma, cond, loss_type).to(torch.float32)
 
     def loss_hybrid_l2(self, data, noise, sigma, cond):
         return self.loss_hybrid(data, noise, sigma, cond, "l2")

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import utils
-from .calodiffusion import CaloDiffusion
+from .calodiffusion import CaloDiffusion, _Denoise
 from .resnet import ResNet
 
 
@@ -66,7 +66,8 @@ class LayerDiffusion(CaloDiffusion):
 
     def compute_loss(self, data, energy, noise, layers, time=None, rnd_normal=None):
         """layerdiffusion.py:52-57: in the layer state the layer model is trained on the layer energies themselves (fresh noise
-        of their shape); one cd_layer_train_step call gives the loss and every gradient."""
+        of their shape); one cd_layer_train_step_loss call gives the loss of the config's TRAINING_OBJ and every gradient, one
+        cd_layer_loss call the loss alone when no gradient is asked for."""
         if self.layer_loss:
             layers = layers.to(torch.float32)
             noise = self.noise_generation(layers.shape).to(torch.float32)
@@ -118,7 +119,17 @@ class LayerDiffusion(CaloDiffusion):
 
     # ------------------------------------------------------------------ hot path
     def denoise(self, x, E=None, sigma=None, layers=None, controls=None):
+        """In the layer state: cd_layer_denoise on the (B, D+1) layer energies, differentiable under the rule of
+        CaloDiffusion.denoise -- with ``torch.is_grad_enabled()`` and ``x.requires_grad`` the backward is one cd_layer_denoise_vjp
+        call (x's gradient and, if a parameter requires grad, every parameter's); sigma and E are constants of the graph.  Any
+        other call is the plain call without a graph."""
         if self.layer_loss:
+            if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:
+                for name, t in (("sigma", sigma), ("E", E)):
+                    if isinstance(t, torch.Tensor) and t.requires_grad:
+                        raise NotImplementedError(f"denoise: no gradient with respect to {name}; pass {name}.detach()")
+                params = list(self.layer_model.parameters())
+                return _Denoise.apply(self.layer_model.engine(), x, sigma.reshape(-1), self.cond_tensor(E, None), *params)
             return self.layer_model.engine().denoise(x, sigma.reshape(-1), self.cond_tensor(E, None))
         return super().denoise(x, E=E, sigma=sigma, layers=layers, controls=controls)
 

@@ -967,8 +967,8 @@ class BespokeNonStationary(Sample):
         self.check_embedding(model, self.config)
         eng = model.engine()
         if not hasattr(eng, "bns_theta_grad"):
-            raise NotImplementedError("BespokeNonStationary: theta training on the layer stage is not provided (the layer model "
-                                      "has no input-gradient VJP)")
+            raise NotImplementedError("BespokeNonStationary: theta training on the layer stage is not provided (the "
+                                      "reference's loop feeds the 5-D shower batch to the layer MLP)")
         path = self.save_path()
         if path is None:
             raise ValueError("No sampler path provided, set it with 'SAMPLER_PATH' in the config")

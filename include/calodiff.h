@@ -340,19 +340,42 @@ int cd_layer_sampler_run(const CdLayerMlpDesc* desc, const float* const* weights
                          uint64_t offset, uint64_t noise_stride, float* x_out, float* xs, float* x0s, void* stream);
 
 /* Training step of the layer model (LayerDiffusion.compute_loss in the layer state, models/layerdiffusion.py:52-57, with
- * the hybrid_weight / l2 loss of models/loss.py:103-104,118-142,163-179): data = layer energies (B, dim_in), noise (B, dim_in),
- * sigma (B), cond (B, cond_size).  loss_out: one double; grads: ONE flat device buffer holding the gradient of every parameter
- * in the order of `weights` (weight, bias, weight, bias, ...), each with the parameter's element count.  The objective must be
- * CD_OBJ_HYBRID.  workspace: cd_layer_train_workspace_bytes. */
+ * the l2 loss of models/loss.py:103-104,118-142): data = layer energies (B, dim_in), noise (B, dim_in), sigma (B),
+ * cond (B, cond_size).  loss_out: one double; grads: ONE flat device buffer holding the gradient of every parameter in the
+ * order of `weights` (weight, bias, weight, bias, ...), each with the parameter's element count.  The objective is the
+ * descriptor's CD_OBJ_* (see cd_layer_train_step_loss).  workspace: cd_layer_train_workspace_bytes.  Nothing is allocated and
+ * the stream is not synchronised. */
 int cd_layer_train_workspace_bytes(const CdLayerMlpDesc* desc, int batch, size_t* bytes);
 int cd_layer_train_step(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
                         const float* noise, const float* sigma, const float* cond, double* loss_out, float* grads,
                         void* workspace, size_t workspace_bytes, void* stream);
 /* The same for every LOSS_TYPE of Loss._loss (models/loss.py:97-116; cd_layer_train_step is loss_type CD_LOSS_L2): the reference's
- * CI fixture trains the layer model with 'huber' (tests/test_execution.py:94). */
+ * CI fixture trains the layer model with 'huber' (tests/test_execution.py:94).  Every objective of the descriptor, with pred /
+ * target / weight as models/loss.py:163-210 defines them on x_noisy = data + sigma noise (the weight enters 'l2' only):
+ *   CD_OBJ_HYBRID      pred = denoise(x_noisy)                                   target = data   weight 1 + sigma^-2
+ *   CD_OBJ_NOISE_PRED  pred = (data - (data - sigma denoise(x_noisy))) / sigma   target = noise  weight 1
+ *   CD_OBJ_MEAN_PRED   pred = denoise(x_noisy) = F                               target = data   weight sigma^-2 */
 int cd_layer_train_step_loss(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
                              const float* noise, const float* sigma, const float* cond, int loss_type /* CD_LOSS_* */,
                              double* loss_out, float* grads, void* workspace, size_t workspace_bytes, void* stream);
+/* The loss of cd_layer_train_step_loss alone (validation): the same kernel without its tape and backward, and no
+ * weight-gradient launch; loss_out is bitwise the training step's.  workspace: cd_layer_train_workspace_bytes. */
+int cd_layer_loss(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* data,
+                  const float* noise, const float* sigma, const float* cond, int loss_type /* CD_LOSS_* */, double* loss_out,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace of cd_layer_denoise_vjp at this batch: with_param_grads 0 sizes the input-gradient-only call (grads == NULL), 1 the
+ * call that also writes grads (the per-sample tape). */
+int cd_layer_vjp_workspace_bytes(const CdLayerMlpDesc* desc, int batch, int with_param_grads, size_t* bytes);
+/* Vector-Jacobian product of cd_layer_denoise: given D = cd_layer_denoise(x, sigma, cond) and gy = dL/dD (B, dim_in), writes
+ * dx = dL/dx (B, dim_in) and, when grads is not NULL, dL/dW of every parameter into the flat buffer of cd_layer_train_step
+ * (overwritten, not accumulated; fixed-order sums: repeated calls are bitwise equal).  sigma and cond are constants.  Every
+ * objective and time embedding of the descriptor.  The forward is recomputed inside the call (one launch; one more for the
+ * parameter gradients).  With grads == NULL no tape is written, no parameter-gradient work is launched and dx is bitwise the dx
+ * of the call with grads.  All scratch is in `workspace`; nothing is allocated and the stream is not synchronised. */
+int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights, int n_weights, int batch, const float* x,
+                         const float* sigma, const float* cond, const float* gy, float* dx, float* grads /* nullable */,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
