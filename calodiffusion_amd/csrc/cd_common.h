@@ -628,6 +628,20 @@ struct ReverseNormArgs {
 };
 void launch_reverse_norm(const ReverseNormArgs& a, hipStream_t s);
 
+// Forward pre-processing of raw showers (preprocess_shower + the incident-energy map of DataLoaderCaloChall,
+// calodiffusion/utils/utils.py:290-312, 315-436), the inverse of the above for the same regular-grid configurations
+struct PreprocessArgs {
+  const float* showers;  // (B, D*H*W) raw voxel energies
+  const float* energy;   // (B) raw incident energies, same unit as the showers
+  float* out;            // (B, 1, D, H, W) normalised-space showers
+  float* layerE;         // (B, 1 + D) normalised {total, layers}, or null: 'logit-norm'
+  float* e_out;          // (B, 1) conditioning energy
+  int32_t* status;       // 0, or 1 + the highest index of a shower without energy (see cd_preprocess)
+  int batch, D, H, W, layer_mode, logE;
+  float logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std, max_deposit, emin, emax, scale;
+};
+void launch_preprocess(const PreprocessArgs& a, hipStream_t s);
+
 // LayerDiffusion's layer-energy MLP: raw forward (mode 0), EDM denoise (mode 1) or a whole sampler trajectory (mode 2)
 struct LayerMlpArgs {
   const float* w[64];    // (weight, bias) per Linear in the reference ResNet's state_dict order

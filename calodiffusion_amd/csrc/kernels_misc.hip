@@ -762,6 +762,113 @@ void launch_reverse_norm(const ReverseNormArgs& a, hipStream_t s) {
   CD_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Forward pre-processing of raw showers (preprocess_shower, calodiffusion/utils/utils.py:315-436, and the incident-energy map of
+// DataLoaderCaloChall, :290-312, for the regular grids: dataset_num 2 / 3, showerMap 'layer-logit-norm' / 'logit-norm'): the
+// inverse of reverse_norm_kernel.  One workgroup per shower, so nothing depends on the batch or on how it is sharded:
+//   pass 1 (layer maps only)  q = shower / (max_deposit e) in fp32, as the reference forms it; one wave per calorimeter layer
+//                             sums its q in fp64 (lane-strided, then a xor butterfly: a fixed order), the total is the sum of
+//                             the layer sums in layer order; layerE from those in fp64, rounded once.  q is kept in LDS when
+//                             the shower fits (Dataset-2: 25.9 KB), so the voxels are read once; otherwise pass 2 reads them again.
+//   pass 2                    logit (alpha 1e-6) and normalisation of every voxel, float4 wide.
+// A shower without energy (e <= 0, NaN, or no deposit at all) is where the reference's masked arrays return fill values: it
+// is reported through `status` instead (its layerE row is not written).
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kPreThreads = 512;
+constexpr size_t kPreCacheBytes = 48 * 1024;  // q of one shower in LDS up to this size
+constexpr float kLogitAlpha = 1e-6f;                         // utils.py:240-243; numpy rounds the python scalars to the
+constexpr float kLogitScale = (float)(1.0 - 2.0 * 1e-6);     // array's float32 before it multiplies
+
+__device__ __forceinline__ float pre_voxel(float q, float mean, float std) {
+  const float o = kLogitAlpha + kLogitScale * q;
+  return (logf(o / (1.f - o)) - mean) / std;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kPreThreads) preprocess_kernel(PreprocessArgs a, int cache_q) {
+  extern __shared__ double pre_smem[];  // D layer sums (padded to 16 bytes), then q when cache_q
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int PV = a.H * a.W, N = a.D * PV;
+  const float* v = a.showers + (size_t)b * N;
+  float* out = a.out + (size_t)b * N;
+  const float e = a.energy[b] * a.scale;
+  const float denom = a.max_deposit * e;
+  if (!(e > 0.f) || isinf(e)) {  // uniform over the workgroup
+    if (tid == 0) atomicMax(a.status, b + 1);
+    return;
+  }
+  if (tid == 0) {
+    // utils.py:307-310: float32 quotient and float32 log10, divided by the python float log10(emax / emin)
+    if (a.logE) a.e_out[b] = (float)((double)(float)log10((double)(e / a.emin)) / log10((double)a.emax / (double)a.emin));
+    else a.e_out[b] = (e - a.emin) / (a.emax - a.emin);
+  }
+  float* q_lds = (float*)(pre_smem + ((a.D + 1) & ~1));
+  if (a.layer_mode) {
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int z = wave; z < a.D; z += kPreThreads / 64) {
+      double acc = 0.0;
+      for (int i = lane; i < PV; i += 64) {
+        const float q = (v[z * PV + i] * a.scale) / denom;
+        if (cache_q) q_lds[z * PV + i] = q;
+        acc += (double)q;
+      }
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      if (lane == 0) pre_smem[z] = acc;
+    }
+    __syncthreads();
+    double total = 0.0;
+    for (int z = 0; z < a.D; ++z) total += pre_smem[z];  // every thread, layer order
+    if (!(total > 0.0)) {
+      if (tid == 0) atomicMax(a.status, b + 1);
+      return;
+    }
+    float* le = a.layerE + (size_t)b * (a.D + 1);
+    if (tid == 0) le[0] = (float)((total - (double)a.totalE_mean) / (double)a.totalE_std);
+    for (int z = tid; z < a.D; z += kPreThreads) {
+      const double o = (double)kLogitAlpha + (double)kLogitScale * (pre_smem[z] / total);
+      le[1 + z] = (float)((log(o / (1.0 - o)) - (double)a.layers_mean) / (double)a.layers_std);
+    }
+  }
+  int nonzero = 0;
+  if ((N & 3) == 0) {
+    const float4* v4 = (const float4*)v;
+    const float4* q4 = (const float4*)q_lds;
+    float4* o4 = (float4*)out;
+    for (int i = tid; i < N / 4; i += kPreThreads) {
+      float4 q;
+      if (cache_q) {
+        q = q4[i];
+      } else {
+        q = v4[i];
+        q.x = (q.x * a.scale) / denom; q.y = (q.y * a.scale) / denom; q.z = (q.z * a.scale) / denom; q.w = (q.w * a.scale) / denom;
+      }
+      nonzero |= (q.x != 0.f) | (q.y != 0.f) | (q.z != 0.f) | (q.w != 0.f);
+      float4 r;
+      r.x = pre_voxel(q.x, a.logit_mean, a.logit_std); r.y = pre_voxel(q.y, a.logit_mean, a.logit_std);
+      r.z = pre_voxel(q.z, a.logit_mean, a.logit_std); r.w = pre_voxel(q.w, a.logit_mean, a.logit_std);
+      o4[i] = r;
+    }
+  } else {
+    for (int i = tid; i < N; i += kPreThreads) {
+      const float q = cache_q ? q_lds[i] : (v[i] * a.scale) / denom;
+      nonzero |= q != 0.f;
+      out[i] = pre_voxel(q, a.logit_mean, a.logit_std);
+    }
+  }
+  // 'logit-norm' has no layer sums: a shower with no deposit at all is found here
+  if (!a.layer_mode && !__syncthreads_or(nonzero) && tid == 0) atomicMax(a.status, b + 1);
+}
+
+void launch_preprocess(const PreprocessArgs& a, hipStream_t s) {
+  const size_t n_bytes = (size_t)a.D * a.H * a.W * sizeof(float);
+  const int cache_q = a.layer_mode && n_bytes <= kPreCacheBytes;
+  const size_t lds = (size_t)((a.D + 1) & ~1) * sizeof(double) + (cache_q ? n_bytes : 0);
+  CD_HIP(hipMemsetAsync(a.status, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)a.batch), dim3(kPreThreads), lds, s, a, cache_q);
+  CD_HIP(hipGetLastError());
+}
+
 
 // ------------------------------------------------------------------------------------------------------------
 // BespokeNonStationary theta gradient (cd_bns_theta_grad, bns.hip).  Every reduction runs over a grid whose size depends on

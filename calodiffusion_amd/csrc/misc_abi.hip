@@ -1,5 +1,5 @@
 // Entry points outside the plan: the layer-energy MLP (forward, denoise, sampler, training step, loss, VJP), the fused Adam step, the
-// reverse normalisation, the convolution precision switch and the per-launch profiler.
+// reverse normalisation and its forward map, the convolution precision switch and the per-launch profiler.
 #include "plan_internal.h"
 
 #include <cstring>
@@ -51,6 +51,26 @@ int cd_reverse_norm_staged(const float* voxels, const float* energy, const float
     a.layers_mean = consts[4]; a.layers_std = consts[5]; a.max_deposit = max_deposit; a.ecut = ecut;
     a.stage = stage; a.alpha = alpha; a.layer_eps = layer_eps;
     launch_reverse_norm(a, (hipStream_t)stream);
+  });
+}
+
+int cd_preprocess(const float* showers, const float* energy, float* out, float* layerE, float* e_out, int32_t* status, int batch,
+                  const int32_t dims[3], const float consts[6], float max_deposit, float emin, float emax, int logE,
+                  float shower_scale, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(showers && energy && out && e_out && status && dims && consts && batch > 0, "bad argument");
+    CD_REQUIRE(dims[0] > 0 && dims[0] <= 4096 && dims[1] > 0 && dims[2] > 0 &&
+                   (int64_t)dims[0] * dims[1] * dims[2] <= ((int64_t)1 << 28),
+               "cd_preprocess: dims = {layers <= 4096, phi, r}, at most 2^28 voxels per shower");
+    CD_REQUIRE(max_deposit > 0.f && shower_scale > 0.f && emax > emin && (!logE || emin > 0.f),
+               "cd_preprocess: max_deposit and shower_scale must be positive, emax > emin (> 0 with logE)");
+    PreprocessArgs a;
+    a.showers = showers; a.energy = energy; a.out = out; a.layerE = layerE; a.e_out = e_out; a.status = status; a.batch = batch;
+    a.D = dims[0]; a.H = dims[1]; a.W = dims[2]; a.layer_mode = layerE ? 1 : 0; a.logE = logE ? 1 : 0;
+    a.logit_mean = consts[0]; a.logit_std = consts[1]; a.totalE_mean = consts[2]; a.totalE_std = consts[3];
+    a.layers_mean = consts[4]; a.layers_std = consts[5]; a.max_deposit = max_deposit; a.emin = emin; a.emax = emax;
+    a.scale = shower_scale;
+    launch_preprocess(a, (hipStream_t)stream);
   });
 }
 

@@ -291,6 +291,22 @@ int cd_reverse_norm_staged(const float* voxels, const float* energy, const float
                            const int32_t dims[3], const float consts[6], float max_deposit, float ecut, float alpha, float layer_eps,
                            int stage, void* stream);
 
+/* Forward pre-processing of raw showers on the device, the inverse of cd_reverse_norm: utils.preprocess_shower
+ * (calodiffusion/utils/utils.py:315-436) and the incident-energy map of DataLoaderCaloChall (:290-312, shower_scale included)
+ * for the regular grids (dataset_num 2 / 3; showerMap 'layer-logit-norm' when layerE != NULL, 'logit-norm' otherwise).
+ * showers (B, D*H*W) raw voxel energies and energy (B) raw incident energies, both multiplied by shower_scale first (0.001
+ * for the CaloChallenge files, 1 for arrays that are already scaled); out (B,1,D,H,W) = (logit(showers / (max_deposit e))
+ * - logit_mean) / logit_std with logit's alpha 1e-6; layerE (B, 1+D) = {(total - totalE_mean) / totalE_std,
+ * (logit(layer / total) - layers_mean) / layers_std} or NULL; e_out (B,1) = log10(e / emin) / log10(emax / emin) if logE,
+ * else (e - emin) / (emax - emin).  consts as for cd_reverse_norm.  One workgroup per shower: layer sums are taken in fp64 in
+ * a fixed order, so a row does not depend on the batch it is in.  status: ONE device int32, zeroed by the call, then 1 + the
+ * highest index of a shower with e <= 0 (or NaN / inf) or without any deposit -- where the reference's masked arrays return
+ * fill values; the outputs of such a row are undefined.  Nothing is allocated and the stream is not synchronised: read
+ * status after the stream has finished. */
+int cd_preprocess(const float* showers, const float* energy, float* out, float* layerE, float* e_out, int32_t* status, int batch,
+                  const int32_t dims[3], const float consts[6], float max_deposit, float emin, float emax, int logE,
+                  float shower_scale, void* stream);
+
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
  * (calodiffusion/models/layerdiffusion.py:35-38, 114-132) samples the (B, D+1) {total, per-layer} energies with.
