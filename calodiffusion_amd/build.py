@@ -19,15 +19,15 @@ LIBDIR = os.path.join(HERE, "lib")
 # its own object directory; load it with CALODIFF_LIB=.../libcalodiff_hip_<tag>.so
 TAG = os.environ.get("CD_BUILD_TAG", "")
 LIB = os.path.join(LIBDIR, f"libcalodiff_hip{'_' + TAG if TAG else ''}.so")
-SOURCES = ["kernels_conv.hip", "kernels_conv_zs.hip", "kernels_attn.hip", "kernels_conv_small.hip", "kernels_deep.hip", "kernels_wgrad16.hip", "kernels_norm_attn.hip", "kernels_misc.hip", "kernels_mlp.hip", "kernels_mlp_train.hip", "kernels_bwd.hip", "profiler.hip", "plan.hip",
+SOURCES = ["kernels_conv.hip", "kernels_conv_zs.hip", "kernels_attn.hip", "kernels_conv_small.hip", "kernels_deep.hip", "kernels_deep_side.hip", "kernels_wgrad16.hip", "kernels_norm_attn.hip", "kernels_misc.hip", "kernels_mlp.hip", "kernels_mlp_train.hip", "kernels_bwd.hip", "profiler.hip", "plan.hip",
            "forward.hip", "sampler.hip", "train.hip", "bns.hip", "ops.hip", "misc_abi.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 FLAGS += os.environ.get("CD_EXTRA_HIPCC_FLAGS", "").split()  # e.g. -DCD_ZS_EXPERIMENTS (tools/zs_stamps.sh, tools/zs_power.sh)
 # per-file flags.  kernels_conv_zs.hip: MFMA results in vector registers (the one-wave-per-SIMD kernel keeps its weights in the
 # accumulation file and sums its partial tiles straight from the MFMA destinations; the default AGPR form costs a
-# v_accvgpr_read per accumulator register and step)
-FILE_FLAGS = {"kernels_conv_zs.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# v_accvgpr_read per accumulator register and step); kernels_deep_side.hip builds a kernel from the same wave program
+FILE_FLAGS = {"kernels_conv_zs.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "kernels_deep_side.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _file_digest(paths, extra: str = "") -> str:

@@ -127,6 +127,9 @@ struct ConvFusion {
   // honour it and set *add_done = 1 on the host; any other kernel ignores it and the caller adds the tensor itself.
   const float* add_src = nullptr;
   int* add_done = nullptr;
+  // z-slide kernel only: deal every strip in this many chunks instead of the launcher's own count (0).  Chunking along voxels changes
+  // no output's summation order, only the grouping of the statistics partials (cd_op_zslide_conv: the test of exactly that).
+  int zs_chunks = 0;
   // Output side of a ResnetBlock's second conv on a grid small enough for one workgroup to see a whole (sample, 32-channel tile)
   // (kernels_conv_small.hip): the kernel applies the block's closing GroupNorm + SiLU and adds the shortcut itself,
   //   out = silu(gn(conv + bias)) + (res0 | res1),
@@ -442,6 +445,23 @@ struct DeepLevelDesc {
 };
 bool deep_level_eligible(const DeepLevelDesc& d);
 void launch_deep_level(const DeepLevelDesc& d, const float* x_in, float* x_out, int batch, int* status, hipStream_t s);
+// The same launch with a side job on the CUs the level leaves idle (kernels_deep_side.hip): one 32-channel K-block of a
+// full-resolution 3x3x3 conv whose input does not depend on the level -- out = conv(in, that K-block's weights) + bias, whole tensor.
+// The rest of the conv follows as a continuation launch of the z-slide kernel (ConvFusion::add_src = out).
+struct DeepSideConv {
+  const float* in = nullptr;  // (B, vox, ldc) channels-last, offset to the first of the K-block's `cin` channels
+  int ldc = 0, cin = 0;
+  const void* wpk = nullptr;  // f16x2 image of the conv, offset to the K-block's first k-step
+  const float* bias = nullptr;
+  float* out = nullptr;       // (B, vox, cout)
+  int cout = 0;
+  Dims3 dims{};
+};
+// chunks per sample the side job would be dealt in, 0 = this conv / batch / environment does not qualify (CD_NO_DEEP_SIDE_CONV=1
+// forces that: the conv then runs after the level as before)
+int deep_side_conv_chunks(int batch, int cin_side, int cout, Dims3 dims);
+void launch_deep_level_side(const DeepLevelDesc& d, const float* x_in, float* x_out, int batch, int* status, const DeepSideConv& side,
+                            hipStream_t s);
 // whole attention block in one launch for small grids (kernels_attn.hip: attn_small_kernel)
 bool attn_small_eligible(int64_t vox);
 void launch_attn_small(const float* x, int C, const float* coef, const void* wqkv_f16x2, float* partials, const float* w_out,

@@ -3,6 +3,7 @@
 // hybrid_weight loss).  Nothing here allocates or synchronises inside a compute call, so a sampler step is hipGraph-capturable.
 #include "plan_internal.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 namespace cd {
@@ -69,6 +70,31 @@ float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1
   return part;
 }
 
+// The x half of a concat conv whose x1 half already ran as the side job of the deepest level's launch (kernels_deep_side.hip):
+// `out` holds conv(x1, second K-block) + bias; this is the one continuation launch of the z-slide kernel that adds the first
+// K-block to it (ConvFusion::add_src) and emits the channel partials.  Same partial buffer and units as conv3_with_stats.
+static float* conv3_x_half_with_stats(Run& r, const float* x0, int c0, int c1, const void* wpk3, float* out, int cout, Dims3 dims,
+                                      int* units) {
+  const int64_t vox = dims.vox();
+  const int cap = (int)((vox + 31) / 32);
+  float* part = r.ws->get<float>((size_t)r.B * cap * cout * 2);
+  int u = 0;
+  if (!r.dry()) {
+    ConvGeom g{dims, dims, 3, 3, 3, 1, 1, 1};
+    ConvFusion fu;
+    int added = 0;
+    fu.act = 1; fu.ch_part = part; fu.units = &u; fu.status = r.status; fu.add_src = out; fu.add_done = &added;
+    char cat[128];
+    std::snprintf(cat, sizeof cat, "conv3x3x3_s1 C%d(of %d)->%d @%dx%dx%d", c0, c0 + c1, cout, dims.d, dims.h, dims.w);
+    prof::Scope scope(cat, r.s, 2.0 * 27 * c0 * cout * (double)vox * r.B, 4.0 * r.B * (double)vox * (c0 + 2 * cout));
+    const bool ran = try_launch_conv_zslide(x0, c0, nullptr, 0, (const char*)wpk3 + packed_bf16x3_bytes(c0 + c1, cout, 27), nullptr, out,
+                                            r.B, cout, g, r.s, fu);
+    CD_REQUIRE(ran && added && u > 0, "internal: the x half of a side conv must run as a z-slide continuation");
+  }
+  *units = u;
+  return part;
+}
+
 // ResnetBlock.forward (models.py:191-200): block1 -> (+ mlp(cond)) -> block2 -> + res_conv(x).
 //   conv1 (stats epilogue) -> finalize -> conv2 normalises h1 while staging it (stats epilogue) -> finalize ->
 //   one elementwise pass: silu(gn(h2)) + shortcut.  `part_out`/`units_out` (optional): channel partials of the block
@@ -76,24 +102,28 @@ float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1
 // `lazy` (optional): leave the closing GroupNorm + SiLU + identity shortcut to the consumer (the head kernel).  If the block
 // qualifies it returns its second conv's raw output, lazy->gn describes the normalisation, lazy->part (to be released by the
 // caller) holds its partials and the shortcut is x0.
+// `h1_side` (optional): the first conv's output buffer, a workspace block this call takes over, in which the x1 half of that conv
+// (and its bias) has already been computed -- only the x0 half is left to add (conv3_x_half_with_stats).
 struct LazyClose {
   GnDefer gn;
   float* part = nullptr;
   bool on = false;
 };
 float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
-                 float** part_out, int* units_out, LazyClose* lazy) {
+                 float** part_out, int* units_out, LazyClose* lazy, float* h1_side) {
   Arena* ws = r.ws;
   CD_REQUIRE(c0 + c1 == w.cin, "internal: resnet block input width mismatch");
   const int64_t vox = dims.vox();
   const int G = r.groups;
   int u1 = 0, u2 = 0;
   static const bool defer_gn = getenv("CD_NO_GNDEFER") == nullptr;  // consumers fold the GroupNorm coefficients (gn_defer.h)
-  float* h1 = ws->get<float>((size_t)r.B * vox * w.cout);
+  float* h1 = h1_side ? h1_side : ws->get<float>((size_t)r.B * vox * w.cout);
   // a 32-channel block on a grid of <= 128 voxels is ONE launch (kernels_conv_small.hip): decided below, once the shortcut exists
   const bool whole = vox <= 128 && w.cout == 32 && defer_gn && conv_precision() == PREC_F16X2 && w.c1w3 && w.c2w3;
   float* p1 = nullptr;
-  if (!whole) p1 = conv3_with_stats(r, x0, c0, x1, c1, w.c1w, w.c1w3, w.c1b, h1, w.cout, dims, nullptr, &u1);
+  CD_REQUIRE(!h1_side || (!whole && c1 > 0), "internal: a side conv belongs to a concat conv on a full-resolution grid");
+  if (h1_side) p1 = conv3_x_half_with_stats(r, x0, c0, c1, w.c1w3, h1, w.cout, dims, &u1);
+  else if (!whole) p1 = conv3_with_stats(r, x0, c0, x1, c1, w.c1w, w.c1w3, w.c1b, h1, w.cout, dims, nullptr, &u1);
   else p1 = ws->get<float>((size_t)r.B * ((vox + 31) / 32) * w.cout * 2);  // (same block as conv3_with_stats would take)
   float* coef1 = ws->get<float>((size_t)r.B * w.cout * 4);
   GnDefer d1;
@@ -482,11 +512,33 @@ float* unet_body(CdPlan* p, Run& r, const float* emb, float* h, LazyClose* lazy 
   // The deepest level (downs[-1], the mid blocks, ups[0] up to its transposed conv) as ONE launch where a sample is <= 128 voxels
   DeepLevelDesc deep;
   const bool deep_on = deep_level_desc(p, emb, &deep);
+  // ... and, in the same launch, on the CUs that level leaves idle: the skip half of the first conv of level 0's first up-block,
+  // conv(cat(x, skips[0])) -- skips[0] is final long before, x only after everything below level 0 (kernels_deep_side.hip).  The
+  // conv's output is allocated here, the x half is added by res_block when it gets there.  Anything not eligible (and the training
+  // tape, the VJP and the full-range precisions, none of which come through here with deep_on) runs the conv whole, as before.
+  const ResW& side_w = p->ups[nres - 1].r1;
+  const int side_c = nres >= 2 ? d.layer_sizes[1] : 0;
+  const bool side_on = deep_on && nres >= 2 && side_w.cin == 2 * side_c && p->packed3(side_w.c1w) &&
+                       deep_side_conv_chunks(r.B, side_c, side_w.cout, p->shapes[0]) > 0;
+  float* side_h1 = nullptr;
   for (int i = 0; i < nres; ++i) {
     const Dims3 dims = p->shapes[i];
     if (deep_on && i == nres - 1) {
       float* y = r.ws->get<float>((size_t)r.B * dims.vox() * cx);
-      if (!r.dry()) launch_deep_level(deep, x, y, r.B, r.status, r.s);
+      if (side_on) {
+        side_h1 = r.ws->get<float>((size_t)r.B * p->shapes[0].vox() * side_w.cout);
+        if (!r.dry()) {
+          DeepSideConv sc;
+          sc.in = skips[0]; sc.ldc = side_c; sc.cin = side_c;
+          // f16x2 image [k-step][tap][ct][term][lane] x 16 B: the skip channels are k-steps side_c / 16 onwards
+          sc.wpk = (const char*)p->packed3(side_w.c1w) + packed_bf16x3_bytes(side_w.cin, side_w.cout, 27) +
+                   (size_t)(side_c / 16) * 27 * (side_w.cout / 32) * 128 * 16;
+          sc.bias = p->raw(side_w.c1b); sc.out = side_h1; sc.cout = side_w.cout; sc.dims = p->shapes[0];
+          launch_deep_level_side(deep, x, y, r.B, r.status, sc, r.s);
+        }
+      } else if (!r.dry()) {
+        launch_deep_level(deep, x, y, r.B, r.status, r.s);
+      }
       r.ws->release(x);
       x = y;
       break;
@@ -546,7 +598,8 @@ float* unet_body(CdPlan* p, Run& r, const float* emb, float* h, LazyClose* lazy 
     const int cs = d.layer_sizes[lv + 1];  // width of the skip (and of x after the previous stage)
     if (!(deep_on && i == 0)) {  // (the deep-level launch already ran ups[0]'s blocks: x is their output, layer_sizes[lv] wide)
       CD_REQUIRE(cx == cs, "internal: up path width mismatch");
-      t = res_block(r, resolve(p, p->ups[i].r1, emb), x, cx, skips[lv], cs, dims);
+      t = res_block(r, resolve(p, p->ups[i].r1, emb), x, cx, skips[lv], cs, dims, nullptr, nullptr, nullptr,
+                    lv == 0 ? side_h1 : nullptr);
       r.ws->release(x);
       r.ws->release(skips[lv]);
       x = t; cx = p->ups[i].r1.cout;

@@ -55,6 +55,24 @@ int cd_op_cyl_conv(const float* x0, int c0, const float* x1, int c1, const float
   });
 }
 
+int cd_op_zslide_conv(const float* x, int cin, const float* w, const float* bias, float* y, float* ch_part, int* units, int batch,
+                      int cout, const int32_t dims[3], int chunks, void* scratch, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(x && w && y && ch_part && units && scratch && chunks >= 0, "bad argument");
+    CD_REQUIRE(cin % 32 == 0 && cout % 32 == 0, "channel counts must be multiples of 32");
+    hipStream_t s = (hipStream_t)stream;
+    launch_pack_weights_f16x2(w, scratch, cout, cin, 27, s);
+    const Dims3 d{dims[0], dims[1], dims[2]};
+    ConvGeom g{d, d, 3, 3, 3, 1, 1, 1};
+    ConvFusion fu;
+    int u = 0;
+    fu.act = 1; fu.ch_part = ch_part; fu.units = &u; fu.zs_chunks = chunks;
+    CD_REQUIRE(try_launch_conv_zslide(x, cin, nullptr, 0, scratch, bias, y, batch, cout, g, s, fu) && u > 0,
+               "this grid is not eligible for the z-slide kernel");
+    *units = u;
+  });
+}
+
 int cd_op_cyl_conv_transpose(const float* x, const float* w, const float* bias, float* y, int batch, int channels,
                              const int32_t dims_in[3], int kernel_z, int stride_z, const int32_t out_pad[3],
                              void* scratch, void* stream) {

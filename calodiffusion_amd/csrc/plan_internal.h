@@ -295,7 +295,7 @@ float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1
                         const float* bias, float* out, int cout, Dims3 dims, const float* coef_in, int* units,
                         const GnDefer* defer_in = nullptr, float* coef_buf = nullptr, const ConvFusion::GnOut* gn_out = nullptr);
 float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
-                 float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr);
+                 float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr, float* h1_side = nullptr);
 float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpart = nullptr, int xunits = 0);
 void bias_grad(Run& r, const float* dy, int C, int64_t vox, float* db);
 void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, const float* w_raw, const float* dy, float* dx,

@@ -122,6 +122,8 @@ _SIGNATURES = {
     "cd_op_to_ncdhw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P]),
     "cd_op_cyl_conv": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P]),
+    "cd_op_zslide_conv": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                    _P, _P]),
     "cd_op_cyl_conv_transpose": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                            C.POINTER(C.c_int32), _P, _P]),
     "cd_op_init_conv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, _P]),
@@ -315,7 +317,7 @@ class UnetEngine:
     # under one setting is not valid under another, so they are part of the cache key.  (The arithmetic mode is not: the
     # library sizes for the largest of its three modes.)
     _WS_SWITCHES = ("CD_NO_DEEP_LEVEL", "CD_NO_PW_CLOSE", "CD_NO_FUSED_ATTN", "CD_NO_GNDEFER", "CD_ATTN_COMBINE_LAUNCH", "CD_PW_F32",
-                    "CD_NO_ATTN_MOMENTS", "CD_ATTN_MOM_MIN")
+                    "CD_NO_ATTN_MOMENTS", "CD_ATTN_MOM_MIN", "CD_NO_DEEP_SIDE_CONV")
 
     def _ws_key(self, batch: int):
         return (int(batch),) + tuple(os.environ.get(k) for k in self._WS_SWITCHES)
@@ -885,6 +887,22 @@ class Ops:
         _check(self.lib.cd_op_cyl_conv(x_cl.data_ptr(), c0, _ptr(x1_cl), c1, w.data_ptr(), _ptr(bias), y.data_ptr(), B, cout,
                                        _i32x3((D, H, W)), _i32x3(k), _i32x3(stride), sc.data_ptr(), _stream()))
         return y
+
+    def zslide_conv_chunked(self, x_cl, w, bias, chunks=0):
+        """3x3x3 conv through the z-slide kernel with every sample dealt in `chunks` chunks (0: the launcher's choice).  Returns
+        (y, stats): stats [B][cout][2] = the kernel's channel partials {sum, sum of squares} of y, added up in fp64."""
+        x_cl, w = _dev32(x_cl, "x"), _dev32(w, "w")
+        B, D, H, W, cin = x_cl.shape
+        cout = w.shape[0]
+        y = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x_cl.device)
+        cap = (D * H * W + 31) // 32
+        part = torch.zeros((B, cap, cout, 2), dtype=torch.float32, device=x_cl.device)
+        units = C.c_int()
+        sc = self.scratch(B, max(cin, cout), D * H * W)
+        _check(self.lib.cd_op_zslide_conv(x_cl.data_ptr(), cin, w.data_ptr(), _ptr(bias), y.data_ptr(), part.data_ptr(), C.byref(units),
+                                          B, cout, _i32x3((D, H, W)), int(chunks), sc.data_ptr(), _stream()))
+        u = units.value  # (the partials are packed [B][units][cout][2] at the front of the buffer)
+        return y, part.view(-1)[:B * u * cout * 2].view(B, u, cout, 2).double().sum(1)
 
     def cyl_conv_transpose(self, x_cl, w, bias, kernel_z, stride_z, out_pad):
         x_cl, w = _dev32(x_cl, "x"), _dev32(w, "w")

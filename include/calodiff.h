@@ -419,6 +419,11 @@ int cd_op_to_ncdhw(const float* ndhwc, float* ncdhw, int batch, int channels, in
 int cd_op_cyl_conv(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias, float* y,
                    int batch, int cout, const int32_t dims_in[3], const int32_t kernel[3], const int32_t stride[3],
                    void* scratch, void* stream);
+/* The same 3x3x3 stride-1 conv, single source, through the z-slide f16x2 kernel only (an error where the grid is not eligible), every
+ * sample dealt in `chunks` chunks of voxels (0: the launcher's own count).  Also returns the kernel's channel statistics of y as
+ * partial sums: ch_part [batch][*units][cout][2] = {sum, sum of squares}, packed; capacity batch * ceil(voxels / 32) * cout * 2 floats. */
+int cd_op_zslide_conv(const float* x, int cin, const float* w, const float* bias, float* y, float* ch_part, int* units, int batch,
+                      int cout, const int32_t dims[3], int chunks, void* scratch, void* stream);
 /* CylindricalConvTrans as built by Upsample (models.py:25-62, 335-348). w: (Cin,Cout,kD,4,4); padding (1, circ, 1). */
 int cd_op_cyl_conv_transpose(const float* x, const float* w, const float* bias, float* y, int batch, int channels,
                              const int32_t dims_in[3], int kernel_z, int stride_z, const int32_t out_pad[3],
