@@ -210,6 +210,7 @@ struct PackJob {
 void launch_pack_jobs(const PackJob* d_jobs, int njobs, hipStream_t s);        // raw copy, f32 / init and bf16x3 images (kernels_conv.hip)
 void launch_pack_jobs_f16x2(const PackJob* d_jobs, int njobs, hipStream_t s);  // f16x2 images (kernels_conv_zs.hip)
 
+// forward conv on whichever kernel family fits it (kernels_conv.hip; the families and what they share: conv_internal.h)
 void launch_conv_mfma(const float* in0, int c0, const float* in1, int c1, const float* wpk, const float* bias, float* out,
                       int batch, int cout, const ConvGeom& g, hipStream_t s, const ConvFusion& fu = ConvFusion());
 // z-slide f16x2 kernel for the full-resolution 3x3x3 convs (kernels_conv_zs.hip); false = geometry not eligible
@@ -218,6 +219,7 @@ bool try_launch_conv_zslide(const float* in0, int c0, const float* in1, int c1, 
 // whole-sample-in-LDS f16x2 kernel for the deepest levels (kernels_conv_small.hip); false = geometry not eligible
 bool try_launch_conv_small(const float* in0, int c0, const float* in1, int c1, const void* wpk_f16x2, const float* bias, float* out,
                            int batch, int cout, const ConvGeom& g, hipStream_t s, const ConvFusion& fu);
+// kernels_conv_transpose.hip
 void launch_conv_transpose_mfma(const float* in, int cin, const float* wpk, const float* bias, float* out, int batch,
                                 int cout, Dims3 din, Dims3 dout, int kz, int sz, hipStream_t s,
                                 const void* wpk_f16x2 = nullptr, int* status = nullptr, const unsigned* in_absmax = nullptr);
@@ -252,7 +254,7 @@ struct PointwiseArgs {
   int* status = nullptr;
 };
 inline int pointwise_units(int64_t vox) { return (int)((vox + 127) / 128); }
-void launch_pointwise(const PointwiseArgs& a, hipStream_t s);
+void launch_pointwise(const PointwiseArgs& a, hipStream_t s);  // kernels_pointwise.hip
 
 struct InitConvArgs {
   const float* x = nullptr;       // (B, cx, D, H, W) planar
@@ -276,7 +278,7 @@ struct InitConvArgs {
   bool table_ready = false;       // coord_table already holds that part (launch_init_coord_table); else it is filled first
   int* status = nullptr;          // bit 0: a staged value exceeded the fp16 range (matrix-core path)
 };
-void launch_init_conv(const InitConvArgs& a, hipStream_t s);
+void launch_init_conv(const InitConvArgs& a, hipStream_t s);  // kernels_init_conv.hip
 // coordinate channels + bias of the init conv into a.coord_table (vox, cout): changes only with the weights / profiles
 void launch_init_coord_table(const InitConvArgs& a, hipStream_t s);
 

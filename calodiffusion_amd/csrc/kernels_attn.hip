@@ -15,6 +15,7 @@
 // per 16 channels instead of 16 f32 MFMAs at half the rate); the context and output products take their operands from
 // accumulator registers and stay on v_mfma_f32_32x32x2_f32.
 #include "cd_common.h"
+#include "conv_internal.h"
 #include "gn_defer.h"
 #include "split16.h"
 
@@ -22,8 +23,6 @@
 #include <cstdlib>
 
 namespace cd {
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 namespace {
 

@@ -8,12 +8,11 @@
 //   * GroupNorm(+SiLU) backward (statistics pass + elementwise pass);
 //   * small elementwise pieces (loss gradient, softmax backward of the linear attention, head).
 #include "cd_common.h"
+#include "conv_internal.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace cd {
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // ------------------------------------------------------------------------------------------------------------
 // Weight gradient.

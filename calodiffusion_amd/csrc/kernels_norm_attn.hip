@@ -2,13 +2,12 @@
 // Reference semantics: nn.GroupNorm(eps=1e-5, biased variance) as used by Block / PreNorm / LinearAttention.to_out
 // (calodiffusion/models/models.py:155,293,325) and LinearAttention.forward (models.py:301-318).
 #include "cd_common.h"
+#include "conv_internal.h"
 #include "gn_defer.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace cd {
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // ------------------------------------------------------------------------------------------------------------
 // GroupNorm, split so that every piece fuses into a neighbour:

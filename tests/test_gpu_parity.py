@@ -98,6 +98,40 @@ def test_halo_tiled_kernels_match_too(ops, monkeypatch):
         assert err < TOL_OP, (tag, err)
 
 
+def _halo_tiled_errors():
+    """(child process of the test below) 3x3x3 convs, one of them over a concatenated input, and a golden down-sampling conv."""
+    from calodiffusion_amd.engine import Ops
+    ops = Ops()
+    gen = torch.Generator().manual_seed(17)
+    errs = {"c32": _conv_case(ops, gen, 2, 32, 0, 32, (9, 16, 9)), "c32+32": _conv_case(ops, gen, 2, 32, 32, 64, (6, 4, 2))}
+    g = gold("primitives_conv")
+    y = back(ops, ops.cyl_conv(cl(ops, g["down_d2.x"]), t(g["down_d2.w"]).cuda(), t(g["down_d2.b"]).cuda(),
+                               stride=(2 if int(g["down_d2.cz"]) else 1, 2, 2)))
+    errs["down_d2"] = rel_l2(y, g["down_d2.y"])
+    return errs
+
+
+@pytest.mark.parametrize("mode", ["f16x2", "bf16x3", "f32"])
+def test_halo_tiled_kernels_in_every_precision(mode):
+    """With the flat-range, z-slide and whole-sample kernels switched off every conv runs on a halo-tiled kernel, in the arithmetic
+    CD_CONV_PRECISION asks for (f16x2 / bf16x3: conv_tiled_bf16x3_kernel's two arms, f32: conv_mfma_kernel), on the tiling the
+    ranking puts first.  The precision and the switches are latched per process: one child interpreter per mode."""
+    import json
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, CD_CONV_PRECISION=mode, CD_NO_FLAT="1", CD_NO_ZSLIDE="1", CD_NO_CONV_SMALL="1", CD_NO_AUTOTUNE="1")
+    code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r);"
+            "from test_gpu_parity import _halo_tiled_errors; print(json.dumps(_halo_tiled_errors()))" % (os.path.dirname(here), here))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    errs = json.loads(out.stdout.strip().splitlines()[-1])
+    print(mode, errs)
+    assert set(errs) == {"c32", "c32+32", "down_d2"}
+    for case, err in errs.items():
+        assert err < TOL_OP, (mode, case, err)
+
+
 def test_concat_conv_equals_conv_of_concat(ops):
     """The skip concat is never materialised: the conv reads two base pointers (models.py:741)."""
     from oracle import torch_oracle as O

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise the gfx950 ISA of one kernel: instruction mix and the order of MFMA / LDS / global / wait instructions.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o /tmp/k.s calodiffusion_amd/csrc/kernels_conv.hip
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o /tmp/k.s calodiffusion_amd/csrc/kernels_conv_flat.hip
     python tools/isa_summary.py /tmp/k.s _ZN2cd17conv3_flat_kernelILi2ELi1EEEvNS_12ConvFlatArgsE
 """
 import collections
