@@ -48,4 +48,14 @@ __device__ __forceinline__ float philox_normal(uint64_t g, uint64_t seed) {
   return lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
 }
 
+// stream element g as a 24-bit uniform in [0, 1) (the sparse geometry decode's draw, kernels_geom.hip)
+__device__ __forceinline__ float philox_uniform(uint64_t g, uint64_t seed) {
+  const uint64_t ctr = g >> 2;
+  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const int lane = (int)(g & 3);
+  const uint32_t w = lane == 0 ? c[0] : lane == 1 ? c[1] : lane == 2 ? c[2] : c[3];
+  return (float)(w >> 8) * (1.0f / 16777216.0f);
+}
+
 }  // namespace cd

@@ -102,16 +102,18 @@ class Diffusion(torch.nn.Module, ABC):
 
     def generate(self, data_loader, sample_steps: int, debug: bool = False, sample_offset: Optional[int] = 0,
                  sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False,
-                 reverse_norm: Optional[Callable] = None):
+                 reverse_norm: Optional[Callable] = None, geometry=None):
         """Sampling loop over a loader of (E, layers, data) batches (diffusion.py:118-197).
 
         The inverse pre-processing (``utils.ReverseNorm``, diffusion.py:171-195) runs on the device for the regular-grid
         configs (``postprocess.ReverseNorm``: Dataset-2 / Dataset-3 shower maps; needs the EMAX / EMIN / logE / MAXDEP / ECUT
         keys of the reference's configs).  ``reverse_norm`` = a callable (generated, energies, layers, config) overrides it
         (e.g. the reference's own function for the geometry-converted datasets); ``reverse_norm=False`` returns the
-        normalised-space showers.
+        normalised-space showers.  ``geometry`` = an ``hgcal.HGCalConverter``: an HGCal config with a [layer-]logit-norm map
+        ends in physical showers (batch, layers, cells) too, decoded on the device (``postprocess.ReverseNormHGCal``, with
+        ``sparse_decoding`` / ``sparse_per_batch``).
         """
-        self._physical_form(reverse_norm)  # raises NOW, not after minutes of sampling, if there is no inverse pre-processing
+        self._physical_form(reverse_norm, geometry)  # raises NOW, not after minutes of sampling, if there is no inverse pre-processing
         generated, energies, layers = [], [], []
         for E, layers_, d_batch in data_loader:
             E = E.to(device=self.device)
@@ -123,9 +125,9 @@ class Diffusion(torch.nn.Module, ABC):
                 layers.append(layers_.detach().cpu().numpy())
         generated, energies = np.concatenate(generated), np.concatenate(energies)
         layers = np.concatenate(layers) if layers else None
-        return self._to_physical(generated, energies, layers, reverse_norm, debug)
+        return self._to_physical(generated, energies, layers, reverse_norm, debug, geometry, sparse_decoding, sparse_per_batch)
 
-    def _physical_form(self, reverse_norm) -> str:
+    def _physical_form(self, reverse_norm, geometry=None) -> str:
         """Which inverse pre-processing generate() will apply: 'callable', 'device', or 'none' (reverse_norm=False).  Raises for
         configs the device form does not cover -- called at the top of generate() (and of LayerDiffusion.generate), before the
         sampling loop."""
@@ -134,10 +136,16 @@ class Diffusion(torch.nn.Module, ABC):
             return "callable"
         if reverse_norm is False:
             return "none"
-        if (reverse_norm is None and cfg.get("DATASET_NUM", 2) in (2, 3)
-                and cfg.get("SHOWERMAP") in ("layer-logit-norm", "logit-norm")
+        if (reverse_norm is None and cfg.get("SHOWERMAP") in ("layer-logit-norm", "logit-norm")
                 and all(k in cfg for k in ("EMAX", "EMIN", "logE", "MAXDEP", "ECUT"))):
-            return "device"
+            if cfg.get("DATASET_NUM", 2) in (2, 3):
+                return "device"
+            if self.hgcal and geometry is not None:
+                from .hgcal import HGCalConverter
+                if not isinstance(geometry, HGCalConverter):
+                    raise TypeError("generate(geometry=) takes an hgcal.HGCalConverter; pass any other decoder through "
+                                    "reverse_norm=<callable>")
+                return "device"
         # the reference always applies utils.ReverseNorm (diffusion.py:171-195): never hand back normalised-space showers
         # silently.  HGCal / Dataset-1 need geometry files outside this package: pass the reference's function.
         raise ValueError(
@@ -145,12 +153,20 @@ class Diffusion(torch.nn.Module, ABC):
             "[layer-]logit-norm SHOWERMAP and the EMAX/EMIN/logE/MAXDEP/ECUT keys); pass reverse_norm=<callable "
             "(generated, energies, layers, config)> or reverse_norm=False for normalised-space showers")
 
-    def _to_physical(self, generated, energies, layers, reverse_norm, debug=False):
+    def _to_physical(self, generated, energies, layers, reverse_norm, debug=False, geometry=None, sparse_decoding=False,
+                     sparse_per_batch=False):
         """Inverse pre-processing of generated showers (shared with LayerDiffusion.generate)."""
         cfg = self.config
-        device_form = self._physical_form(reverse_norm) == "device"
+        device_form = self._physical_form(reverse_norm, geometry) == "device"
         if callable(reverse_norm):
             generated, energies = reverse_norm(generated, energies, layers, cfg)
+        elif device_form and self.hgcal:
+            from .postprocess import ReverseNorm
+            generated, energies = ReverseNorm(generated, energies, shape=cfg["SHAPE_FINAL"], config=cfg, emax=cfg["EMAX"],
+                                              emin=cfg["EMIN"], layerE=layers, logE=cfg["logE"], max_deposit=cfg["MAXDEP"],
+                                              showerMap=cfg["SHOWERMAP"], dataset_num=cfg["DATASET_NUM"], ecut=float(cfg["ECUT"]),
+                                              hgcal=True, embed=self.pre_embed, NN_embed=geometry,
+                                              sparse_decoding=sparse_decoding, sparse_per_batch=sparse_per_batch)
         elif device_form:
             from .postprocess import ReverseNorm
             generated, energies = ReverseNorm(generated, energies, shape=cfg["SHAPE_FINAL"], config=cfg, emax=cfg["EMAX"],

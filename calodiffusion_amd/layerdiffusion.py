@@ -169,9 +169,10 @@ class LayerDiffusion(CaloDiffusion):
         return out
 
     def generate(self, data_loader, sample_steps: int, debug: bool = False, sample_offset: Optional[int] = 0,
-                 sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False, reverse_norm=None):
-        """layerdiffusion.py:171-235: no layer energies are taken from the loader, the layer model generates them."""
-        self._physical_form(reverse_norm)  # raise before sampling if this config has no inverse pre-processing here
+                 sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False, reverse_norm=None, geometry=None):
+        """layerdiffusion.py:171-235: no layer energies are taken from the loader, the layer model generates them.  ``geometry``:
+        as for ``Diffusion.generate``."""
+        self._physical_form(reverse_norm, geometry)  # raise before sampling if this config has no inverse pre-processing here
         generated, energies, layers = [], [], []
         for E, _, _d in data_loader:
             E = E.to(device=self.device)
@@ -181,4 +182,4 @@ class LayerDiffusion(CaloDiffusion):
             layers.append(out["layers"].detach().cpu().numpy())
             energies.append(E.detach().cpu().numpy())
         generated, energies, layers = np.concatenate(generated), np.concatenate(energies), np.concatenate(layers)
-        return self._to_physical(generated, energies, layers, reverse_norm)
+        return self._to_physical(generated, energies, layers, reverse_norm, False, geometry, sparse_decoding, sparse_per_batch)

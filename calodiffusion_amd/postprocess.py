@@ -2,9 +2,10 @@
 446-573) for the regular-grid datasets, on the device (``cd_reverse_norm``).
 
 Supported: ``dataset_num`` 2 / 3, ``showerMap`` 'layer-logit-norm' / 'logit-norm' (the shipped Dataset-2 / Dataset-3 configs), and
-the HGCal variant ``ReverseNormHGCal`` (utils/HGCal_utils.py:167-292) as two device stages around its geometry decode: the decoder
-(``NN_embed`` with the reference's ``dec_batches``) is the caller's -- the geometry file it needs does not ship with the reference.
-Quantile maps and the Dataset-1 geometry conversion are not provided."""
+the HGCal variant ``ReverseNormHGCal`` (utils/HGCal_utils.py:167-292) as two device stages around its geometry decode.  With an
+``hgcal.HGCalConverter`` as ``NN_embed`` the decode runs on the device between them (``cd_geom_apply`` / ``cd_geom_decode_sparse``)
+and only the final showers are copied to the host; any other ``NN_embed`` is called through the reference's ``dec_batches`` on the
+host.  Quantile maps and the Dataset-1 geometry conversion are not provided."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +28,8 @@ DATASET_PARAMS.update({
     120: dict(logit_mean=-18.1561, logit_std=1.56255, totalE_mean=0.5389, totalE_std=0.30325, layers_mean=-6.7899, layers_std=5.64943),
     121: dict(logit_mean=-17.8664, logit_std=2.34207, totalE_mean=1.0270, totalE_std=0.09394, layers_mean=-11.6495, layers_std=7.31088),
 })
+# (embed_mean, embed_std) of the sets that have them (consts.py:136-137, 150-151, 163-164, 177-178): HGCalConverter's `norm`
+HGCAL_EMBED_PARAMS = {101: (0.0835, 3.1083), 111: (0.0, 1.0), 120: (0.0, 1.0), 121: (0.0, 1.0)}
 
 
 def ReverseNorm(voxels, e, hgcal=False, **kwargs):
@@ -53,9 +56,10 @@ def ReverseNormHGCal(voxels, e, shape=None, emax=9999.0, emin=0.0001, max_deposi
                      sparse_decoding=False, sparse_per_batch=False):
     """``utils.ReverseNormHGCal`` (calodiffusion/utils/HGCal_utils.py:167-292), same arguments and return values.  The incident
     energy is LINEAR in e here (``emin + (emax - emin) e``, :195-199, whatever ``logE`` says), reverse_logit uses alpha 1e-8, the
-    energy cut is disabled in the reference (``if ecut > 0 and False``).  ``embed``: the caller's ``NN_embed.dec_batches`` decodes
-    between the two device stages (the reference builds an ``HGCalConverter`` from ``binning_file`` when none is given: that needs
-    its geometry pickle, so here the converter must be passed in)."""
+    energy cut is disabled in the reference (``if ecut > 0 and False``).  ``embed``: ``NN_embed`` decodes between the two device
+    stages -- an ``hgcal.HGCalConverter`` on the device (``sparse_decoding`` / ``sparse_per_batch`` included), any other object
+    through its ``dec_batches`` on the host (the reference builds an ``HGCalConverter`` from ``binning_file`` when none is given:
+    that needs its geometry pickle, so here the converter must be passed in)."""
     if dataset_num not in DATASET_PARAMS:
         raise NotImplementedError("ReverseNormHGCal: no constants for dataset_num %r" % (dataset_num,))
     if "logit" not in showerMap or "norm" not in showerMap or "quantile" in showerMap:
@@ -71,8 +75,12 @@ def ReverseNormHGCal(voxels, e, shape=None, emax=9999.0, emin=0.0001, max_deposi
         if NN_embed is None:
             raise NotImplementedError("ReverseNormHGCal(embed=True) needs the geometry converter (NN_embed): building one takes the "
                                       "geometry file of the HGCalShowers package, which does not ship with the reference")
-        dec = NN_embed.dec_batches(data.cpu().numpy(), sparse_decoding=sparse_decoding, sparse_per_batch=sparse_per_batch)
-        data = torch.as_tensor(np.asarray(dec, dtype=np.float32)).cuda().contiguous()
+        from .hgcal import HGCalConverter
+        if isinstance(NN_embed, HGCalConverter):
+            data = NN_embed.dec(data, sparse_decoding=sparse_decoding, sparse_per_batch=sparse_per_batch)
+        else:
+            dec = NN_embed.dec_batches(data.cpu().numpy(), sparse_decoding=sparse_decoding, sparse_per_batch=sparse_per_batch)
+            data = torch.as_tensor(np.asarray(dec, dtype=np.float32)).cuda().contiguous()
     layer_mode = "layer" in showerMap
     le = None
     if layer_mode:

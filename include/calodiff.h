@@ -307,6 +307,41 @@ int cd_preprocess(const float* showers, const float* energy, float* out, float* 
                   const int32_t dims[3], const float consts[6], float max_deposit, float emin, float emax, int logE,
                   float shower_scale, void* stream);
 
+/* ---- HGCal geometry maps -------------------------------------------------------------------------------------------
+ * The linear maps between HGCal's irregular cells and the regular (layer, alpha, r) grid: Embeder / Decoder / HGCalConverter of
+ * calodiffusion/utils/HGCal_utils.py:295-407, 636-680.  init_map (:412-486) puts one or two non-zeros in a column of a layer's
+ * (alpha*r, cells) matrix and its thresholded pseudo-inverse is as sparse, so a map is kept packed: per-layer CSR of every entry
+ * != 0 in ascending column order (dropping exact zeros only, the product equals the dense einsum up to summation order), and
+ * optionally the column-major view of the entries > 1e-6, which is the `mask` of generate_sparse_mat (:355-407). */
+typedef struct CdGeomMap CdGeomMap;
+/* Packs a dense DEVICE tensor (layers, rows, cols) -- Embeder.mat (L, E, N) or Decoder.mat (L, N, E), `mat * mask` for a
+ * trainable one (:316, :341).  want_columns != 0 also builds the column view cd_geom_decode_sparse needs.  The handle owns its
+ * index and value arrays (device memory allocated here); the call synchronises `stream`.  layers * rows * cols < 2^31. */
+int cd_geom_create(const float* dense_dev, int layers, int rows, int cols, int want_columns, CdGeomMap** out, void* stream);
+int cd_geom_destroy(CdGeomMap* map);
+/* Embeder.forward (:315-320) and Decoder.forward without sparse decoding (:340-349), with the converter's `norm` (enc :636-640,
+ * dec :659-663):  y[r, l, i] = sum_j M[l, i, j] x[r, l, j]  for r < batch_rows (batch x channels);  x (batch_rows, L, cols),
+ * y (batch_rows, L, rows).  scale = embed_std, shift = embed_mean: with affine_first the input is x * scale + shift (dec),
+ * otherwise the output is (y - shift) / scale (enc), each operation rounded on its own as torch does; scale 1, shift 0 is the
+ * plain product.  A row's sum runs over its entries in ascending j with fp32 FMAs: repeated calls are bitwise equal, and a
+ * result row does not depend on batch_rows.  Nothing is allocated and the stream is not synchronised. */
+int cd_geom_apply(const CdGeomMap* map, const float* x, float* y, int batch_rows, float scale, float shift, int affine_first,
+                  void* stream);
+/* Decoder.forward(sparse_decoding=True) (:340-349 with generate_sparse_mat, :355-407) without the (B, L, N, E) matrix: every
+ * (shower, layer, column e) keeps the entries n with u + m > 1 and the one of largest u + m (the first of equal ones, as
+ * torch.argmax), m the entries > 1e-6 of column e and u a uniform in [0, 1) per (b, l, n, e), and the column's input is shared
+ * equally among them:  y[b, c, l, n] = sum over selected (n, e), in ascending e, of x[b, c, l, e] / count[b, l, e].
+ * x (batch, channels, L, cols), y (batch, channels, L, rows); one selection serves every channel of a shower; per_batch != 0:
+ * one selection (that of b = 0) serves every shower (sparse_per_batch).  u = rand[b, l, n, e] when rand is given, a dense DEVICE
+ * tensor (batch or 1 if per_batch, L, rows, cols) (torch.rand_like's draw, :373); otherwise the 24-bit uniform of the Philox
+ * stream (as cd_randn's) at element offset + ((b L + l) rows + n) cols + e, so a batch shard passes offset + first_shower * L *
+ * rows * cols and draws its slice of the global tensor.  Two launches, no atomics: the first writes (argmax n, count) per
+ * (b, l, e) into count_ws, caller memory of cd_geom_sparse_workspace_bytes; the second gathers per output row.  The map needs
+ * its column view (want_columns).  Nothing is allocated and the stream is not synchronised. */
+int cd_geom_sparse_workspace_bytes(const CdGeomMap* map, int batch, size_t* bytes);
+int cd_geom_decode_sparse(const CdGeomMap* map, const float* x, float* y, int batch, int channels, int per_batch,
+                          const float* rand /* nullable */, uint64_t seed, uint64_t offset, void* count_ws, void* stream);
+
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
  * (calodiffusion/models/layerdiffusion.py:35-38, 114-132) samples the (B, D+1) {total, per-layer} energies with.

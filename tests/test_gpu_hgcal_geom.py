@@ -1,0 +1,230 @@
+"""GPU (MI355X): the HGCal geometry maps on the device -- cd_geom_create / cd_geom_apply / cd_geom_decode_sparse through
+calodiffusion_amd/hgcal.py -- against the reference's Embeder / Decoder / generate_sparse_mat outputs on a synthetic geometry
+(fixture: tools/gen_golden_hgcal_geom.py), float64 restatements at the derived bound (hgcal_geom_cases.bound), and up through
+postprocess.ReverseNormHGCal and generate(geometry=)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import gold, rel_l2
+from helpers import t
+from hgcal_geom_cases import apply64, bound, sparse64, sparse_bound, sparse_matrix, worst_ratio
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -23
+
+
+def _fixture():
+    from calodiffusion_amd import hgcal
+    g = gold("hgcal_geom")
+    bins = [int(b) for b in g["g.bins"]]
+    conv = hgcal.HGCalConverter.from_matrices(bins, g["g.enc_mat"], g["g.dec_mat"], g["g.enc_mask"], g["g.dec_mask"])
+    return g, conv, bins
+
+
+def _one_or_two_per_cell(rng, L, E, N):
+    """enc (L, E, N): every cell in one bin, or split 0.5 / 0.5 over two; dec (L, N, E): its transpose with every column
+    normalised to sum 1 (what the pseudo-inverse is where the cells of a bin do not overlap)."""
+    enc = np.zeros((L, E, N), dtype=np.float32)
+    ll, nn = np.meshgrid(np.arange(L), np.arange(N), indexing="ij")
+    e1 = rng.integers(0, E, size=(L, N))
+    two = rng.random((L, N)) < 0.3
+    e2 = (e1 + 1 + rng.integers(0, E - 1, size=(L, N))) % E
+    enc[ll, e1, nn] = np.where(two, 0.5, 1.0)
+    enc[ll[two], e2[two], nn[two]] = 0.5
+    dec = np.ascontiguousarray(enc.transpose(0, 2, 1))
+    dec = (dec / np.maximum(dec.sum(1, keepdims=True), 1e-30)).astype(np.float32)
+    return enc, dec
+
+
+def test_encode_and_decode_match_the_reference():
+    """enc and dec, with and without the converter's norm, on the fixture shapes (N = 37, E = 20, B = 3) against the reference's
+    Embeder / Decoder outputs, per element within 2 nnz_row 2^-23 sum_j |M_ij x_j|."""
+    g, conv, (L, A, R) = _fixture()
+    x, z = t(g["x"]).cuda(), t(g["z"]).cuda()
+    zf = g["z"].reshape(g["z"].shape[:3] + (A * R,))
+    worst = {}
+    for norm in (False, True):
+        conv.norm = norm
+        conv.embed_mean, conv.embed_std = (float(v) for v in g["norm"]) if norm else (0.0, 1.0)
+        enc, dec = conv.enc(x), conv.dec(z)
+        assert enc.is_cuda and dec.is_cuda and enc.shape == g["enc"].shape and dec.shape == g["dec"].shape
+        sfx = "_norm" if norm else ""
+        worst["enc" + sfx] = worst_ratio(enc.cpu().numpy().reshape(g["x"].shape[:3] + (-1,)),
+                                         g["enc" + sfx].reshape(g["x"].shape[:3] + (-1,)), bound(g["g.enc_mat"], g["x"]))
+        worst["dec" + sfx] = worst_ratio(dec.cpu().numpy(), g["dec" + sfx], bound(g["g.dec_mat"], zf))
+    print("device vs reference, worst |err| / bound:", {k: round(v, 3) for k, v in worst.items()})
+    assert max(worst.values()) <= 1.0
+    # the numpy entry points of the reference, in batches that do not divide the 3 showers
+    assert np.array_equal(conv.enc_batches(g["x"], batch_size=2), enc.cpu().numpy())
+    assert np.array_equal(conv.dec_batches(g["z"], batch_size=2), dec.cpu().numpy())
+
+
+def test_repeatable_and_channels_are_independent():
+    """The same call twice is bitwise equal; c = 2 equals two c = 1 calls, bitwise (plain and sampled decode, encode)."""
+    g, conv, (L, A, R) = _fixture()
+    gen = torch.Generator().manual_seed(5)
+    x2 = torch.rand((3, 2, L, g["x"].shape[-1]), generator=gen).cuda()
+    z2 = (torch.rand((3, 2, L, A, R), generator=gen) - 0.2).cuda()
+    runs = {"enc": lambda v: conv.enc(v), "dec": lambda v: conv.dec(v),
+            "sparse": lambda v: conv.dec(v, sparse_decoding=True, seed=9, offset=77),
+            "sparse_pb": lambda v: conv.dec(v, sparse_decoding=True, sparse_per_batch=True, seed=9, offset=77)}
+    for name, f in runs.items():
+        v = x2 if name == "enc" else z2
+        a, b = f(v), f(v)
+        assert torch.equal(a, b), name
+        assert torch.equal(a, torch.cat([f(v[:, :1].contiguous()), f(v[:, 1:].contiguous())], dim=1)), name
+
+
+@pytest.mark.parametrize("tag,per_batch", [("sparse", False), ("sparse_pb", True)])
+def test_sparse_decode_with_the_recorded_uniforms(tag, per_batch):
+    """Decoder.forward(sparse_decoding=True) on the uniforms the reference drew: its support exactly (the fixture's seed keeps
+    every u + m more than 1e-6 from 1 and has no equal maxima), its values at the derived bound."""
+    g, conv, (L, A, R) = _fixture()
+    z = g["z"]
+    got = conv.decoder(t(z).cuda(), sparse_decoding=True, sparse_per_batch=per_batch, rand=t(g[f"{tag}.rand"]).cuda()).cpu().numpy()
+    want = g[f"{tag}.out"]
+    assert got.shape == want.shape
+    sm = sparse_matrix(g["g.dec_mat"], g[f"{tag}.rand"])
+    ratio = worst_ratio(got, want, sparse_bound(g["g.dec_mat"], sm, z.reshape(z.shape[:3] + (A * R,))))
+    print(f"[{tag}] device vs reference: worst |err| / bound {ratio:.3f}; non-zero outputs {int((want != 0).sum())} of {want.size}")
+    assert np.array_equal(got != 0, want != 0)
+    assert ratio <= 1.0
+
+
+def test_sparse_decode_with_philox():
+    g, conv, (L, A, R) = _fixture()
+    dec_mat = g["g.dec_mat"]
+    N, E, B = dec_mat.shape[1], A * R, 3
+    kept = (dec_mat > 1e-6).sum(1)  # (L, E) kept entries per column
+    gen = torch.Generator().manual_seed(11)
+    val = torch.rand((B, L, E), generator=gen) + 0.1
+    # column e alone in channel e: the one selection serves every channel, so channel e's output is column e's share-out
+    z = (val[:, None] * torch.eye(E)[None, :, None, :]).reshape(B, E, L, A, R).cuda()
+    out = conv.decoder(z, sparse_decoding=True, seed=21, offset=0).cpu().numpy().astype(np.float64)  # (B, E, L, N)
+    sums = out.sum(-1).transpose(0, 2, 1)                                                              # (B, L, E)
+    want = np.where(kept[None] > 0, val.numpy().astype(np.float64), 0.0)
+    assert np.all(np.abs(sums - want) <= kept[None] * U * np.abs(want)), float(np.abs(sums - want).max())
+    assert np.all(sums[:, kept == 0] == 0)
+    # every output goes to a kept entry of its column, and a column with several kept entries is really sampled
+    sup = out != 0                                                                                      # (B, E, L, N)
+    assert not np.any(sup & ~(dec_mat > 1e-6).transpose(2, 0, 1)[None])
+    n_sel = sup.sum(-1).transpose(0, 2, 1)
+    assert np.all(n_sel[:, kept > 0] >= 1) and np.any(n_sel < kept[None])
+
+    zp = (torch.rand((B, 1, L, A, R), generator=gen) + 0.1).cuda()  # positive: the support of the output is the selection
+    a = conv.decoder(zp, sparse_decoding=True, seed=21, offset=0)
+    b = conv.decoder(zp, sparse_decoding=True, seed=22, offset=0)
+    assert not torch.equal(a != 0, b != 0)
+    # batch shards are slices of one global stream
+    per = L * N * E
+    lo = conv.decoder(zp[:2].contiguous(), sparse_decoding=True, seed=21, offset=0)
+    hi = conv.decoder(zp[2:].contiguous(), sparse_decoding=True, seed=21, offset=2 * per)
+    assert torch.equal(torch.cat([lo, hi]), a)
+    # one selection for the whole batch: that of the first shower of the per-shower call at the same stream position
+    pb = conv.decoder(zp, sparse_decoding=True, sparse_per_batch=True, seed=21, offset=0)
+    assert all(torch.equal(pb[i] != 0, pb[0] != 0) for i in range(B)) and torch.equal(pb[0], a[0])
+    # without seed / offset the decoder walks its own stream
+    conv.decoder.noise_offset = 0
+    c, d = conv.decoder(zp, sparse_decoding=True), conv.decoder(zp, sparse_decoding=True)
+    assert conv.decoder.noise_offset == 2 * B * per and not torch.equal(c != 0, d != 0)
+    assert torch.equal(c, conv.decoder(zp, sparse_decoding=True, seed=conv.decoder.noise_seed, offset=0))
+
+
+def test_hgcal_layer_shape():
+    """HGCal's own sizes (28 layers, 12 x 21 bins, 3000 cells, B = 2): rows beyond one wave, many workgroups, N not a multiple
+    of 64; dec and enc against a float64 einsum of the same fp32 arrays at the derived bound."""
+    from calodiffusion_amd import hgcal
+    L, A, R, N, B = 28, 12, 21, 3000, 2
+    rng = np.random.default_rng(7)
+    enc_mat, dec_mat = _one_or_two_per_cell(rng, L, A * R, N)
+    conv = hgcal.HGCalConverter.from_matrices([L, A, R], enc_mat, dec_mat)
+    x = (rng.random((B, 1, L, N)) * (rng.random((B, 1, L, N)) > 0.5)).astype(np.float32)
+    z = (rng.random((B, 1, L, A * R)) * 2.0 - 0.5).astype(np.float32)
+    enc = conv.enc(t(x).cuda()).cpu().numpy().reshape(B, 1, L, A * R)
+    dec = conv.dec(t(z.reshape(B, 1, L, A, R)).cuda()).cpu().numpy()
+    r_enc = worst_ratio(enc, apply64(enc_mat, x), bound(enc_mat, x))
+    r_dec = worst_ratio(dec, apply64(dec_mat, z), bound(dec_mat, z))
+    print(f"HGCal shape: enc rows hold up to {int((enc_mat != 0).sum(-1).max())} entries, worst |err| / bound enc {r_enc:.3f} dec {r_dec:.3f}")
+    assert r_enc <= 1.0 and r_dec <= 1.0
+    # the sampled decode at this size conserves every (shower, layer) sum of a column-normalised map's input
+    zs = np.abs(z).reshape(B, 1, L, A, R)
+    sp = conv.dec(t(zs).cuda(), sparse_decoding=True, seed=3, offset=0).cpu().numpy().astype(np.float64)
+    has = (dec_mat > 1e-6).any(1)  # (L, E)
+    want = (zs.reshape(B, 1, L, A * R).astype(np.float64) * has[None, None]).sum(-1)
+    # an output is at most two shares x / count and their sum, each rounded once: 2^-23 of the shares' total per (shower, layer)
+    assert np.all(np.abs(sp.sum(-1) - want) <= 2 * U * want)
+
+
+def test_dense_map_and_a_real_affine():
+    """Correctness does not hang on sparsity: a dense (2, 9, 7) map of mixed signs, plain and with set 101's norm (mean 0.0835,
+    std 3.1083; the fixture's set 111 has the identity).  With the norm the bound grows by the affine's own roundings: the
+    decoder's input x std + mean is two fp32 operations, 2^-23 (|x| std + |mean|) per element, carried through |M|; the encoder's
+    (y - mean) / std divides the product's bound by std and adds the subtraction and the division, 2^-23 (|y| + |mean|) / std."""
+    from calodiffusion_amd import hgcal
+    rng = np.random.default_rng(13)
+    M = rng.standard_normal((2, 9, 7)).astype(np.float32)
+    x = rng.standard_normal((4, 1, 2, 7)).astype(np.float32)
+    enc_like = hgcal.Embeder(3, 3, t(M), None)
+    got = enc_like(t(x).cuda()).cpu().numpy().reshape(4, 1, 2, 9)
+    r0 = worst_ratio(got, apply64(M, x), bound(M, x))
+    mean, std = hgcal.HGCAL_EMBED_PARAMS[101]
+    y64 = apply64(M, x)
+    got = enc_like._embed(t(x).cuda(), std, mean).cpu().numpy().reshape(4, 1, 2, 9)
+    r1 = worst_ratio(got, (y64 - mean) / std, bound(M, x) / std + U * (np.abs(y64) + abs(mean)) / std)
+    dec_like = hgcal.Decoder(1, 7, t(M), None)
+    xa = x.astype(np.float64) * std + mean
+    got = dec_like._decode(t(x.reshape(4, 1, 2, 1, 7)).cuda(), std, mean, False, False).cpu().numpy()
+    r2 = worst_ratio(got, apply64(M, xa), bound(M, xa) + U * apply64(np.abs(M), np.abs(x) * std + abs(mean)))
+    print(f"dense map: worst |err| / bound plain {r0:.3f}, enc norm {r1:.3f}, dec norm {r2:.3f}")
+    assert max(r0, r1, r2) <= 1.0
+    # trainable: mat * mask is what gets packed
+    mask = t((rng.random((2, 9, 7)) > 0.5))
+    tr = hgcal.Embeder(3, 3, t(M), mask, trainable=True)(t(x).cuda()).cpu().numpy().reshape(4, 1, 2, 9)
+    Mm = M * mask.numpy()
+    assert worst_ratio(tr, apply64(Mm, x), bound(Mm, x)) <= 1.0
+
+
+def test_reverse_norm_hgcal_with_the_device_converter():
+    """postprocess.ReverseNormHGCal(embed=True, NN_embed=<device converter>) against the reference's ReverseNormHGCal around its
+    own Decoder, at the bounds of the existing HGCal reverse-norm test (1e-5 overall, 3e-5 per (shower, layer) row)."""
+    from calodiffusion_amd import postprocess
+    from test_oracle_golden import per_layer_worst
+    g, conv, _ = _fixture()
+    data, gen = postprocess.ReverseNorm(g["rn.vox"], g["rn.e"], hgcal=True, emax=1000., emin=1., max_deposit=2, logE=True,
+                                        layerE=g["rn.layerE"], showerMap="layer-logit-norm", dataset_num=111, embed=True, NN_embed=conv)
+    assert data.shape == g["rn.data"].shape and np.allclose(gen, g["rn.gen"], rtol=1e-6)
+    e_all, e_row = rel_l2(data, g["rn.data"]), per_layer_worst(data, g["rn.data"])
+    print(f"ReverseNormHGCal through the device converter: rel L2 {e_all:.2e}, worst (shower, layer) row {e_row:.2e}")
+    assert e_all < 1e-5 and e_row < 3e-5
+    sp, _ = postprocess.ReverseNormHGCal(g["rn.vox"], g["rn.e"], emax=1000., emin=1., max_deposit=2, layerE=g["rn.layerE"],
+                                         showerMap="layer-logit-norm", dataset_num=111, embed=True, NN_embed=conv,
+                                         sparse_decoding=True, sparse_per_batch=True)
+    assert sp.shape == data.shape and np.isfinite(sp).all() and (sp != 0).sum() < (data != 0).sum()
+
+
+def test_generate_ends_in_physical_showers():
+    """generate(loader, 2, geometry=conv) on the HGCal config (B = 2, two DDIM steps, a synthetic map of its (28, 12, 21) bins
+    onto 64 cells) equals ReverseNormHGCal applied by hand to sample() of the same seed."""
+    from calodiffusion_amd import hgcal, postprocess
+    from calodiffusion_amd.calodiffusion import CaloDiffusion
+    from calodiffusion_amd.configs import load_config
+    cfg = dict(load_config("hgcal"), SAMPLER="DDim", EMAX=1000., EMIN=1., logE=True, MAXDEP=2, ECUT=0.0)
+    torch.manual_seed(1234)
+    m = CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
+    enc_mat, dec_mat = _one_or_two_per_cell(np.random.default_rng(17), 28, 252, 64)
+    conv = hgcal.HGCalConverter.from_matrices(cfg["SHAPE_FINAL"], enc_mat, dec_mat)
+    gen = torch.Generator().manual_seed(3)
+    E, layers = torch.rand((2, 3), generator=gen), torch.randn((2, 29), generator=gen)
+    m.noise_offset = 0
+    phys, e = m.generate([(E, layers, None)], 2, geometry=conv)
+    m.noise_offset = 0
+    raw = m.sample(E.cuda(), layers.cuda(), num_steps=2)
+    want, want_e = postprocess.ReverseNormHGCal(raw, E.numpy(), emax=1000., emin=1., max_deposit=2, logE=True, layerE=layers.numpy(),
+                                                showerMap="layer-logit-norm", dataset_num=111, embed=True, NN_embed=conv)
+    assert phys.shape == (2, 28, 64) and e.shape == (2, 3) and np.isfinite(phys).all()
+    assert np.array_equal(phys, want) and np.array_equal(e, np.reshape(want_e, (2, -1)))
+    m.noise_offset = 0
+    sp, _ = m.generate([(E, layers, None)], 2, geometry=conv, sparse_decoding=True)
+    assert sp.shape == (2, 28, 64) and np.isfinite(sp).all() and not np.array_equal(sp, phys)
