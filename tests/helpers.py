@@ -38,6 +38,19 @@ def t(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
+def attn_block_weights(C, gen, qscale=1.0, kscale=1.0, bias=0.0):
+    """CPU state dict of one Residual(PreNorm(LinearAttention)) block at C channels, keyed as engine.Ops.linear_attention takes it:
+    to_qkv / sqrt(C) (q rows x qscale, k rows x kscale), to_out / sqrt(32) with `bias` added to its bias, norm parameters
+    1 + 0.1 randn / 0.1 randn.  The draws from `gen` come in a fixed order."""
+    wqkv = torch.randn((96, C, 1, 1, 1), generator=gen) / C ** 0.5
+    wqkv[:32] *= qscale
+    wqkv[32:64] *= kscale
+    return {"fn.norm.weight": 1 + 0.1 * torch.randn(C, generator=gen), "fn.norm.bias": 0.1 * torch.randn(C, generator=gen),
+            "fn.fn.to_qkv.conv.weight": wqkv, "fn.fn.to_out.0.conv.weight": torch.randn((C, 32, 1, 1, 1), generator=gen) / 32 ** 0.5,
+            "fn.fn.to_out.0.conv.bias": 0.1 * torch.randn(C, generator=gen) + bias,
+            "fn.fn.to_out.1.weight": 1 + 0.1 * torch.randn(C, generator=gen), "fn.fn.to_out.1.bias": 0.1 * torch.randn(C, generator=gen)}
+
+
 def seeded_layer_models(cfg_name="dataset2", seed=SEED):
     """(ResNet layer model, CondUnet) with the parameters the reference's LayerDiffusion gets for torch.manual_seed(seed):
     the layer model is constructed first (layerdiffusion.py:35-40)."""

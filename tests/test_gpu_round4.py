@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t
+from helpers import attn_block_weights, t
 
 pytestmark = pytest.mark.gpu
 
@@ -197,13 +197,7 @@ def test_attention_moment_form_equals_the_separate_closing_pass(shape, batch, mo
     C = 32
     x = (torch.randn((batch, D, H, W, C), generator=gen) * 1.5 + 0.3).cuda()
     for qscale, bias in ((1.0, 0.0), (12.0, 0.0), (1.0, 3.0)):
-        wqkv = torch.randn((96, C, 1, 1, 1), generator=gen) / C ** 0.5
-        wqkv[:32] *= qscale
-        sd = {"fn.norm.weight": 1 + 0.1 * torch.randn(C, generator=gen), "fn.norm.bias": 0.1 * torch.randn(C, generator=gen),
-              "fn.fn.to_qkv.conv.weight": wqkv, "fn.fn.to_out.0.conv.weight": torch.randn((C, 32, 1, 1, 1), generator=gen) / 32 ** 0.5,
-              "fn.fn.to_out.0.conv.bias": 0.1 * torch.randn(C, generator=gen) + bias,
-              "fn.fn.to_out.1.weight": 1 + 0.1 * torch.randn(C, generator=gen), "fn.fn.to_out.1.bias": 0.1 * torch.randn(C, generator=gen)}
-        sd = {k: v.cuda().contiguous() for k, v in sd.items()}
+        sd = {k: v.cuda().contiguous() for k, v in attn_block_weights(C, gen, qscale=qscale, bias=bias).items()}
         y_mom = ops.linear_attention(x, sd)
         monkeypatch.setenv("CD_NO_ATTN_MOMENTS", "1")
         y_sep = ops.linear_attention(x, sd)
