@@ -1,6 +1,7 @@
 // HGCal geometry maps (include/calodiff.h, "HGCal geometry maps"): a dense (layers, rows, cols) map packed into per-layer CSR (and,
 // for the sparse decode, the column-major view of its entries > 1e-6), the product with a batch of showers, and
-// generate_sparse_mat's sampled decode in two gather passes.  Kernels and their C ABI; nothing here touches a plan.
+// generate_sparse_mat's sampled decode in two gather passes, and the HGCal forward pre-processing, which applies the packed encoder
+// inside its own launch (cd_preprocess_hgcal).  Kernels and their C ABI; nothing here touches a plan.
 #include "philox.h"
 #include "plan_internal.h"
 
@@ -185,6 +186,160 @@ __global__ void __launch_bounds__(256) geom_sparse_gather_kernel(const int* __re
   }
 }
 
+// ---- HGCal forward pre-processing: cells -> training batch -----------------------------------------------------------
+// preprocess_hgcal_shower and the loader around it (calodiffusion/utils/HGCal_utils.py:20-86, 125-162), one workgroup per shower
+// so that a row has the same bits in any batch or shard.  FUSED: the shower arrives as raw cells; a layer's cell row is staged
+// in LDS (coalesced reads, the next layer's in flight in registers meanwhile), multiplied by shower_scale, and a thread per grid
+// row forms the CSR row sum exactly as geom_apply_kernel does (ascending columns, the same fmaf chain, the same (y - mean) / std);
+// the grid never leaves LDS.  Otherwise the shower is already on the grid and is kept in LDS when it fits (`cached`), re-read
+// when it does not.  From there, as the reference forms the values:
+//   q = grid / (max_deposit e)                       float32
+//   'layer' maps (the reference's arrays are masked arrays there, whose arithmetic with python scalars is float64):
+//     layer sums and the total                       float32 in the reference; here summed in fp64 in a fixed order (a wave per
+//                                                    layer, lane-strided, xor butterfly; the total over the layers in layer
+//                                                    order) and rounded to float32 once
+//     layers / total                                 float32 quotient; from here on float64: logit, both normalisations, and the
+//                                                    logit and normalisation of every voxel, rounded to float32 at the end
+//   'logit-norm'                                     everything float32
+// logit is np.ma.log(o / (1 - o)).filled(0): 0 wherever the argument is not positive or the logarithm not finite (and where
+// layers / total is not finite: a total of 0), BEFORE the normalisation.
+namespace {
+constexpr int kHgThreads = 512;
+constexpr int kHgStageRegs = 4;                          // staged cells of a layer per thread
+constexpr int kHgMaxCells = kHgThreads * kHgStageRegs;   // fused form: cells per layer (8 KB of staging)
+constexpr size_t kHgGridBytes = 48 * 1024;               // grid of one shower in LDS up to this size
+constexpr int kHgFusedMaxLayers = 512;                   // fused form: 4 KB of layer sums; 60 KB of LDS in all
+constexpr int kHgMaxLayers = 4096;
+constexpr int kHgMaxGenCols = 8;
+
+struct PreHgcalArgs {
+  const int* row_ptr;  // the packed encoder (fused form only)
+  const int* col_idx;
+  const float* val;
+  const float* showers;
+  int64_t row_stride;
+  const float* gen_info;
+  float* out;
+  float* layerE;
+  float* e_out;
+  int32_t* status;
+  int layers, cells, grid, gen_cols, layer_mode, embed_affine;
+  double logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std;
+  float embed_mean, embed_std, max_deposit, scale;
+  double emin[kHgMaxGenCols], emax[kHgMaxGenCols];
+};
+
+__device__ __forceinline__ double hg_logit64(double x) {
+#pragma clang fp contract(off)
+  const double o = 1e-8 + (1.0 - 2.0 * 1e-8) * x;
+  const double r = o / (1.0 - o);
+  const double lg = log(r);
+  return (r > 0.0 && isfinite(lg)) ? lg : 0.0;
+}
+__device__ __forceinline__ float hg_logit32(float x) {
+#pragma clang fp contract(off)
+  const float o = 1e-8f + x;  // numpy rounds 1 - 2e-8 to the array's float32: 1
+  const float r = o / (1.f - o);
+  const float lg = logf(r);
+  return (r > 0.f && isfinite(lg)) ? lg : 0.f;
+}
+}  // namespace
+
+template <bool FUSED>
+__global__ void __launch_bounds__(kHgThreads) preprocess_hgcal_kernel(PreHgcalArgs a, int cached) {
+  extern __shared__ double hg_smem[];  // layer sums (padded to 16 bytes), q of the shower when cached, a cell row when FUSED
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int L = a.layers, E = a.grid, NV = L * E;
+  const float e = a.gen_info[(size_t)b * a.gen_cols];
+  if (!(e > 0.f) || isinf(e)) {  // uniform over the workgroup
+    if (tid == 0) atomicMax(a.status, b + 1);
+    return;
+  }
+  // np.array(emin) is float64: a double computation rounded once (HGCal_utils.py:131-132, 158)
+  if (tid < a.gen_cols)
+    a.e_out[(size_t)b * a.gen_cols + tid] =
+        (float)(((double)a.gen_info[(size_t)b * a.gen_cols + tid] - a.emin[tid]) / (a.emax[tid] - a.emin[tid]));
+  double* lsum = hg_smem;
+  float* q_lds = (float*)(hg_smem + ((L + 1) & ~1));
+  const float denom = __fmul_rn(a.max_deposit, e);
+  const float* in = a.showers + (size_t)b * L * a.row_stride;
+  float* out = a.out + (size_t)b * NV;
+
+  if (FUSED) {
+    float* stage = q_lds + NV;
+    float r[kHgStageRegs];
+#pragma unroll
+    for (int k = 0; k < kHgStageRegs; ++k) {
+      const int j = tid + k * kHgThreads;
+      r[k] = j < a.cells ? in[j] : 0.f;
+    }
+    for (int l = 0; l < L; ++l) {
+#pragma unroll
+      for (int k = 0; k < kHgStageRegs; ++k) {
+        const int j = tid + k * kHgThreads;
+        if (j < a.cells) stage[j] = __fmul_rn(r[k], a.scale);
+      }
+      __syncthreads();
+      if (l + 1 < L) {
+        const float* nx = in + (size_t)(l + 1) * a.row_stride;
+#pragma unroll
+        for (int k = 0; k < kHgStageRegs; ++k) {
+          const int j = tid + k * kHgThreads;
+          r[k] = j < a.cells ? nx[j] : 0.f;
+        }
+      }
+      for (int i = tid; i < E; i += kHgThreads) {
+        const int lo = a.row_ptr[l * E + i], hi = a.row_ptr[l * E + i + 1];
+        float acc = 0.f;
+        for (int p = lo; p < hi; ++p) acc = fmaf(a.val[p], stage[a.col_idx[p]], acc);
+        if (a.embed_affine) acc = __fdiv_rn(__fsub_rn(acc, a.embed_mean), a.embed_std);
+        q_lds[l * E + i] = __fdiv_rn(acc, denom);
+      }
+      __syncthreads();  // the row is consumed before the next one is staged; after the last, q is complete
+    }
+  }
+
+  if (a.layer_mode) {
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int z = wave; z < L; z += kHgThreads / 64) {
+      double acc = 0.0;
+      for (int i = lane; i < E; i += 64) {
+        float q;
+        if (FUSED) {
+          q = q_lds[z * E + i];
+        } else {
+          q = __fdiv_rn(in[z * E + i], denom);
+          if (cached) q_lds[z * E + i] = q;
+        }
+        acc += (double)q;
+      }
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      if (lane == 0) lsum[z] = acc;
+    }
+    __syncthreads();
+    double total = 0.0;
+    for (int z = 0; z < L; ++z) total += lsum[z];  // every thread, layer order
+    const float total32 = (float)total;
+    float* le = a.layerE + (size_t)b * (L + 1);
+    if (tid == 0) le[0] = (float)(((double)total32 - a.totalE_mean) / a.totalE_std);
+    for (int z = tid; z < L; z += kHgThreads) {
+      const float share = __fdiv_rn((float)lsum[z], total32);  // np.ma.divide masks it where it is not finite (total == 0)
+      const double lg = isfinite(share) ? hg_logit64((double)share) : 0.0;
+      le[1 + z] = (float)((lg - a.layers_mean) / a.layers_std);
+    }
+    for (int i = tid; i < NV; i += kHgThreads) {
+      const float q = (FUSED || cached) ? q_lds[i] : __fdiv_rn(in[i], denom);
+      out[i] = (float)((hg_logit64((double)q) - a.logit_mean) / a.logit_std);
+    }
+  } else {
+    const float mean = (float)a.logit_mean, std = (float)a.logit_std;
+    for (int i = tid; i < NV; i += kHgThreads) {
+      const float q = FUSED ? q_lds[i] : __fdiv_rn(in[i], denom);
+      out[i] = __fdiv_rn(__fsub_rn(hg_logit32(q), mean), std);
+    }
+  }
+}
+
 static void pack(const float* dense, int n_lines, bool columns, int layers, int rows, int cols, int** ptr_out, int** idx_out,
                  float** val_out, hipStream_t s) {
   int* ptr = nullptr;
@@ -275,6 +430,55 @@ int cd_geom_decode_sparse(const CdGeomMap* map, const float* x, float* y, int ba
     hipLaunchKernelGGL(geom_sparse_gather_kernel, row_grid(map, (int64_t)batch * channels), dim3(256), 0, s, map->row_ptr,
                        map->col_idx, map->val, (const int2*)count_ws, x, y, map->layers, map->rows, map->cols, batch, channels,
                        per_batch ? 1 : 0, rand, seed, offset);
+    CD_HIP(hipGetLastError());
+  });
+}
+
+int cd_preprocess_hgcal(const CdGeomMap* enc, const float* showers, int64_t row_stride, const float* gen_info, int gen_cols,
+                        float* out, float* layerE, float* e_out, int32_t* status, int batch, int layers, int cells, int grid,
+                        const double consts[6], float embed_mean, float embed_std, float max_deposit, const double* emin,
+                        const double* emax, float shower_scale, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(showers && gen_info && out && e_out && status && consts && emin && emax && batch > 0, "bad argument");
+    CD_REQUIRE(layers > 0 && layers <= kHgMaxLayers && cells > 0 && grid > 0 && (int64_t)layers * grid <= ((int64_t)1 << 28) &&
+                   row_stride >= cells,
+               "cd_preprocess_hgcal: 1..4096 layers, at most 2^28 grid values per shower, row_stride >= cells");
+    CD_REQUIRE(gen_cols >= 1 && gen_cols <= kHgMaxGenCols, "cd_preprocess_hgcal: gen_info has 1..8 columns");
+    for (int k = 0; k < gen_cols; ++k) CD_REQUIRE(emax[k] > emin[k], "cd_preprocess_hgcal: emax > emin in every column");
+    CD_REQUIRE(max_deposit > 0.f && consts[1] != 0.0 && consts[3] != 0.0 && consts[5] != 0.0,
+               "cd_preprocess_hgcal: max_deposit must be positive and the three std constants non-zero");
+    PreHgcalArgs a{};
+    a.showers = showers; a.row_stride = row_stride; a.gen_info = gen_info; a.out = out; a.layerE = layerE; a.e_out = e_out;
+    a.status = status; a.layers = layers; a.cells = cells; a.grid = grid; a.gen_cols = gen_cols; a.layer_mode = layerE ? 1 : 0;
+    a.logit_mean = consts[0]; a.logit_std = consts[1]; a.totalE_mean = consts[2]; a.totalE_std = consts[3];
+    a.layers_mean = consts[4]; a.layers_std = consts[5]; a.max_deposit = max_deposit;
+    for (int k = 0; k < gen_cols; ++k) {
+      a.emin[k] = emin[k];
+      a.emax[k] = emax[k];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sums = sizeof(double) * (size_t)((layers + 1) & ~1), grid_bytes = sizeof(float) * (size_t)layers * grid;
+    if (enc) {
+      CD_REQUIRE(enc->layers == layers && enc->rows == grid && enc->cols == cells,
+                 "cd_preprocess_hgcal: the map is not (layers, grid, cells)");
+      CD_REQUIRE(embed_std != 0.f && shower_scale > 0.f, "cd_preprocess_hgcal: embed_std must not be 0, shower_scale positive");
+      CD_REQUIRE(grid_bytes <= kHgGridBytes && cells <= kHgMaxCells && layers <= kHgFusedMaxLayers,
+                 "cd_preprocess_hgcal: the fused form keeps the grid of a shower on chip: layers * grid * 4 bytes <= 48 KB, "
+                 "cells <= 2048, layers <= 512; beyond that apply the map first (cd_geom_apply) and pass enc = NULL");
+      a.row_ptr = enc->row_ptr; a.col_idx = enc->col_idx; a.val = enc->val;
+      a.embed_mean = embed_mean; a.embed_std = embed_std; a.scale = shower_scale;
+      a.embed_affine = !(embed_std == 1.f && embed_mean == 0.f);  // cd_geom_apply's choice of the plain product
+      CD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+      hipLaunchKernelGGL(preprocess_hgcal_kernel<true>, dim3((unsigned)batch), dim3(kHgThreads),
+                         sums + grid_bytes + sizeof(float) * (size_t)cells, s, a, 1);
+    } else {
+      CD_REQUIRE(cells == grid && row_stride == grid,
+                 "cd_preprocess_hgcal: without a map the showers are (batch, layers, grid): cells = row_stride = grid");
+      const int cached = a.layer_mode && grid_bytes <= kHgGridBytes && sums + grid_bytes <= 60 * 1024;
+      CD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+      hipLaunchKernelGGL(preprocess_hgcal_kernel<false>, dim3((unsigned)batch), dim3(kHgThreads), sums + (cached ? grid_bytes : 0),
+                         s, a, cached);
+    }
     CD_HIP(hipGetLastError());
   });
 }

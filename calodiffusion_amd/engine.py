@@ -105,6 +105,9 @@ _SIGNATURES = {
                                          C.c_float, C.c_float, C.c_int, _P]),
     "cd_preprocess": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float,
                                 C.c_float, C.c_int, C.c_float, _P]),
+    "cd_preprocess_hgcal": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(C.c_double), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.c_float, _P]),
     "cd_geom_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
     "cd_geom_destroy": (C.c_int, [_P]),
     "cd_geom_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),

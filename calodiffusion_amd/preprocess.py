@@ -3,8 +3,11 @@
 device (``cd_preprocess``).  The inverse of ``postprocess.ReverseNorm``, for the same configurations.
 
 Supported: ``dataset_num`` 2 / 3, ``showerMap`` 'layer-logit-norm' / 'logit-norm' (the shipped Dataset-2 / Dataset-3 configs),
-regular grid (``orig_shape=False``).  Dataset-0/1 (geometry conversion from the binning XML), ``orig_shape``, the quantile /
-log / sqrt / scaled maps and HGCal's ``preprocess_hgcal_shower`` are not provided.  Reading the HDF5 file stays the caller's.
+regular grid (``orig_shape=False``).  Dataset-0/1 (geometry conversion from the binning XML), ``orig_shape`` and the quantile /
+log / sqrt / scaled maps are not provided.  Reading the HDF5 file stays the caller's.
+
+HGCal has its own pair, ``preprocess_hgcal_shower`` and ``PreprocessHGCal`` (``DataLoaderHGCal``, utils/HGCal_utils.py:20-164,
+on ``cd_preprocess_hgcal``): raw cells through the geometry map of an ``hgcal.HGCalConverter`` to a loader batch in one launch.
 
 A shower without energy (incident energy <= 0, or no deposit at all) is where the reference's masked arrays hand back
 unspecified fill values; here such a row raises ``ValueError`` and nothing is returned.  An empty LAYER of a shower that has
@@ -101,8 +104,8 @@ class Preprocess:
 
     def __init__(self, config, shower_scale=0.001):
         if config.get("HGCAL", False):
-            raise NotImplementedError("Preprocess: HGCal's preprocess_hgcal_shower (its embedding needs the geometry file) is "
-                                      "not provided")
+            raise NotImplementedError("Preprocess: an HGCal config needs preprocess_hgcal_shower and the geometry map: use "
+                                      "PreprocessHGCal(config, geometry)")
         missing = [k for k in ("EMAX", "EMIN", "logE", "MAXDEP", "SHOWERMAP") if k not in config]
         shape = config.get("SHAPE_PAD", config.get("SHAPE_FINAL"))
         if shape is None:
@@ -120,4 +123,133 @@ class Preprocess:
     def __call__(self, showers, incident_energies):
         data, layers, E = _run(showers, incident_energies, self.dims, self.showerMap, self.dataset_num, self.max_deposit,
                                self.emin, self.emax, self.logE, self.shower_scale)
+        return E, layers, data
+
+
+# ---- HGCal ---------------------------------------------------------------------------------------------------------------------
+HGCAL_SETS = (100, 101, 111, 120, 121)
+# the on-chip limits of cd_preprocess_hgcal's fused form (include/calodiff.h)
+FUSED_GRID_BYTES, FUSED_MAX_CELLS, FUSED_MAX_LAYERS = 48 * 1024, 2048, 512
+
+
+def _refuse_uncovered_hgcal(who, showerMap, dataset_num, orig_shape):
+    if orig_shape:
+        raise NotImplementedError("%s: orig_shape=True is not provided" % who)
+    if dataset_num not in HGCAL_SETS:
+        raise NotImplementedError("%s: no HGCal constants for dataset_num %r (the HGCal sets are %s)"
+                                  % (who, dataset_num, ", ".join(str(n) for n in HGCAL_SETS)))
+    if showerMap not in SHOWER_MAPS:
+        missing = [k for k in ("quantile", "scaled", "sqrt", "log") if k in showerMap.replace("logit", "")]
+        what = "the %s map" % missing[0] if missing else "this map"
+        raise NotImplementedError("%s: showerMap '%s' is not provided (%s is missing; %s only)"
+                                  % (who, showerMap, what, " / ".join(SHOWER_MAPS)))
+
+
+def _run_hgcal(showers, gen_info, bins, showerMap, dataset_num, max_deposit, emin, emax, conv=None, max_cells=None,
+               shower_scale=1.0, fused=True):
+    """(data (B,1,L,A,R), layerE (B,1+L) or None, E (B,k)): device tensors, one cd_preprocess_hgcal call and one flag read.
+    ``conv`` None: ``showers`` are already on the grid.  Otherwise raw cells (B, L, >= max_cells); a grid beyond the fused
+    form's on-chip limit (or ``fused=False``) runs the composition, ``conv.enc`` then the grid form: the same bits."""
+    L, A, R = (int(d) for d in bins)
+    v = _device_f32(showers, "showers")
+    B = v.shape[0] if v.dim() else 0
+    if B == 0:
+        raise ValueError("preprocess_hgcal: no showers")
+    g = _device_f32(gen_info, "gen_info")
+    if g.dim() == 1:
+        g = g.reshape(-1, 1)
+    k = len(emin)
+    if g.dim() != 2 or tuple(g.shape) != (B, k):
+        raise ValueError("preprocess_hgcal: gen_info of %s for %d showers and %d EMIN / EMAX columns" % (tuple(g.shape), B, k))
+    lib = engine.load_library()
+    handle, cells, stride, mean, std = None, A * R, A * R, 0.0, 1.0
+    if conv is None:
+        if v.numel() != B * L * A * R:
+            raise ValueError("preprocess_hgcal: showers of %s do not hold %d x %d x %d grid values each" % (tuple(v.shape), L, A, R))
+    else:
+        pm = conv.embeder.packed()
+        n = pm.cols if max_cells is None else int(max_cells)
+        if v.dim() != 3 or v.shape[1] != L or v.shape[2] < n or n != pm.cols or (pm.layers, pm.rows) != (L, A * R):
+            raise ValueError("preprocess_hgcal: showers of %s are not (batch, %d layers, >= %d cells) for a geometry map of "
+                             "(%d, %d, %d)" % (tuple(v.shape), L, n, pm.layers, pm.rows, pm.cols))
+        std, mean = conv._affine()
+        if fused and 4 * L * A * R <= FUSED_GRID_BYTES and n <= FUSED_MAX_CELLS and L <= FUSED_MAX_LAYERS:
+            handle, cells, stride = pm.handle, n, int(v.shape[2])
+        else:
+            v = conv.enc(v[:, :, :n] * float(shower_scale)).contiguous()
+    c = DATASET_PARAMS[dataset_num]
+    out = torch.empty((B, 1, L, A, R), dtype=torch.float32, device="cuda")
+    layerE = torch.empty((B, L + 1), dtype=torch.float32, device="cuda") if "layer" in showerMap else None
+    e_out = torch.empty((B, k), dtype=torch.float32, device="cuda")
+    status = torch.empty((1,), dtype=torch.int32, device="cuda")
+    consts = (C.c_double * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
+    engine._check(lib.cd_preprocess_hgcal(handle, v.data_ptr(), stride, g.data_ptr(), k, out.data_ptr(), engine._ptr(layerE),
+                                          e_out.data_ptr(), status.data_ptr(), B, L, cells, A * R, consts, float(mean), float(std),
+                                          float(max_deposit), (C.c_double * k)(*emin), (C.c_double * k)(*emax),
+                                          float(shower_scale), engine._stream()))
+    bad = int(status.item())
+    if bad:
+        raise ValueError("preprocess_hgcal: shower %d (the last such row of this call) has an incident energy <= 0, NaN or inf; "
+                         "the reference's masked arrays return unspecified fill values there.  Drop such rows before the call"
+                         % (bad - 1))
+    return out, layerE, e_out
+
+
+def preprocess_hgcal_shower(shower, e, shape, showerMap="log-norm", dataset_num=2, orig_shape=False, ecut=0, max_deposit=2):
+    """``preprocess_hgcal_shower`` (utils/HGCal_utils.py:20-86), same arguments and return values: (shower float32 ndarray shaped
+    like the input, layerE (B, 1+L) float32 ndarray or None).  ``shower`` is the EMBEDDED shower (..., L, alpha, r) in the
+    loader's units and ``e`` the incident energies (B,); ``shape`` and ``ecut`` are not used by the reference either.  A layer
+    without deposit and a shower without any are defined results (the masked logit); only ``e`` <= 0, NaN or inf raises."""
+    _refuse_uncovered_hgcal("preprocess_hgcal_shower", showerMap, dataset_num, orig_shape)
+    dims = tuple(shower.shape)
+    if len(dims) < 4:
+        raise ValueError("preprocess_hgcal_shower: the embedded shower is (batch, ..., layers, alpha, r); got %s" % (dims,))
+    # the condition map is not part of this function: emin / emax only have to be valid
+    out, layerE, _ = _run_hgcal(shower, _device_f32(e, "e").reshape(-1, 1), dims[-3:], showerMap, dataset_num, max_deposit,
+                                [0.0], [1.0])
+    return out.reshape(dims).cpu().numpy(), None if layerE is None else layerE.cpu().numpy()
+
+
+class PreprocessHGCal:
+    """Raw HGCal cell energies -> one loader batch on the device: what ``DataLoaderHGCal(embed=True)`` (utils/HGCal_utils.py:89-164)
+    does after reading the file, in one ``cd_preprocess_hgcal`` call.
+
+    Built from the config keys that loader is called with: SHAPE_PAD / SHAPE_FINAL, EMAX and EMIN (lists, one entry per
+    ``gen_info`` column, or scalars), MAXDEP, SHOWERMAP, DATASET_NUM, SHOWERSCALE (200.0 when absent; the ``shower_scale``
+    argument overrides it) and MAX_CELLS (the geometry's when absent).  ``geometry`` is an ``hgcal.HGCalConverter``; its
+    ``norm`` / ``embed_mean`` / ``embed_std`` are used as they are, so the loader's ``init(norm=True, dataset_num)`` is the
+    caller's, as for ``generate(geometry=)``.  Called with ``showers`` (B, L, >= max_cells) and ``gen_info`` (B,) / (B, k), numpy
+    arrays or tensors; returns device tensors ``(E (B, k), layers (B, 1+L) or None, data (B, 1, L, A, R))`` -- ready for
+    ``compute_loss(data, E, noise, layers)``."""
+
+    def __init__(self, config, geometry, shower_scale=None):
+        from .hgcal import HGCalConverter
+        if not isinstance(geometry, HGCalConverter):
+            raise TypeError("PreprocessHGCal: geometry must be an hgcal.HGCalConverter, not %s" % type(geometry).__name__)
+        missing = [k for k in ("EMAX", "EMIN", "MAXDEP", "SHOWERMAP", "DATASET_NUM") if k not in config]
+        shape = config.get("SHAPE_PAD", config.get("SHAPE_FINAL"))
+        if shape is None:
+            missing.append("SHAPE_PAD")
+        if missing:
+            raise ValueError("PreprocessHGCal: the config lacks %s" % ", ".join(missing))
+        self.dataset_num, self.showerMap = config["DATASET_NUM"], config["SHOWERMAP"]
+        _refuse_uncovered_hgcal("PreprocessHGCal", self.showerMap, self.dataset_num, False)
+        self.bins = tuple(int(d) for d in shape[-3:])
+        if self.bins != (geometry.num_layers, geometry.num_alpha_bins, geometry.num_r_bins):
+            raise ValueError("PreprocessHGCal: the config's grid %s is not the geometry's %s"
+                             % (self.bins, (geometry.num_layers, geometry.num_alpha_bins, geometry.num_r_bins)))
+        self.emin = [float(x) for x in np.atleast_1d(config["EMIN"])]
+        self.emax = [float(x) for x in np.atleast_1d(config["EMAX"])]
+        if len(self.emin) != len(self.emax):
+            raise ValueError("PreprocessHGCal: EMIN and EMAX differ in length")
+        self.max_deposit = float(config["MAXDEP"])
+        self.shower_scale = float(config.get("SHOWERSCALE", 200.0) if shower_scale is None else shower_scale)
+        self.max_cells = None if config.get("MAX_CELLS") is None else int(config["MAX_CELLS"])
+        self.geometry = geometry
+        self.fused = True
+
+    def __call__(self, showers, gen_info):
+        data, layers, E = _run_hgcal(showers, gen_info, self.bins, self.showerMap, self.dataset_num, self.max_deposit, self.emin,
+                                     self.emax, conv=self.geometry, max_cells=self.max_cells, shower_scale=self.shower_scale,
+                                     fused=self.fused)
         return E, layers, data

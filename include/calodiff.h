@@ -342,6 +342,38 @@ int cd_geom_sparse_workspace_bytes(const CdGeomMap* map, int batch, size_t* byte
 int cd_geom_decode_sparse(const CdGeomMap* map, const float* x, float* y, int batch, int channels, int per_batch,
                           const float* rand /* nullable */, uint64_t seed, uint64_t offset, void* count_ws, void* stream);
 
+/* HGCal forward pre-processing, cells to training batch: what DataLoaderHGCal (calodiffusion/utils/HGCal_utils.py:89-164) does
+ * between reading the file and returning (showers, gen, layerE) -- x shower_scale (:125-128), NN_embed.enc (:144-145, 636-640),
+ * preprocess_hgcal_shower (:20-86), the condition map (:131-132, 158) -- in one launch, one workgroup per shower.
+ *   enc != NULL  showers are raw cells (batch, layers, >= cells) with `row_stride` floats between layer rows (the [:, :, :max_cells]
+ *                slice of a wider file array needs no copy); each is multiplied by shower_scale in float32 and every grid value
+ *                is the packed map's row sum in ascending column order with the fmaf sequence and the (y - embed_mean) / embed_std
+ *                rounding of cd_geom_apply(affine_first = 0), so the result is bitwise that of cd_geom_apply into a temporary
+ *                followed by the enc == NULL form.  The map is (layers, grid, cells).  The grid of a shower stays in LDS:
+ *                layers * grid * 4 bytes <= 48 KB, cells <= 2048, layers <= 512, or the call fails naming these limits.
+ *   enc == NULL  showers are already on the grid, (batch, layers, grid) contiguous (cells = row_stride = grid); shower_scale,
+ *                embed_mean and embed_std are not used.  Any size: a grid beyond 48 KB is read twice.
+ * e = gen_info[:, 0], not scaled; gen_info (batch, gen_cols), gen_cols <= 8.  Outputs: out (batch, layers, grid), layerE
+ * (batch, 1 + layers) or NULL ('logit-norm'), e_out (batch, gen_cols) = (gen_info - emin) / (emax - emin) per column, in double
+ * from the HOST arrays emin / emax[gen_cols] (np.array(emin) is float64, :131-132) and rounded once.
+ * Numerics, as the reference forms them.  q = grid / (max_deposit e) is float32.  With layerE the reference's arrays are numpy
+ * masked arrays, whose arithmetic with python scalars is float64: the layer sums, the total and their quotient are float32 (here
+ * summed in fp64 in a fixed order -- a wave per layer, then the layers in layer order -- and rounded to float32 once), and
+ * logit (alpha 1e-8), the normalisations of total, layers and of every voxel are float64, rounded to float32 at the end; the
+ * voxels are not divided by their layer's energy.  Without layerE everything is float32.  consts = {logit_mean, logit_std,
+ * totalE_mean, totalE_std, layers_mean, layers_std} as doubles (rounded to float32 by the float32 mode, as numpy rounds them).
+ * logit is np.ma.log(o / (1 - o)).filled(0), o = alpha + (1 - 2 alpha) x: where the argument is not positive or the logarithm
+ * not finite the value is 0 BEFORE the normalisation (negative embedded values of a set with embed_mean > 0, negative layer
+ * shares); a layer without deposit is ordinary data (logit(0)), and a shower whose total is 0 has its layer shares masked the
+ * same way (np.ma.divide): defined results, no error.  status: ONE device int32, zeroed by the call, then 1 + the highest index
+ * of a shower with e <= 0, NaN or inf, where the reference returns whatever its masked buffers hold; such a row's outputs are
+ * not written.  A row's bits do not depend on the batch.  Nothing is allocated, no atomics but the status, and the stream is
+ * not synchronised: read status after the stream has finished. */
+int cd_preprocess_hgcal(const CdGeomMap* enc /* nullable */, const float* showers, int64_t row_stride, const float* gen_info,
+                        int gen_cols, float* out, float* layerE /* nullable */, float* e_out, int32_t* status, int batch,
+                        int layers, int cells, int grid, const double consts[6], float embed_mean, float embed_std,
+                        float max_deposit, const double* emin, const double* emax, float shower_scale, void* stream);
+
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
  * (calodiffusion/models/layerdiffusion.py:35-38, 114-132) samples the (B, D+1) {total, per-layer} energies with.
