@@ -113,6 +113,12 @@ _SIGNATURES = {
     "cd_geom_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "cd_geom_sparse_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_geom_decode_sparse": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_uint64, _P, _P]),
+    "cd_radial_create": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.POINTER(_P), _P]),
+    "cd_radial_destroy": (C.c_int, [_P]),
+    "cd_radial_enc": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "cd_radial_dec": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "cd_radial_enc_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "cd_radial_dec_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),

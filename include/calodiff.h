@@ -374,6 +374,46 @@ int cd_preprocess_hgcal(const CdGeomMap* enc /* nullable */, const float* shower
                         int layers, int cells, int grid, const double consts[6], float embed_mean, float embed_std,
                         float max_deposit, const double* emin, const double* emax, float shower_scale, void* stream);
 
+/* ---- Dataset-1 radial maps ----------------------------------------------------------------------------------------
+ * The linear maps between CaloChallenge Dataset-1's irregular voxels and the regular (layer, alpha, r) grid: GeomConverter
+ * (calodiffusion/utils/utils.py:659-784) with fixed matrices, NNConverter (:576-656) with trainable ones.  A flat shower
+ * (V voxels) is L layers; layer i holds voxels [bound[i], bound[i+1]) as (alpha[i], rin[i]), alpha[i] either 1 or A; the grid is
+ * (L, A, R).  The matrices are the `weight` tensors of the reference's nn.Linear(bias=False) layers, concatenated in layer
+ * order: encoder W_i (R, rin_i) at float offset R * (rin_0 + ... + rin_{i-1}), decoder D_i (rin_i, R) at the same offset.  They
+ * are DEVICE arrays passed per call (live parameters); the handle holds the layout only.
+ * Every sum is a chain of fp32 FMAs in a fixed order, there are no atomics, a row b of a result depends on row b of the inputs
+ * only (not on `batch`), and repeated calls are bitwise equal.  Each call is one launch; nothing is allocated and the stream is
+ * not synchronised.  A workgroup keeps the matrices of one direction and one shower in LDS, which sets the limits
+ *   L <= 64,   R * (rin_0 + ... + rin_{L-1}) <= 8192 floats (32 KB),   max(V, L * A * R) <= 6144 floats (24 KB);
+ * a geometry beyond them is refused by cd_radial_create (Dataset-1 photons: 5 layers, 1590 and 1500 floats). */
+typedef struct CdRadialMap CdRadialMap;
+/* bound[L+1], alpha[L], rin[L] are HOST arrays, copied to the device here (the call allocates, and synchronises `stream`).
+ * Refused with CD_EINVAL, before anything touches the device: null pointers, non-positive sizes, bound[0] != 0, a bound that is
+ * not strictly increasing, an alpha[i] outside {1, A} (where the reference calls exit(1), :626-631), rin[i] <= 0, a span
+ * bound[i+1] - bound[i] != alpha[i] * rin[i], and the limits above. */
+int cd_radial_create(int layers, const int32_t* bound, const int32_t* alpha, const int32_t* rin, int alpha_out, int r_out,
+                     CdRadialMap** out, void* stream);
+int cd_radial_destroy(CdRadialMap* map);
+/* NNConverter.enc (:610-633) and GeomConverter.convert of the reshaped shower (:724-732, 744-764): x (batch, V) ->
+ * y (batch, 1, L, A, R);  y[b,0,i,a,:] = W_i x[b, layer i, a, :]  where alpha[i] == A, else  (W_i x[b, layer i, 0, :]) / A  in
+ * every a: the dot product in ascending input bin, then the one division (:618-625). */
+int cd_radial_enc(const CdRadialMap* map, const float* w, const float* x, float* y, int batch, void* stream);
+/* NNConverter.dec (:635-653) and GeomConverter.unconvert + unreshape (:734-742, 766-784): g (batch, 1, L, A, R) -> x (batch, V);
+ * o[b,a,:] = D_i g[b,0,i,a,:] in ascending r, and where alpha[i] == 1 the voxel is the sum of o over a in ascending a (:644). */
+int cd_radial_dec(const CdRadialMap* map, const float* d, const float* g, float* x, int batch, void* stream);
+/* What autograd derives from enc: dx (batch, V) = enc's transpose applied to gy (batch, 1, L, A, R) -- per a the sum over r in
+ * ascending r; where alpha[i] == 1 those are summed in ascending a and divided by A once -- and, unless dw is NULL,
+ * dw (as w):  dW_i[r, j] = sum_b sum_a gy[b,0,i,a,r] x[b, layer i, a, j]  (alpha[i] == 1: sum_b ((sum_a gy[b,0,i,a,r]) / A) x[b, layer
+ * i, 0, j]).  The batch sum has a fixed order: 8 interleaved slices (b mod 8), each in ascending b and a, then a fixed tree over
+ * the slices, inside the same launch. */
+int cd_radial_enc_vjp(const CdRadialMap* map, const float* w, const float* x, const float* gy, float* dx, float* dw /* nullable */,
+                      int batch, void* stream);
+/* What autograd derives from dec: dg (batch, 1, L, A, R):  dg[b,0,i,a,:] = D_i^T gx[b, layer i, a, :]  (alpha[i] == 1: of
+ * gx[b, layer i, 0, :], in every a), in ascending input bin, and, unless dd is NULL, dd (as d):  dD_i[j, r] = sum_b sum_a
+ * gx[b, layer i, a, j] g[b,0,i,a,r]  (alpha[i] == 1: sum_b gx[b, layer i, 0, j] sum_a g[b,0,i,a,r]), reduced as dw is. */
+int cd_radial_dec_vjp(const CdRadialMap* map, const float* d, const float* g, const float* gx, float* dg, float* dd /* nullable */,
+                      int batch, void* stream);
+
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
  * (calodiffusion/models/layerdiffusion.py:35-38, 114-132) samples the (B, D+1) {total, per-layer} energies with.
