@@ -6,3 +6,4 @@ from calodiffusion_amd.utils import create_phi_image, create_R_Z_image, get_devi
 from calodiffusion_amd.postprocess import ReverseNorm, ReverseNormCaloChall  # noqa: F401
 from calodiffusion_amd.preprocess import Preprocess, preprocess_shower  # noqa: F401
 from calodiffusion_amd.geom1 import GeomConverter, NNConverter  # noqa: F401
+from calodiffusion_amd.xml_handler import XMLHandler  # noqa: F401

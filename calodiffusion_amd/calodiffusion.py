@@ -24,14 +24,14 @@ class CaloDiffusion(Diffusion):
         self.layer_cond = "layer" in config.get("SHOWERMAP", "")
         if self.fully_connected:
             raise NotImplementedError("the FCN/ResNet layer model is outside the HIP hot path (SURVEY.md 8f rank 3)")
-        if "NN" in config.get("SHOWER_EMBED", "") and not self.pre_embed:
-            raise NotImplementedError("in-model geometry embeddings (NNConverter / HGCalConverter) need binning files that "
-                                      "are not part of the hot path; use a pre-embedded ('...-pre-embed') dataset")
+        if self.hgcal and not self.pre_embed:
+            raise NotImplementedError("HGCal's in-model embedding (HGCalConverter inside forward) is not on the device path; use a "
+                                      "pre-embedded ('...-pre-embed') dataset")
         if self.time_embed not in ("log", "sigma"):
             raise KeyError(self.time_embed)  # the reference's do_time_embed raises the same way (calodiffusion.py:148-152)
         self.model = self.init_model()
-        self.NN_embed = None
-        self.do_embed = False
+        self.NN_embed = self.init_embedding_model()  # (after init_model: the RNG draws come in the reference's order)
+        self.do_embed = self.NN_embed is not None and not self.pre_embed
 
     # ------------------------------------------------------------------ construction / weights
     def init_model(self):
@@ -52,6 +52,31 @@ class CaloDiffusion(Diffusion):
             coords=utils.coordinate_profiles(self.dataset_num, cfg["SHAPE_FINAL"][2:]))
         return unet.to(self.device)
 
+    def init_embedding_model(self):
+        """calodiffusion.py:100-119, the non-HGCal 'NN' case: an ``NNConverter`` over the binning file.  Without an XML at hand,
+        ``config['NN_EMBED']`` may hold an already built ``geom1.NNConverter`` (taken as it is: no RNG draws)."""
+        cfg = self.config
+        if "NN" not in cfg.get("SHOWER_EMBED", "") or self.hgcal or self.pre_embed:
+            return None
+        from .geom1 import NNConverter
+        nn_embed = cfg.get("NN_EMBED")
+        if nn_embed is None:
+            from .xml_handler import XMLHandler
+            bins = XMLHandler("photon" if cfg.get("DATASET_NUM", 2) == 1 else "pion", cfg["BIN_FILE"])
+            nn_embed = NNConverter(bins=bins)
+        elif not isinstance(nn_embed, NNConverter):
+            raise TypeError("config['NN_EMBED'] takes a calodiffusion_amd.geom1.NNConverter")
+        gc = nn_embed.gc
+        grid = tuple(int(v) for v in cfg["SHAPE_FINAL"][2:])
+        have = (int(gc.num_layers), int(gc.alpha_out), int(gc.dim_r_out))
+        if have != grid:
+            raise ValueError(f"the geometry embedding maps onto (layers, alpha_out, dim_r_out) = {have}, but SHAPE_FINAL gives the "
+                             f"U-Net the grid {grid}")
+        gc.descriptor()  # refuses a layout the device maps cannot hold, now rather than at the first denoise
+        if int(gc.layer_boundaries[-1]) != int(self._data_shape[-1]):
+            raise ValueError(f"the geometry embedding has {int(gc.layer_boundaries[-1])} voxels, SHAPE_ORIG says {self._data_shape[-1]}")
+        return nn_embed.to(self.device)
+
     def load_state_dict(self, state_dict, strict=True):
         """Prefix-tolerant loading, as the reference (calodiffusion.py:31-37)."""
         base = list(state_dict.keys())[10].split(".")[0]
@@ -60,7 +85,14 @@ class CaloDiffusion(Diffusion):
         return super().load_state_dict(state_dict, strict)
 
     def engine(self):
-        return self.model.engine()
+        eng = self.model.engine()
+        if self.do_embed and eng.embedding is not self.NN_embed:
+            eng.set_embedding(self.NN_embed)  # (a fresh engine after .to(): bound again)
+        return eng
+
+    def _params(self):
+        """The parameters the device calls hand gradients to, in ``engine().param_grads`` order."""
+        return list(self.model.parameters()) + (list(self.NN_embed.parameters()) if self.do_embed else [])
 
     def to(self, *a, **k):
         out = super().to(*a, **k)
@@ -81,8 +113,11 @@ class CaloDiffusion(Diffusion):
         """calodiffusion.py:86-98: x is the already c_in-scaled input; returns the raw network output F."""
         if controls is not None:
             raise NotImplementedError("ControlNet is dead code in the reference")
+        if self.do_embed:
+            x = self.NN_embed.enc(x.to(torch.float32))
         rz_phi = self.add_RZPhi(x).float()
-        return self.model(rz_phi, cond=self.cond_tensor(E, layers), time=time.float())
+        out = self.model(rz_phi, cond=self.cond_tensor(E, layers), time=time.float())
+        return self.NN_embed.dec(out) if self.do_embed else out
 
     def add_RZPhi(self, x):
         """calodiffusion.py:121-142 (only used by the generic `forward`; `denoise` synthesises the channels in-kernel)."""
@@ -101,7 +136,8 @@ class CaloDiffusion(Diffusion):
         return embed[self.time_embed](sigma)
 
     def denoise(self, x, E=None, sigma=None, layers=None, controls=None):
-        """EDM-preconditioned denoiser (calodiffusion.py:154-169): one C-ABI call.
+        """EDM-preconditioned denoiser (calodiffusion.py:154-169): one C-ABI call.  With a geometry embedding (``do_embed``) x is
+        the flat shower (B, V): enc and dec run inside the call, and the embedding's weights take gradients as the U-Net's do.
 
         Differentiable when ``torch.is_grad_enabled()`` and ``x.requires_grad``: backward then gives x its gradient and, if a
         parameter requires grad, every parameter too (cd_denoise_vjp recomputes the forward on the device).  Any other call is
@@ -114,7 +150,7 @@ class CaloDiffusion(Diffusion):
             for name, t in (("sigma", sigma), ("E", E), ("layers", layers)):
                 if isinstance(t, torch.Tensor) and t.requires_grad:
                     raise NotImplementedError(f"denoise: no gradient with respect to {name}; pass {name}.detach()")
-            params = list(self.model.parameters())
+            params = self._params()
             return _Denoise.apply(self.engine(), x, sigma.reshape(-1), self.cond_tensor(E, layers), *params)
         return self.engine().denoise(x, sigma.reshape(-1), self.cond_tensor(E, layers))
 

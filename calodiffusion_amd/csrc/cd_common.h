@@ -627,6 +627,24 @@ __device__ __forceinline__ float objective_weight(int objective, int loss_type, 
   if (loss_type != 0 || objective == 1) return 1.0f;
   return objective == 0 ? 1.0f + 1.0f / (sg * sg) : 1.0f / (sg * sg);
 }
+// d loss / d x0 = norm * w_b * f'(d):  l2: 2 w d / (mean(w) N);  mse: 2 d / N;  l1: sign(d) / N;  huber: clamp(d, -1, 1) / N
+// (scal: (batch, 4), sigma in column 3; one thread of a workgroup evaluates the norm)
+__device__ __forceinline__ float loss_grad_norm(const float* scal, int batch, int64_t per, int loss_type, int objective) {
+  double wsum = 0.0;
+  for (int b = 0; b < batch; ++b) {
+    wsum += (double)objective_weight(objective, 0, scal[b * 4 + 3]);
+  }
+  return loss_type == 0 ? (float)(2.0 / ((wsum / batch) * (double)batch * (double)per))
+                        : (float)((loss_type == 2 ? 2.0 : 1.0) / ((double)batch * (double)per));
+}
+// ... times d pred / d F (`chain`): the gradient at the network's output F
+__device__ __forceinline__ float loss_grad_dF(float norm, float x0, float data, float noise, float sg, float chain, int loss_type,
+                                              int objective) {
+  const float dd = objective_residual(objective, x0, data, noise, sg);
+  const float fp = loss_type == 1 ? (dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f))
+                                  : (loss_type == 3 ? fminf(fmaxf(dd, -1.f), 1.f) : dd);
+  return norm * objective_weight(objective, loss_type, sg) * fp * chain;
+}
 
 void launch_loss_partial(const float* x0, const float* data, const float* noise, const float* sigma_b, double* partial, int batch,
                          int64_t per, hipStream_t s, int loss_type = 0, int objective = 0);

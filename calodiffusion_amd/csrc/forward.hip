@@ -659,16 +659,22 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
   float* emb = pre ? opt->emb_pre : p->ws.get<float>((size_t)B * p->emb_ld);
   float* scal = pre ? opt->scal_pre : p->ws.get<float>((size_t)B * 4);
   float* h = p->ws.get<float>((size_t)B * dims.vox() * d.layer_sizes[0]);
+  // flat-state embedding (cd_plan_set_radial): x and out are (B, V); the network runs on g_in = enc(c_in x) and leaves its raw
+  // output on the grid, which embed-out decodes and combines with x
+  const CdRadialMap* rad = raw ? nullptr : p->rad.map;
+  float* g_in = rad ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
+  float* f_grid = rad ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
   if (!r.dry()) {
     // (running this launch beside the init conv on a second stream was measured: no gain inside the step graph)
     if (!pre) launch_embed(embed_args(p, B, cond, t, raw ? CD_TIME_RAW : d.time_embed_kind, emb, raw ? nullptr : scal), s);
+    if (rad) launch_embed_in(rad, p->rad.enc_w, x, scal, g_in, B, s);
     InitConvArgs a;
-    a.x = x; a.cin = d.in_channels; a.wpk = p->packed(p->init_w); a.bias = p->raw(p->init_b); a.out = h; a.batch = B;
+    a.x = rad ? g_in : x; a.cin = d.in_channels; a.wpk = p->packed(p->init_w); a.bias = p->raw(p->init_b); a.out = h; a.batch = B;
     a.cout = d.layer_sizes[0]; a.dims = dims;
     if (raw) {
       a.cx = d.in_channels;
     } else {
-      a.cx = 1; a.sigma_b = t; a.sigma_data = d.sigma_data; a.use_rz = d.rz_input; a.use_phi = d.phi_input;
+      a.cx = 1; a.sigma_b = rad ? nullptr : t; a.sigma_data = d.sigma_data; a.use_rz = d.rz_input; a.use_phi = d.phi_input;  // (g_in carries c_in)
       a.r_w = p->d_coords; a.z_d = p->d_coords + d.grid[2]; a.phi_h = p->d_coords + d.grid[2] + d.grid[0];
       a.coord_table = p->d_init_table; a.table_ready = true; a.status = r.status;
     }
@@ -680,14 +686,20 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
   float* hf = unet_body(p, r, emb, h, head_fused ? &lazy : nullptr, &xin);
   if (!r.dry()) {
     HeadArgs ha;
-    ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = out; ha.batch = B; ha.vox = dims.vox();
-    if (!raw) { ha.x = x; ha.scal = scal; ha.objective = d.objective; }
+    ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = rad ? f_grid : out; ha.batch = B; ha.vox = dims.vox();
+    if (!raw && !rad) { ha.x = x; ha.scal = scal; ha.objective = d.objective; }
     if (lazy.on) { ha.defer = lazy.gn; ha.res = xin; }
-    if (opt && opt->upd) {
+    if (opt && opt->upd && !rad) {
       ha.upd_stepvals = opt->upd->upd_stepvals; ha.upd_noise = opt->upd->upd_noise; ha.upd_x_next = opt->upd->upd_x_next;
       ha.upd_xs = opt->upd->upd_xs; ha.upd_x0s = opt->upd->upd_x0s;
     }
     launch_head(ha, s);
+    // (the sampler's fused update moves with the combination: it acts on the flat state)
+    if (rad) launch_embed_out(rad, p->rad.dec_w, f_grid, x, scal, d.objective, out, opt ? opt->upd : nullptr, B, s);
+  }
+  if (rad) {
+    r.ws->release(f_grid);
+    r.ws->release(g_in);
   }
   if (lazy.on) {
     r.ws->release(lazy.part);
@@ -707,7 +719,7 @@ extern "C" {
 int cd_plan_workspace_bytes(CdPlan* plan, int batch, size_t* bytes) {
   return guarded([&] {
     CD_REQUIRE(plan && bytes && batch > 0, "bad argument");
-    const int64_t n = (int64_t)batch * plan->shapes[0].vox();
+    const int64_t n = (int64_t)batch * plan->state_per();
     *bytes = dry_forward_bytes(plan, batch, [&] {
       // superset of what any entry point allocates around forward_impl: x0 / noise / x_noisy, sigma, partials
       plan->ws.get<float>((size_t)n);
@@ -768,7 +780,7 @@ int cd_loss_hybrid(CdPlan* plan, int batch, const float* data, const float* nois
     CD_REQUIRE(loss_type >= CD_LOSS_L2 && loss_type <= CD_LOSS_HUBER, "loss_type must be one of CD_LOSS_L2 / L1 / MSE / HUBER");
     check_ready(plan, true);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per = plan->shapes[0].vox();
+    const int64_t per = plan->state_per();
     const int64_t n = (int64_t)batch * per;
     plan->ws.reset((char*)workspace, workspace_bytes, false);
     float* xn = plan->ws.get<float>((size_t)n);

@@ -1666,15 +1666,7 @@ __global__ void __launch_bounds__(256) head_loss_bwd_kernel(const float* __restr
   __shared__ float sNorm;
   const int tid = threadIdx.x, sub = tid & 7, grp = tid >> 3;
   if (tid < 32) sW[tid] = wh[tid];
-  if (tid == 0) {
-    double wsum = 0.0;
-    for (int b = 0; b < batch; ++b) {
-      wsum += (double)objective_weight(objective, 0, scal[b * 4 + 3]);
-    }
-    // d loss / d x0 = sNorm * w_b * f'(d):  l2: 2 w d / (mean(w) N);  mse: 2 d / N;  l1: sign(d) / N;  huber: clamp(d, -1, 1) / N
-    sNorm = loss_type == 0 ? (float)(2.0 / ((wsum / batch) * (double)batch * (double)vox))
-                           : (float)((loss_type == 2 ? 2.0 : 1.0) / ((double)batch * (double)vox));
-  }
+  if (tid == 0) sNorm = loss_grad_norm(scal, batch, vox, loss_type, objective);
   __syncthreads();
   const int64_t total = (int64_t)batch * vox;
   f32x4 aw = {0.f, 0.f, 0.f, 0.f};
@@ -1682,12 +1674,9 @@ __global__ void __launch_bounds__(256) head_loss_bwd_kernel(const float* __restr
   for (int64_t i = (int64_t)blockIdx.x * 32 + grp; i < total; i += (int64_t)gridDim.x * 32) {
     const int b = (int)(i / vox);
     const float sg = scal[b * 4 + 3];
-    const float dd = objective_residual(objective, x0[i], data[i], objective == 1 ? noise[i] : 0.f, sg);
-    const float fp = loss_type == 1 ? (dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f))
-                                    : (loss_type == 3 ? fminf(fmaxf(dd, -1.f), 1.f) : dd);
     // d pred / d F: c_out (hybrid), -sigma (noise_pred: out = x - sigma F and pred ~ out), 1 (mean_pred)
     const float chain = objective == 0 ? scal[b * 4 + 2] : (objective == 1 ? -sg : 1.0f);
-    const float dF = sNorm * objective_weight(objective, loss_type, sg) * fp * chain;
+    const float dF = loss_grad_dF(sNorm, x0[i], data[i], objective == 1 ? noise[i] : 0.f, sg, chain, loss_type, objective);
     const f32x4 hv = *(const f32x4*)(h + (size_t)i * 32 + sub * 4);
     f32x4 o;
 #pragma unroll

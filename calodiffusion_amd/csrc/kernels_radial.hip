@@ -1,6 +1,9 @@
 // Dataset-1 radial maps (include/calodiff.h, "Dataset-1 radial maps"): GeomConverter / NNConverter of the reference
 // (calodiffusion/utils/utils.py:576-784) as four launches -- enc, dec and the vector-Jacobian product of each -- over per-layer
-// matrices that are live parameters.  Kernels and their C ABI; nothing here touches a plan.
+// matrices that are live parameters.  Kernels and their C ABI, and the forms a plan with a flat-state embedding
+// (cd_plan_set_radial) launches around its U-Net: the same row programs with the EDM preconditioning in their staging (embed-in:
+// enc of c_in x) and in their epilogue (embed-out: dec, then the objective's combination and a sampler's fused update; enc's VJP:
+// the direct x term).
 //
 // Two row programs serve the four operations, because a VJP with respect to the input is the other direction's product with the
 // transposed matrix:
@@ -16,16 +19,6 @@
 #include "plan_internal.h"
 
 #include <vector>
-
-struct CdRadialMap {
-  int layers = 0, A = 0, R = 0, V = 0, wtotal = 0;
-  int4* lay = nullptr;  // device, per layer {bound, alpha, rin, float offset of its matrix}
-  int* vlay = nullptr;  // device, layer of every voxel
-  ~CdRadialMap() {
-    if (lay) (void)hipFree(lay);
-    if (vlay) (void)hipFree(vlay);
-  }
-};
 
 namespace cd {
 namespace {
@@ -47,7 +40,19 @@ struct RadialArgs {
   const float* other;  // weight gradient: the forward's input (`in` is then the cotangent)
   float* dw;           // weight gradient or null
   int L, A, R, V, wtotal, batch, row_blocks;
+  // plan forms (null / 0: the plain maps).  scal: (batch, 4) {c_in, c_skip, c_out, sigma} of embed_kernel
+  const float* scal;   // expand<ENC>: the staged row is c_in * in.  collapse: the scalars of its epilogue
+  int epi;             // collapse: kEpiNone, kEpiDenoise (DEC) or kEpiDirect (enc's VJP)
+  int objective;       // CD_OBJ_*
+  const float* xflat;  // kEpiDenoise: the denoiser's input x (batch, V);  kEpiDirect: the caller's cotangent gy (batch, V)
+  // kEpiDenoise: the sampler update of head_kernel (HeadArgs::upd_*), on the flat state
+  const float* upd_stepvals;
+  const float* upd_noise;
+  float* upd_x_next;
+  float* upd_xs;
+  float* upd_x0s;
 };
+enum { kEpiNone = 0, kEpiDenoise = 1, kEpiDirect = 2 };
 
 // lay_s[L] (16 bytes each), then the matrices (wtotal floats rounded up to 4) or the weight gradient's partial sums, then a row
 __device__ __forceinline__ float* rad_weights(char* smem, int L) { return (float*)(smem + sizeof(int4) * (size_t)L); }
@@ -137,7 +142,12 @@ __global__ void __launch_bounds__(kRadThreads) radial_expand_kernel(RadialArgs a
   const int AR = a.A * a.R, LAR = a.L * AR;
   for (int b = blockIdx.x; b < a.batch; b += a.row_blocks) {
     const float* in = a.in + (size_t)b * a.V;
-    for (int v = threadIdx.x; v < a.V; v += kRadThreads) row[v] = in[v];
+    if (ENC && a.scal) {  // embed-in: the scaling first, then the dot product (x * scales['c_in'], then NN_embed.enc)
+      const float c_in = a.scal[(size_t)b * 4];
+      for (int v = threadIdx.x; v < a.V; v += kRadThreads) row[v] = __fmul_rn(in[v], c_in);
+    } else {
+      for (int v = threadIdx.x; v < a.V; v += kRadThreads) row[v] = in[v];
+    }
     __syncthreads();  // (the first pass: the matrices too)
     float* out = a.out + (size_t)b * LAR;
     for (int o = threadIdx.x; o < LAR; o += kRadThreads) {
@@ -190,7 +200,27 @@ __global__ void __launch_bounds__(kRadThreads) radial_collapse_kernel(RadialArgs
         res = one ? __fadd_rn(res, acc) : acc;
       }
       if (!DEC && one) res = __fdiv_rn(res, (float)a.A);
-      out[v] = res;
+      if (a.epi == kEpiDenoise) {  // head_kernel's combination and sampler update, res in the place of the head's F
+        const size_t i = (size_t)b * a.V + v;
+        const float xv = a.xflat[i];
+        float pred = res;
+        if (a.objective == 0) pred = a.scal[b * 4 + 1] * xv + a.scal[b * 4 + 2] * pred;
+        else if (a.objective == 1) pred = xv - a.scal[b * 4 + 3] * pred;
+        out[v] = pred;
+        if (a.upd_stepvals) {  // (ddim_update_kernel's arithmetic)
+          const float sigma = a.upd_stepvals[0], sprev = a.upd_stepvals[1], dsig = a.upd_stepvals[2], denom = a.upd_stepvals[3];
+          const float eps = (xv - pred) / sigma;
+          float r = pred + sprev * eps;
+          if (a.upd_noise) r += dsig * a.upd_noise[i] / denom;
+          a.upd_x_next[i] = r;
+          if (a.upd_xs) a.upd_xs[i] = r;
+          if (a.upd_x0s) a.upd_x0s[i] = pred;
+        }
+      } else if (a.epi == kEpiDirect) {  // init_dgrad_kernel's epilogue: res carries c_in already
+        out[v] = a.objective == 2 ? res : fmaf(a.objective == 0 ? a.scal[b * 4 + 1] : 1.f, a.xflat[(size_t)b * a.V + v], res);
+      } else {
+        out[v] = res;
+      }
     }
     __syncthreads();
   }
@@ -201,8 +231,9 @@ namespace {
 enum RadialOp { kEnc, kDec, kEncVjp, kDecVjp };
 
 void radial_launch(RadialOp op, const CdRadialMap* m, const float* w, const float* in, float* out, const float* other, float* dw,
-                   int batch, hipStream_t s) {
+                   int batch, hipStream_t s, const RadialArgs* plan_form = nullptr) {
   RadialArgs a{};
+  if (plan_form) a = *plan_form;  // (scal, epi, objective, xflat, upd_*; everything else is set below)
   a.lay = m->lay; a.vlay = m->vlay; a.w = w; a.in = in; a.out = out; a.other = other; a.dw = dw;
   a.L = m->layers; a.A = m->A; a.R = m->R; a.V = m->V; a.wtotal = m->wtotal; a.batch = batch;
   a.row_blocks = batch < kRadMaxRowBlocks ? batch : kRadMaxRowBlocks;
@@ -222,6 +253,72 @@ void radial_launch(RadialOp op, const CdRadialMap* m, const float* w, const floa
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------------------
+// The forms of a plan with a flat-state embedding (forward.hip, train.hip)
+// ------------------------------------------------------------------------------------------------------------
+void launch_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s) {
+  RadialArgs f{};
+  f.scal = scal;
+  radial_launch(kEnc, m, enc_w, x, g, nullptr, nullptr, batch, s, &f);
+}
+
+void launch_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
+                      float* out, const HeadArgs* upd, int batch, hipStream_t s) {
+  RadialArgs f{};
+  f.scal = scal; f.epi = kEpiDenoise; f.objective = objective; f.xflat = x;
+  if (upd && upd->upd_stepvals) {
+    CD_REQUIRE(upd->upd_x_next, "embed-out: the fused sampler update needs x_next");
+    f.upd_stepvals = upd->upd_stepvals; f.upd_noise = upd->upd_noise; f.upd_x_next = upd->upd_x_next;
+    f.upd_xs = upd->upd_xs; f.upd_x0s = upd->upd_x0s;
+  }
+  radial_launch(kDec, m, dec_w, F, out, nullptr, nullptr, batch, s, &f);
+}
+
+void launch_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
+                          hipStream_t s) {
+  radial_launch(kDecVjp, m, dec_w, gf, dF, F, dd, batch, s);
+}
+
+void launch_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
+                          const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s) {
+  RadialArgs f{};
+  if (gy) {
+    f.scal = scal; f.epi = kEpiDirect; f.objective = objective; f.xflat = gy;
+  }
+  radial_launch(kEncVjp, m, enc_w, dg, dx, x, dw, batch, s, &f);
+}
+
+// The cotangent of f = dec(F) on the flat state.  LOSS: head_loss_bwd_kernel's dF from the loss (x0, data, noise); otherwise
+// head_vjp_kernel's dF = coef_b gy from a caller's cotangent of the denoiser output.
+template <bool LOSS>
+__global__ void __launch_bounds__(256) embed_cotangent_kernel(const float* __restrict__ x0, const float* __restrict__ data,
+                                                              const float* __restrict__ noise, const float* __restrict__ gy,
+                                                              const float* __restrict__ scal, float* __restrict__ gf, int batch,
+                                                              int64_t per, int loss_type, int objective) {
+  __shared__ float sNorm;
+  if (LOSS) {
+    if (threadIdx.x == 0) sNorm = loss_grad_norm(scal, batch, per, loss_type, objective);
+    __syncthreads();
+  }
+  const int64_t total = (int64_t)batch * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int b = (int)(i / per);
+    const float sg = scal[b * 4 + 3];
+    const float chain = objective == 0 ? scal[b * 4 + 2] : (objective == 1 ? -sg : 1.0f);
+    gf[i] = LOSS ? loss_grad_dF(sNorm, x0[i], data[i], objective == 1 ? noise[i] : 0.f, sg, chain, loss_type, objective)
+                 : chain * gy[i];
+  }
+}
+void launch_embed_cotangent(const float* x0, const float* data, const float* noise, const float* gy, const float* scal, float* gf,
+                            int batch, int64_t per, int loss_type, int objective, hipStream_t s) {
+  int64_t blocks = ((int64_t)batch * per + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (gy) hipLaunchKernelGGL(embed_cotangent_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x0, data, noise, gy, scal, gf, batch, per, loss_type, objective);
+  else hipLaunchKernelGGL(embed_cotangent_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x0, data, noise, gy, scal, gf, batch, per, loss_type, objective);
+  CD_HIP(hipGetLastError());
+}
+
 }  // namespace cd
 
 extern "C" {

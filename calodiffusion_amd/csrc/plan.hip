@@ -422,11 +422,39 @@ int cd_plan_status(CdPlan* plan, int* flags, void* stream) {
 int cd_plan_grad_layout(const CdPlan* plan, int idx, int64_t* offset, int64_t* total_floats) {
   return guarded([&] {
     CD_REQUIRE(plan, "null argument");
-    if (total_floats) *total_floats = (int64_t)plan->grad_floats;
+    const int nw = (int)plan->weights.size();
+    if (total_floats) *total_floats = (int64_t)(plan->grad_floats + 2 * plan->rad_grad_floats());
     if (offset) {
-      CD_REQUIRE(idx >= 0 && idx < (int)plan->weights.size(), "weight index out of range");
-      *offset = (int64_t)plan->weights[idx].grad_off;
+      CD_REQUIRE(idx >= 0 && idx < nw + (plan->rad.map ? 2 : 0), "weight index out of range");
+      *offset = idx < nw ? (int64_t)plan->weights[idx].grad_off
+                         : (int64_t)(idx == nw ? plan->enc_grad_off() : plan->dec_grad_off());
     }
+  });
+}
+
+int cd_plan_set_radial(CdPlan* plan, const CdRadialMap* map, const float* enc_w, const float* dec_w, int want_grads, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan, "null argument");
+    if (map) {  // refused before anything touches the device
+      CD_REQUIRE(enc_w && dec_w, "cd_plan_set_radial: a map needs enc_w and dec_w");
+      const CdUnetDesc& d = plan->desc;
+      if (map->layers != d.grid[0] || map->A != d.grid[1] || map->R != d.grid[2])
+        throw Fail{CD_EINVAL, "cd_plan_set_radial: the map's grid (L, alpha_out, r_out) = (" + std::to_string(map->layers) + ", " +
+                                  std::to_string(map->A) + ", " + std::to_string(map->R) + ") is not the plan's grid (" +
+                                  std::to_string(d.grid[0]) + ", " + std::to_string(d.grid[1]) + ", " + std::to_string(d.grid[2]) + ")"};
+    }
+    // A cached step graph holds the launches, the state size and the layout of the embedding it was captured with, and the kernels
+    // of an earlier call may still read the matrices.  Equal pointers do not mean an equal embedding (a freed map's or buffer's
+    // address may be handed out again for another geometry), so every call with a map, and every call that clears one, drops them.
+    if (map || plan->rad.map) {
+      CD_HIP(hipStreamSynchronize((hipStream_t)stream));
+      plan->ddim_graph.destroy();
+      plan->prog_graph.destroy();
+    }
+    plan->rad.map = map;
+    plan->rad.enc_w = map ? enc_w : nullptr;
+    plan->rad.dec_w = map ? dec_w : nullptr;
+    plan->rad.want_grads = map ? want_grads != 0 : true;
   });
 }
 

@@ -145,6 +145,17 @@ struct StepGraph {
 
 using namespace cd;
 
+// Layout of one Dataset-1 geometry (cd_radial_create, kernels_radial.hip)
+struct CdRadialMap {
+  int layers = 0, A = 0, R = 0, V = 0, wtotal = 0;
+  int4* lay = nullptr;  // device, per layer {bound, alpha, rin, float offset of its matrix}
+  int* vlay = nullptr;  // device, layer of every voxel
+  ~CdRadialMap() {
+    if (lay) (void)hipFree(lay);
+    if (vlay) (void)hipFree(vlay);
+  }
+};
+
 struct CdPlan {
   CdUnetDesc desc{};
   int nres = 0;
@@ -213,6 +224,19 @@ struct CdPlan {
   size_t grad_floats = 0;
   std::vector<LinearWgradJob> lin_jobs_host;
   LinearWgradJob* d_lin_jobs = nullptr;
+
+  // flat-state embedding (cd_plan_set_radial): the caller's map and its live matrices; map null = none.  With one, the state of
+  // every denoise-based entry point is (B, V) and the gradients of enc_w / dec_w follow the U-Net's in the flat gradient buffer
+  struct RadialEmbed {
+    const CdRadialMap* map = nullptr;
+    const float* enc_w = nullptr;
+    const float* dec_w = nullptr;
+    bool want_grads = true;
+  } rad;
+  int64_t state_per() const { return rad.map ? (int64_t)rad.map->V : shapes[0].vox(); }
+  size_t rad_grad_floats() const { return rad.map ? ((size_t)rad.map->wtotal + 63) & ~(size_t)63 : 0; }
+  size_t enc_grad_off() const { return grad_floats; }
+  size_t dec_grad_off() const { return grad_floats + rad_grad_floats(); }
 
   Arena ws;
 
@@ -306,6 +330,21 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
 EmbedArgs embed_args(CdPlan* p, int B, const float* cond, const float* t, int kind, float* emb, float* scal);
 void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const float* t, float* out, bool raw, hipStream_t s,
                   const FwdOpts* opt = nullptr);
+// kernels_radial.hip: the launches of a plan's flat-state embedding around its U-Net.  scal: (B, 4) of launch_embed
+// g (B, 1, L, A, R) = enc(c_in x)
+void launch_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s);
+// out (B, V) = the objective's combination of x and dec(F), as launch_head forms it on the grid; upd: its fused sampler update
+void launch_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
+                      float* out, const HeadArgs* upd, int batch, hipStream_t s);
+// gf (B, V), the cotangent of dec(F): from the loss (gy null; x0, data, noise) or from a caller's cotangent gy of the output
+void launch_embed_cotangent(const float* x0, const float* data, const float* noise, const float* gy, const float* scal, float* gf,
+                            int batch, int64_t per, int loss_type, int objective, hipStream_t s);
+// dF = dec's VJP of gf, and dd (nullable) = the gradient of dec_w
+void launch_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
+                          hipStream_t s);
+// dx = enc's VJP of dg (which carries c_in) plus, with gy, the preconditioning's direct x term; dw (nullable) = the gradient of enc_w
+void launch_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
+                          const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s);
 // plan.hip
 void check_ready(CdPlan* p, bool need_coords);
 // train.hip

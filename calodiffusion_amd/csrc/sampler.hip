@@ -55,7 +55,7 @@ int cd_ddim_sample(CdPlan* plan, int batch, const float* start, const float* con
     CD_REQUIRE(n_steps >= 1 && n_steps <= CdPlan::kMaxSteps, "n_steps out of range (1..4096)");
     check_ready(plan, true);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n = (int64_t)batch * plan->shapes[0].vox();
+    const int64_t n = (int64_t)batch * plan->state_per();
     bool noisy = false;
     for (int i = 0; i < n_steps; ++i) noisy |= steps[i].ddim_sigma != 0.f;
 
@@ -184,7 +184,7 @@ int cd_ddim_sample(CdPlan* plan, int batch, const float* start, const float* con
 // workspace of cd_sampler_run: the buffers, the coefficient table, sigma / Philox words, and the network's own
 static size_t sampler_front_bytes(CdPlan* plan, int batch, int n_bufs, size_t table_floats, float** bufs, float** table, float** sigma_b,
                                   uint64_t** noise_dev) {
-  const int64_t n = (int64_t)batch * plan->shapes[0].vox();
+  const int64_t n = (int64_t)batch * plan->state_per();
   for (int k = 1; k < n_bufs; ++k) {
     float* b = plan->ws.get<float>((size_t)n);
     if (bufs) bufs[k] = b;
@@ -216,7 +216,7 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
     CD_REQUIRE(n_bufs >= 2 && n_bufs <= 16 && n_steps >= 1 && n_steps <= 1 << 20 && n_ops >= 1 && n_coef >= 1, "bad program size");
     check_ready(plan, true);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n = (int64_t)batch * plan->shapes[0].vox();
+    const int64_t n = (int64_t)batch * plan->state_per();
     const bool uniform = op_begin == nullptr;
     if (!uniform) {
       CD_REQUIRE(op_begin[0] == 0 && op_begin[n_steps] == n_ops, "op_begin must run from 0 to n_ops");

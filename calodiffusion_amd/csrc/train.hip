@@ -436,6 +436,8 @@ struct TapedForward {
   const float* xn = nullptr;  // network input before c_in (data + sigma noise, or the caller's x)
   double* lpart = nullptr;    // training: the loss partials
   float* hf = nullptr;        // the head's input (the last ResnetBlock's output)
+  // flat-state embedding: g_in = enc(c_in xn), the head's raw output on the grid and the cotangent of dec's output, (B, V)
+  float *g_in = nullptr, *f_grid = nullptr, *gf = nullptr;
 };
 
 // Taped forward shared by cd_train_step (training: the input is data + sigma * noise, formed here) and cd_denoise_vjp (the
@@ -445,7 +447,8 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
   const CdUnetDesc& d = p->desc;
   const int B = r.B;
   const Dims3 dims = p->shapes[0];
-  const int64_t per = dims.vox(), n = (int64_t)B * per;
+  const CdRadialMap* rad = p->rad.map;
+  const int64_t per = p->state_per(), n = (int64_t)B * per;  // the state: the grid, or the flat shower of an embedding
   Arena* ws = r.ws;
   hipStream_t s = r.s;
   TrainTape& T = f.T;
@@ -460,9 +463,15 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
   }
   T.emb = ws->get<float>((size_t)B * p->emb_ld);
   T.scal = ws->get<float>((size_t)B * 4);
-  T.h0 = ws->get<float>((size_t)n * d.layer_sizes[0]);
+  T.h0 = ws->get<float>((size_t)B * dims.vox() * d.layer_sizes[0]);
+  if (rad) {
+    f.g_in = ws->get<float>((size_t)B * dims.vox());
+    f.f_grid = ws->get<float>((size_t)B * dims.vox());
+    f.gf = ws->get<float>((size_t)n);
+  }
   InitConvArgs& ia = f.ia;
-  ia.x = f.xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = T.scal; ia.scale_stride = 4; ia.use_rz = d.rz_input; ia.use_phi = d.phi_input;
+  ia.x = rad ? f.g_in : f.xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = rad ? nullptr : T.scal;  // (g_in carries c_in)
+  ia.scale_stride = 4; ia.use_rz = d.rz_input; ia.use_phi = d.phi_input;
   ia.r_w = p->d_coords; ia.z_d = p->d_coords + d.grid[2]; ia.phi_h = p->d_coords + d.grid[2] + d.grid[0];
   ia.wpk = p->packed(p->init_w); ia.bias = p->raw(p->init_b); ia.out = T.h0; ia.batch = B; ia.cout = d.layer_sizes[0]; ia.dims = dims;
   ia.coord_table = p->d_init_table; ia.table_ready = true; ia.status = r.status;
@@ -475,10 +484,20 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
     }
     if (training) launch_axpy_sigma(data, noise, sigma, xn, B, per, s);
     launch_embed(f.ea, s);
+    if (rad) launch_embed_in(rad, p->rad.enc_w, f.xn, T.scal, f.g_in, B, s);
     launch_init_conv(ia, s);
   }
   f.hf = unet_body_train(p, r, T.emb, T.h0, T);
 }
+
+struct BackwardState;
+// Flat-state embedding, the top of the backward pass: the cotangent gf of dec's output is in place; dec's VJP gives the head its
+// cotangent on the grid (and dec_w its gradient), the head's backward runs raw (no preconditioning: mean_pred's chain of 1)
+void embed_head_backward(CdPlan* p, Run& r, const TapedForward& f, const Grads& G, BackwardState& bs, float* hpart);
+// ... and its bottom: the init conv's input gradient on the grid (times c_in, no direct term), then enc's VJP: dx with the
+// preconditioning's direct x term (gy; null in training, whose input is data: dx is scratch there, and with frozen matrices
+// nothing is launched) and enc_w's gradient.  Consumes nothing.
+void embed_input_backward(CdPlan* p, Run& r, const TapedForward& f, const float* g, const float* gy, float* dx, const Grads& G);
 
 // State of one backward pass: the GroupNorm layers queue their parameter-gradient reductions (per-sample sums in `qsums`), one
 // launch flushes them at the end; the weight gradients queue the reductions of their per-workgroup partials (65 launches of 4-7 us
@@ -639,7 +658,8 @@ void finish_param_grads(CdPlan* p, Run& r, const TapedForward& f, float* g, cons
 void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, const float* sigma, const float* cond, double* loss_out,
                      float* grads, hipStream_t s, int loss_type = 0) {
   const CdUnetDesc& d = p->desc;
-  const int64_t per = p->shapes[0].vox();
+  const CdRadialMap* rad = p->rad.map;
+  const int64_t vox = p->shapes[0].vox(), per = p->state_per();
   Run r{&p->ws, s, B, d.groups};
   r.status = p->status_word;
   Grads G{p, grads};
@@ -648,21 +668,55 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   const TrainTape& T = f.T;
   if (!r.dry()) {
     HeadArgs ha;
-    ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = T.x0; ha.batch = B; ha.vox = per;
-    ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective;
+    ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = rad ? f.f_grid : T.x0; ha.batch = B; ha.vox = vox;
+    if (!rad) { ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective; }
     launch_head(ha, s);
+    if (rad) launch_embed_out(rad, p->rad.dec_w, f.f_grid, f.xn, T.scal, d.objective, T.x0, nullptr, B, s);
     launch_loss_partial(T.x0, data, noise, sigma, f.lpart, B, per, s, loss_type, d.objective);
     launch_loss_final(f.lpart, sigma, loss_out, B, per, s, loss_type, d.objective);
   }
   BackwardState bs;
   begin_backward(p, r, bs);
-  float* hpart = r.ws->get<float>((size_t)head_bwd_blocks(B, per) * 33);
-  if (!r.dry())
+  float* hpart = r.ws->get<float>((size_t)head_bwd_blocks(B, vox) * 33);
+  if (rad) {
+    if (!r.dry()) launch_embed_cotangent(T.x0, data, noise, nullptr, T.scal, f.gf, B, per, loss_type, d.objective, s);
+    embed_head_backward(p, r, f, G, bs, hpart);
+  } else if (!r.dry()) {
     launch_head_loss_bwd(T.x0, data, noise, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
                          loss_type, d.objective);
+  }
   float* g = body_backward(p, r, T, bs.g, G, bs.demb);
+  // the embedding's encoder: its weight gradient (the input is data: no input gradient is wanted, the row program's goes to gf)
+  if (rad) embed_input_backward(p, r, f, g, nullptr, f.gf, G);
   // init conv: weight and bias gradients only (its input is data)
   finish_param_grads(p, r, f, g, G, bs);
+}
+
+void embed_head_backward(CdPlan* p, Run& r, const TapedForward& f, const Grads& G, BackwardState& bs, float* hpart) {
+  const int B = r.B;
+  const int64_t vox = p->shapes[0].vox();
+  const bool want = r.param_grads && p->rad.want_grads && G.base;
+  float* dF = r.ws->get<float>((size_t)B * vox);
+  if (!r.dry()) {
+    launch_embed_dec_vjp(p->rad.map, p->rad.dec_w, f.f_grid, f.gf, dF, want ? G.base + p->dec_grad_off() : nullptr, B, r.s);
+    launch_head_vjp(dF, f.T.scal, f.hf, p->raw(p->head_w), bs.g, r.param_grads ? hpart : nullptr,
+                    r.param_grads ? G.at(p->head_w) : nullptr, r.param_grads ? G.at(p->head_b) : nullptr, B, vox, CD_OBJ_MEAN_PRED, r.s);
+  }
+  r.ws->release(dF);
+}
+
+void embed_input_backward(CdPlan* p, Run& r, const TapedForward& f, const float* g, const float* gy, float* dx, const Grads& G) {
+  const CdUnetDesc& d = p->desc;
+  const int B = r.B;
+  const Dims3 dims = p->shapes[0];
+  const bool want = r.param_grads && p->rad.want_grads && G.base;
+  float* dg = r.ws->get<float>((size_t)B * dims.vox());
+  if (!r.dry() && (gy || want)) {
+    launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], nullptr, f.T.scal, CD_OBJ_MEAN_PRED, dg, B, dims, r.s);
+    launch_embed_enc_vjp(p->rad.map, p->rad.enc_w, f.xn, dg, gy, f.T.scal, d.objective, dx, want ? G.base + p->enc_grad_off() : nullptr,
+                         B, r.s);
+  }
+  r.ws->release(dg);
 }
 
 // Vector-Jacobian product of cd_denoise: dx = (dD/dx)^T gy and, with grads, every parameter's gradient (the taped forward is
@@ -671,6 +725,7 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
 void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,
                       bool param_grads, hipStream_t s) {
   const CdUnetDesc& d = p->desc;
+  const CdRadialMap* rad = p->rad.map;
   const Dims3 dims = p->shapes[0];
   const int64_t per = dims.vox();
   Run r{&p->ws, s, B, d.groups};
@@ -683,12 +738,23 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
   BackwardState bs;
   begin_backward(p, r, bs);
   float* hpart = param_grads ? r.ws->get<float>((size_t)head_bwd_blocks(B, per) * 33) : nullptr;
-  if (!r.dry())
+  if (rad) {
+    if (!r.dry()) {
+      // the head's raw output on the grid, which dec_w's gradient pairs with the cotangent
+      HeadArgs ha;
+      ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = f.f_grid; ha.batch = B; ha.vox = per;
+      if (param_grads && p->rad.want_grads) launch_head(ha, s);
+      launch_embed_cotangent(nullptr, nullptr, nullptr, gy, T.scal, f.gf, B, p->state_per(), 0, d.objective, s);
+    }
+    embed_head_backward(p, r, f, G, bs, hpart);
+  } else if (!r.dry()) {
     launch_head_vjp(gy, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, param_grads ? G.at(p->head_w) : nullptr,
                     param_grads ? G.at(p->head_b) : nullptr, B, per, d.objective, s);
+  }
   float* g = body_backward(p, r, T, bs.g, G, bs.demb);
   // init conv: the data channel's input gradient, the preconditioning folded in (the coordinate channels are constants)
-  if (!r.dry())
+  if (rad) embed_input_backward(p, r, f, g, gy, dx, G);
+  else if (!r.dry())
     launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], gy, T.scal, d.objective, dx, B, dims, s);
   if (param_grads) {
     finish_param_grads(p, r, f, g, G, bs);

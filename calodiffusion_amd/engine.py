@@ -119,6 +119,7 @@ _SIGNATURES = {
     "cd_radial_dec": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "cd_radial_enc_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "cd_radial_dec_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "cd_plan_set_radial": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
@@ -267,6 +268,8 @@ class UnetEngine:
         self._weight_ids = None
         self._held_weights = []
         self._ws: Dict[tuple, torch.Tensor] = {}
+        self.embedding = None  # set_embedding: the NNConverter whose enc / dec run inside the denoise-based calls
+        self.state_shape = (1,) + self.grid  # per-sample state of those calls
         self.device = next(unet.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("move the model to the GPU first (model.to('cuda')): calodiffusion_amd has no CPU path")
@@ -294,10 +297,61 @@ class UnetEngine:
         ps = list(self.unet.parameters())
         return tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (tuple(id(p) for p in ps),)
 
+    # ------------------------------------------------------------------ flat-state embedding
+    def set_embedding(self, nn_embed):
+        """Bind a ``geom1.NNConverter`` (None: unbind) to the plan (cd_plan_set_radial): the state of denoise, the samplers, the
+        loss, train_step and denoise_vjp becomes the flat shower (B, V).  The per-layer ``encs[i].weight`` / ``decs[i].weight`` are
+        gathered into two device buffers the plan reads in place, refreshed whenever a weight changed (sync_weights)."""
+        self._grad_layout = None
+        self._ws, self._tws, self._vws = {}, {}, {}
+        self._embed_version = None
+        if nn_embed is None:
+            _check(self.lib.cd_plan_set_radial(self.plan, None, None, None, 0, _stream()))
+            self.embedding, self.state_shape = None, (1,) + self.grid
+            self._rmap = self._enc_flat = self._dec_flat = None
+            return
+        rmap = nn_embed.gc.radial_map()
+        if (rmap.L, rmap.A, rmap.R) != self.grid:
+            raise ValueError(f"the embedding maps onto the grid {(rmap.L, rmap.A, rmap.R)}, the U-Net runs on {self.grid}")
+        self._rmap = rmap  # (the plan reads the handle: kept alive here)
+        self._enc_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
+        self._dec_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
+        self.embedding, self.state_shape = nn_embed, (rmap.V,)
+        self._sync_embedding()
+
+    def _check_state(self, x, name, what="x"):
+        """The per-sample state is the grid, or with an embedding the flat shower: a tensor of the other form would be read and
+        written with the wrong size on the device."""
+        if tuple(x.shape[1:]) != self.state_shape:
+            raise ValueError(f"{name}: {what} has shape {tuple(x.shape)}, expected (B,) + {self.state_shape}")
+
+    def _embed_params(self):
+        return [lay.weight for lay in self.embedding.encs] + [lay.weight for lay in self.embedding.decs]
+
+    def embedding_trains(self) -> bool:
+        return self.embedding is not None and any(p.requires_grad for p in self._embed_params())
+
+    def _sync_embedding(self):
+        ps = self._embed_params()
+        ver = tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (self.embedding_trains(),)
+        if ver == self._embed_version:
+            return
+        n = len(self.embedding.encs)
+        torch.cat([p.detach().reshape(-1).to(device=self.device, dtype=torch.float32) for p in ps[:n]], out=self._enc_flat)
+        torch.cat([p.detach().reshape(-1).to(device=self.device, dtype=torch.float32) for p in ps[n:]], out=self._dec_flat)
+        # (the plan reads the two buffers in place: only a first binding or a change of the gradient flag is a call, which
+        # synchronises and drops the cached step graphs)
+        if self._embed_version is None or self._embed_version[-1] != ver[-1]:
+            _check(self.lib.cd_plan_set_radial(self.plan, self._rmap.handle, self._enc_flat.data_ptr(), self._dec_flat.data_ptr(),
+                                               int(ver[-1]), _stream()))
+        self._embed_version = ver
+
     def sync_weights(self, force=False):
         """(Re-)pack the parameters into the plan's arena; cheap no-op when nothing changed.  All tensors go in ONE C-ABI call
         (cd_plan_set_weights: two launches); the plan's tensor order and the Parameter objects behind it are looked up once (and
         again whenever a Parameter object of the module is replaced)."""
+        if self.embedding is not None:
+            self._sync_embedding()
         ver = self._version()
         if not force and ver == self._weights_version:
             return
@@ -380,8 +434,9 @@ class UnetEngine:
         sigma = _dev32(sigma, "sigma").reshape(-1)
         if sigma.numel() == 1 and B > 1:
             sigma = sigma.expand(B).contiguous()
-        if tuple(x.shape[1:]) != (1,) + self.grid or sigma.numel() != B or cond.shape != (B, self.unet.cond_size):
-            raise ValueError(f"denoise shapes: x {tuple(x.shape)}, sigma {tuple(sigma.shape)}, cond {tuple(cond.shape)}")
+        if tuple(x.shape[1:]) != self.state_shape or sigma.numel() != B or cond.shape != (B, self.unet.cond_size):
+            raise ValueError(f"denoise shapes: x {tuple(x.shape)} (expected (B,) + {self.state_shape}), sigma {tuple(sigma.shape)}, "
+                             f"cond {tuple(cond.shape)}")
         self.sync_weights()
         ws = self.workspace(B)
         out = torch.empty_like(x)
@@ -403,6 +458,7 @@ class UnetEngine:
         tensor size so that the union of the shards is the single-GPU result)."""
         start, cond = _dev32(start, "start"), _dev32(cond, "cond")
         B = start.shape[0]
+        self._check_state(start, "ddim_sample", "start")
         steps = np.ascontiguousarray(steps, dtype=np.float32)
         n_steps = steps.shape[0]
         assert steps.shape == (n_steps, 4)
@@ -428,6 +484,7 @@ class UnetEngine:
         Returns (x, xs, x0s); the trajectories (n_steps, B, 1, D, H, W) only when ``debug`` and the program records them."""
         start, cond = _dev32(start, "start"), _dev32(cond, "cond")
         B = start.shape[0]
+        self._check_state(start, "sampler_run", "start")
         coefs = np.ascontiguousarray(program.coefs, dtype=np.float32)
         n_steps, n_coef = coefs.shape
         ops = (CdSamplerOp * len(program.ops))()
@@ -490,6 +547,10 @@ class UnetEngine:
                 _check(self.lib.cd_plan_weight_name(self.plan, i, buf, 256, C.byref(numel)))
                 _check(self.lib.cd_plan_grad_layout(self.plan, i, C.byref(off), C.byref(total)))
                 lay[buf.value.decode()] = (off.value, numel.value)
+            if self.embedding is not None:  # the embedding's two blocks follow the U-Net's (cd_plan_set_radial)
+                for k, name in enumerate(("NN_embed.encs", "NN_embed.decs")):
+                    _check(self.lib.cd_plan_grad_layout(self.plan, n.value + k, C.byref(off), C.byref(total)))
+                    lay[name] = (off.value, self._rmap.wtotal)
             self._grad_layout = (lay, total.value)
         return self._grad_layout
 
@@ -508,6 +569,9 @@ class UnetEngine:
         data, noise, cond = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(cond, "cond")
         sigma = _dev32(sigma, "sigma").reshape(-1)
         B = data.shape[0]
+        self._check_state(data, "train_step", "data")
+        if noise.shape != data.shape or sigma.numel() != B:
+            raise ValueError(f"train_step: noise {tuple(noise.shape)} must have data's shape and sigma {tuple(sigma.shape)} B elements")
         self.sync_weights()
         ws = self.train_workspace(B)
         _, total = self.grad_layout()
@@ -537,7 +601,7 @@ class UnetEngine:
         sigma = _dev32(sigma, "sigma").reshape(-1)
         if sigma.numel() == 1 and B > 1:
             sigma = sigma.expand(B).contiguous()
-        if (tuple(x.shape[1:]) != (1,) + self.grid or gy.shape != x.shape or sigma.numel() != B
+        if (tuple(x.shape[1:]) != self.state_shape or gy.shape != x.shape or sigma.numel() != B
                 or cond.shape != (B, self.unet.cond_size)):
             raise ValueError(f"denoise_vjp shapes: x {tuple(x.shape)}, gy {tuple(gy.shape)}, sigma {tuple(sigma.shape)}, "
                              f"cond {tuple(cond.shape)}")
@@ -585,18 +649,28 @@ class UnetEngine:
         return loss, dtheta
 
     def param_grads(self, flat):
-        """Views of the flat gradient buffer, one per parameter of the bound CondUnet, in .parameters() order."""
+        """Views of the flat gradient buffer, one per parameter of the bound CondUnet, in .parameters() order; with an embedding,
+        its ``encs[i].weight`` and then its ``decs[i].weight`` follow (the order of ``NNConverter.parameters()``)."""
         lay, _ = self.grad_layout()
         out = []
         for name, p in self.unet.named_parameters():
             off, numel = lay[name]
             out.append(flat[off:off + numel].view(p.shape))
+        if self.embedding is not None:
+            for name, layers in (("NN_embed.encs", self.embedding.encs), ("NN_embed.decs", self.embedding.decs)):
+                off = lay[name][0]
+                for layer in layers:
+                    out.append(flat[off:off + layer.weight.numel()].view(layer.weight.shape))
+                    off += layer.weight.numel()
         return out
 
     def loss_hybrid(self, data, noise, sigma, cond, loss_type="l2"):
         data, noise, cond = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(cond, "cond")
         sigma = _dev32(sigma, "sigma").reshape(-1)
         B = data.shape[0]
+        self._check_state(data, "loss_hybrid", "data")
+        if noise.shape != data.shape or sigma.numel() != B:
+            raise ValueError(f"loss_hybrid: noise {tuple(noise.shape)} must have data's shape and sigma {tuple(sigma.shape)} B elements")
         self.sync_weights()
         ws = self.workspace(B)
         out = torch.empty((), dtype=torch.float64, device=data.device)

@@ -21,6 +21,12 @@ from .resnet import ResNet
 
 class LayerDiffusion(CaloDiffusion):
     def __init__(self, config, n_steps=400, loss_type="l2"):
+        from .configs import load_config
+        embed = load_config(config).get("SHOWER_EMBED", "")
+        if "NN" in embed and "orig" in embed and "pre-embed" not in embed:
+            raise NotImplementedError("LayerDiffusion over an in-model geometry embedding (SHOWER_EMBED 'orig-NN'): the two-stage "
+                                      "sampling and its layer-energy conditioning are not wired to the flat Dataset-1 state yet; "
+                                      "use CaloDiffusion for such a config")
         super().__init__(config, n_steps, loss_type)
         self.layer_loss = False
         sampler_algo = self.config.get("LAYER_SAMPLER", "DDim")

@@ -65,7 +65,7 @@ class Loss:
         name in CaloDiffusion.init_model as the reference's denoise branches on it, calodiffusion.py:156-169), so one call
         evaluates pred / target / weight of that class and, in training, every parameter gradient."""
         cond = model.cond_tensor(E, layers)
-        params = list(model.model.parameters())
+        params = model._params() if hasattr(model, "_params") else list(model.model.parameters())
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             # training: TrainDiffusion.training_loop calls loss.backward(); optimizer.step() on the result
             return _TrainStep.apply(model.engine(), self.loss_type, data, noise, sigma, cond, *params)

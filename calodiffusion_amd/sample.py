@@ -965,6 +965,9 @@ class BespokeNonStationary(Sample):
         running offset, which advances), or the step_sigma hook."""
         from .engine import randn
         self.check_embedding(model, self.config)
+        if getattr(model, "do_embed", False):
+            raise NotImplementedError("BespokeNonStationary: theta training on a model with an in-model geometry embedding "
+                                      "(SHOWER_EMBED 'orig-NN') is not provided: cd_bns_theta_grad runs its chain on the grid")
         eng = model.engine()
         if not hasattr(eng, "bns_theta_grad"):
             raise NotImplementedError("BespokeNonStationary: theta training on the layer stage is not provided (the "

@@ -414,6 +414,24 @@ int cd_radial_enc_vjp(const CdRadialMap* map, const float* w, const float* x, co
 int cd_radial_dec_vjp(const CdRadialMap* map, const float* d, const float* g, const float* gx, float* dg, float* dd /* nullable */,
                       int batch, void* stream);
 
+/* A plan's flat-state embedding: CaloDiffusion.forward with an NN_embed (calodiffusion/models/calodiffusion.py:86-98) runs enc
+ * before and dec after the U-Net, and the EDM preconditioning, the samplers and the loss act on the flat shower.  With a map
+ * set, the per-sample state of cd_denoise, cd_denoise_safe, cd_ddim_sample, cd_sampler_run, cd_loss_hybrid*, cd_train_step and
+ * cd_denoise_vjp (and their workspace queries) is V = bound[L] floats, shape (batch, V), instead of the grid:
+ *   denoise(x) = combine(x, dec(F(enc(c_in x))))   -- the scaling first, then enc; F on the grid; combine as CD_OBJ_* says.
+ * Two launches more per denoise: embed-in before the init conv (which then does not scale again) and embed-out after the head
+ * (dec, the combination and, in cd_ddim_sample, the fused sampler update).  enc_w / dec_w are DEVICE arrays in cd_radial_enc's /
+ * cd_radial_dec's layout, read in place by every later call (live parameters, as the map: both must outlive their use).
+ * want_grads: cd_train_step and cd_denoise_vjp (with grads) write their gradients behind the U-Net's in the flat gradient buffer --
+ * cd_plan_grad_layout then takes idx = cd_plan_num_weights for enc_w and + 1 for dec_w, and its total grows -- reduced as
+ * cd_radial_enc_vjp / cd_radial_dec_vjp reduce them; 0 (frozen matrices): those slots are not written and no reduction runs.
+ * Refused with CD_EINVAL before anything touches the device: a map whose (L, alpha_out, r_out) is not the plan's grid, a map
+ * without matrices.  map = NULL clears the embedding (the other arguments are ignored): every launch sequence is then the
+ * plan's own.  cd_unet_forward is the raw network either way; cd_bns_theta_grad refuses a plan with an embedding.  Every call with a
+ * map, or that clears one, synchronises `stream` and drops the cached step graphs; call cd_plan_grad_layout and the workspace queries after. */
+int cd_plan_set_radial(CdPlan* plan, const CdRadialMap* map /* nullable */, const float* enc_w, const float* dec_w, int want_grads,
+                       void* stream);
+
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
  * (calodiffusion/models/layerdiffusion.py:35-38, 114-132) samples the (B, D+1) {total, per-layer} energies with.
