@@ -290,7 +290,7 @@ void launch_gn_finalize(const float* part, int units, const float* gamma, const 
                         float* coef, int batch, int channels, int groups, int64_t vox, hipStream_t s,
                         float* stat_out = nullptr /* [B][G][2] = {mean, rstd}, kept for the backward pass */);
 
-// ---- backward (kernels_bwd.hip) ---------------------------------------------------------------------------------
+// ---- backward: weight gradients (kernels_wgrad.hip, kernels_wgrad16.hip) -------------------------------------------
 size_t wgrad_partial_floats(int64_t out_vox, int batch, bool per_sample, int A, int Bc, int T);
 // Deferred slot reductions of the weight gradients (training step).  Every launch_wgrad ends in a reduction of its per-workgroup
 // partials: ~28 MB read for a few hundred KB of dw whatever the level, 65 launches of 4-7 us per step.  Given a queue
@@ -300,7 +300,7 @@ size_t wgrad_partial_floats(int64_t out_vox, int batch, bool per_sample, int A, 
 struct WgradReduceJob {
   const float* partial;
   float* dw;
-  int A, Bc, T, nslots, flags /* 1 accumulate, 2 transposed_out */, b_total, b_off;
+  int A, Bc, T, nslots, b_total, b_off;
   unsigned first_block;
 };
 struct WgradReduceQueue {
@@ -319,21 +319,27 @@ struct WgradAux {
   const unsigned* gmax = nullptr;
   const unsigned* xmax = nullptr;
 };
-// dW[a][b][tap] (or [b][a][tap] if transposed_out) = sum_{n,o} g[n][o][a] * x[n][in(o,tap)][xoff + b]; see kernels_bwd.hip
-void launch_wgrad(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int kh, int kw,
-                  int sz, int sxy, int batch, bool per_sample, float* partial, float* dw, bool accumulate, bool transposed_out,
-                  hipStream_t s, int b_total = 0, int b_off = 0,
-                  // x is read through silu(coef[0] x + coef[1]) + coef[2] per (sample, channel) ([B][xld][4]): only where
-                  // wgrad_x_norm_supported() says so (the fp16-pipe 3x3x3 kernel)
-                  const float* xcoef = nullptr, const WgradAux& aux = WgradAux());
-bool wgrad_x_norm_supported(Dims3 dg, Dims3 dx, int kd, int kh, int kw, int sz, int sxy);
-// stride-1 3x3x3 weight gradient on the fp16 matrix pipe (kernels_wgrad16.hip); false = geometry not eligible
-bool wgrad_f16x2_eligible(Dims3 d);
-bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int xld, int xoff, Dims3 d, int batch, float* partial,
-                            const WgradAux& aux, int* nblk_out, hipStream_t s, const float* xcoef = nullptr);
-// the strided (KD, 4, 4) convs between the levels (and the transposed conv with the tensors' roles swapped): kernels_wgrad16.hip
-bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int sz,
-                                    int batch, float* partial, int max_slots, const WgradAux& aux, int* nblk_out, hipStream_t s);
+// dW[a][b][tap] = sum_{n,o} g[n][o][a] * x[n][in(o,tap)][xoff + b] in the torch layout (A, b_total, taps); see kernels_wgrad.hip.
+// For a transposed conv g is the layer's input and x the output gradient: geom is then that of the strided conv from x's grid to g's.
+struct WgradOp {
+  const float* g = nullptr;     // (B, geom.out.vox, A): the conv's output gradient
+  int A = 0;
+  const float* x = nullptr;     // (B, geom.in.vox, xld): the conv's input, Bc channels at offset xoff
+  int Bc = 0, xld = 0, xoff = 0;
+  ConvGeom geom{};              // in = x's grid, out = g's grid, taps and strides (sh serves both phi and r)
+  int batch = 0;
+  bool per_sample = false;      // no sum over the batch: dw is (B, A, Bc, taps) (the attention's context gradient)
+  float* partial = nullptr;     // wgrad_partial_floats floats
+  float* dw = nullptr;
+  int b_total = 0, b_off = 0;   // dw's b columns are a slice of a wider weight (a source of a channel concat); 0 = Bc, packed
+  // x is read through silu(coef[0] x + coef[1]) + coef[2] per (sample, channel) ([B][xld][4]): only where
+  // wgrad_x_norm_supported() says so (the fp16-pipe 3x3x3 kernel)
+  const float* xcoef = nullptr;
+  WgradAux aux;
+};
+void launch_wgrad(const WgradOp& op, hipStream_t s);
+bool wgrad_x_norm_supported(const ConvGeom& g);
+// ---- backward: everything else (kernels_{conv,gn,attn,head,init,embed}_bwd.hip) -------------------------------------
 void launch_strided_dgrad_naive(const float* dy, const float* w, float* dx, int batch, int cin, int cout, Dims3 din, Dims3 dout,
                                 int kd, int sz, hipStream_t s);
 void launch_softmax32(const float* qkv, float* qs, int64_t rows, hipStream_t s);
@@ -392,7 +398,7 @@ void launch_gn_backward(const float* dy, const float* h, const float* coef, cons
                         float* dgamma, float* dbeta, float* dadd, int dadd_ld, int batch, int channels, int64_t vox, int groups,
                         int silu, float* scratch, bool accumulate_params, hipStream_t s,
                         // (optional, round 4) the bias gradient of the conv that produced h, and sum_{b,v} dy per channel (the bias
-                        // gradient of a conv that adds into y): both fall out of the statistics pass, see kernels_bwd.hip
+                        // gradient of a conv that adds into y): both fall out of the statistics pass, see kernels_gn_bwd.hip
                         float* dbias = nullptr, float* dsumdy = nullptr,
                         // (optional) queue the batch reduction of the parameter gradients instead of launching it (training step)
                         GnParamQueue* queue = nullptr,

@@ -6,7 +6,7 @@
 //   training: L = sum_b w_b sum_i (pred - target)^2 / (mean(w) B D), seeded with dL/dF;   VJP: seeded with (dD/dF) gy
 // One workgroup per sample runs the forward with every pre-activation in LDS, then the explicit chain rule back to the per-layer
 // output deltas (for the VJP on through in_lay to dx) in the same launch.  With parameter gradients, inputs and deltas of the
-// 20 Linear layers go to a per-sample tape in HBM and linear_wgrad_kernel (kernels_bwd.hip) forms all weight / bias gradients
+// 20 Linear layers go to a per-sample tape in HBM and linear_wgrad_kernel (kernels_embed_bwd.hip) forms all weight / bias gradients
 // (sums over the batch, fixed order => deterministic) in one more launch; its job table is written by the taping kernel itself,
 // so nothing here copies from the host or synchronises.  Forward and backward are device functions shared by the kernels.
 #include "cd_common.h"

@@ -15,6 +15,7 @@
 //  * one partial [27][32][32] per workgroup, summed in a fixed order by wgrad_reduce_kernel (deterministic).
 #include "cd_common.h"
 #include "split16.h"
+#include "wgrad_internal.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -905,19 +906,19 @@ bool wgrad_f16x2_eligible(Dims3 d) {
   return d.d >= 1 && d.h * d.w >= min_pv && wgrad16_lds(d) <= 160 * 1024;
 }
 // returns false when the geometry does not fit (caller falls back to the fp32 kernels); `partial` sized by wgrad_partial_floats
-bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int xld, int xoff, Dims3 d, int batch, float* partial,
-                            const WgradAux& aux, int* nblk_out, hipStream_t s, const float* xcoef) {
+bool try_launch_wgrad_f16x2(const WgradOp& op, int* nblk_out, hipStream_t s) {
+  const Dims3 d = op.geom.out;
   if (!wgrad_f16x2_eligible(d)) return false;
   const size_t lds = wgrad16_lds(d);
   Wgrad16Args f;
-  f.xcoef = xcoef;
-  f.g = g; f.x = x; f.A = A; f.xld = xld; f.xoff = xoff; f.D = d.d; f.H = d.h; f.W = d.w;
+  f.xcoef = op.xcoef;
+  f.g = op.g; f.x = op.x; f.A = op.A; f.xld = op.xld; f.xoff = op.xoff; f.D = d.d; f.H = d.h; f.W = d.w;
   f.units_per_sample = (d.d + WG_NZ - 1) / WG_NZ;
-  f.total_units = f.units_per_sample * batch;
-  f.partial = partial; f.tilesB = Bc / 32;
+  f.total_units = f.units_per_sample * op.batch;
+  f.partial = op.partial; f.tilesB = op.Bc / 32;
   // max |dy|: the caller's word if it has one (conv_backward: the dx convolution of this very backward measured it)
-  f.gmax_bits = aux.gmax ? aux.gmax : launch_absmax_bits(g, (size_t)batch * d.vox() * A, aux.words, s);
-  const int tiles = (A / 32) * (Bc / 32);
+  f.gmax_bits = op.aux.gmax ? op.aux.gmax : launch_absmax_bits(op.g, (size_t)op.batch * d.vox() * op.A, op.aux.words, s);
+  const int tiles = (op.A / 32) * (op.Bc / 32);
   int nblk = 256 / tiles;
   if (nblk < 32) nblk = 32;
   {
@@ -927,19 +928,19 @@ bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int x
     static const bool no_ring = getenv("CD_NO_WGRAD_RING") != nullptr;
     if (!no_ring && wgrad_ring_geometry(d, &NZ, &rlds)) {
       WgradRingArgs r;
-      r.g = g; r.x = x; r.A = A; r.xld = xld; r.xoff = xoff; r.D = d.d; r.H = d.h; r.W = d.w;
+      r.g = op.g; r.x = op.x; r.A = op.A; r.xld = op.xld; r.xoff = op.xoff; r.D = d.d; r.H = d.h; r.W = d.w;
       r.NZ = NZ; r.S = 2 * NZ + 2;
       r.U = (d.d + NZ - 1) / NZ;
       int want = nblk;
       if (const char* e = getenv("CD_WGRAD_RING_NBLK")) want = atoi(e) > 0 ? atoi(e) : nblk;  // tests: few workgroups => long chunks, several per workgroup
       if (want > nblk) want = nblk;
-      int cps = want / batch;
+      int cps = want / op.batch;
       if (cps < 1) cps = 1;
       if (cps > r.U) cps = r.U;
       r.upc = (r.U + cps - 1) / cps;
       r.cps = (r.U + r.upc - 1) / r.upc;
-      r.total_chunks = r.cps * batch;
-      r.partial = partial; r.tilesB = Bc / 32; r.gmax_bits = f.gmax_bits; r.xcoef = xcoef;
+      r.total_chunks = r.cps * op.batch;
+      r.partial = op.partial; r.tilesB = op.Bc / 32; r.gmax_bits = f.gmax_bits; r.xcoef = op.xcoef;
       r.abl = getenv("CD_WGRAD_ABL") ? atoi(getenv("CD_WGRAD_ABL")) : 0;
       int rblk = want < r.total_chunks ? want : r.total_chunks;
       static bool ring_attr = false;
@@ -969,12 +970,13 @@ bool try_launch_wgrad_f16x2(const float* g, int A, const float* x, int Bc, int x
 }
 
 // Strided (KD, 4, 4) / stride (SZ, 2, 2) weight gradient on the fp16 pipe (wgrad_strided_f16x2_kernel).  dg = the coarse grid (g), dx
-// the fine grid (x).  max_slots: capacity of `partial` in [A x Bc x T]-float slots.  Returns false when it does not apply (the
-// caller runs the f32-MFMA kernel).
-bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float* x, int Bc, int xld, int xoff, Dims3 dx, int kd, int sz,
-                                    int batch, float* partial, int max_slots, const WgradAux& aux, int* nblk_out, hipStream_t s) {
+// the fine grid (x).  Returns false when it does not apply (the caller runs the f32-MFMA kernel).
+bool try_launch_wgrad_strided_f16x2(const WgradOp& op, int* nblk_out, hipStream_t s) {
+  const Dims3 dg = op.geom.out, dx = op.geom.in;
+  const int kd = op.geom.kd, sz = op.geom.sz;
+  const int max_slots = wgrad_chunks(dg.vox(), op.batch, false, op.A, op.Bc, kd * 16) * op.batch;  // capacity of `partial` in [A x Bc x T]-float slots
   static const bool off = getenv("CD_NO_WGRAD16") != nullptr || getenv("CD_NO_WGRAD16_STRIDED") != nullptr;
-  if (off || (kd != 3 && kd != 4) || dx.h < 2 || A % 32 || Bc % 32 || xld % 4 || xoff % 4) return false;
+  if (off || (kd != 3 && kd != 4) || dx.h < 2 || op.A % 32 || op.Bc % 32 || op.xld % 4 || op.xoff % 4) return false;
   // the coarse grid must be the strided conv's output of the fine one (padding 1 everywhere, circular in phi)
   if (dg.d != (dx.d + 2 - kd) / sz + 1 || dg.h != (dx.h - 2) / 2 + 1 || dg.w != (dx.w - 2) / 2 + 1) return false;
   const int PVo = dg.h * dg.w;
@@ -988,15 +990,15 @@ bool try_launch_wgrad_strided_f16x2(const float* g, int A, Dims3 dg, const float
     if (nz <= dg.d && lds_for(nz) <= 160 * 1024) { NZ = nz; break; }
   if (!NZ) return false;
   WgradS16Args f;
-  f.g = g; f.x = x; f.A = A; f.xld = xld; f.xoff = xoff;
+  f.g = op.g; f.x = op.x; f.A = op.A; f.xld = op.xld; f.xoff = op.xoff;
   f.Do = dg.d; f.Ho = dg.h; f.Wo = dg.w; f.Di = dx.d; f.Hi = dx.h; f.Wi = dx.w; f.KD = kd; f.SZ = sz; f.NZ = NZ;
   f.units_per_sample = (dg.d + NZ - 1) / NZ;
-  f.total_units = f.units_per_sample * batch;
-  f.partial = partial; f.tilesB = Bc / 32;
+  f.total_units = f.units_per_sample * op.batch;
+  f.partial = op.partial; f.tilesB = op.Bc / 32;
   // both operands are rescaled from their maxima; the one the caller's input-gradient conv already measured is re-used
-  f.gmax_bits = aux.gmax ? aux.gmax : launch_absmax_bits(g, (size_t)batch * dg.vox() * A, aux.words, s);
-  f.xmax_bits = aux.xmax ? aux.xmax : launch_absmax_bits(x, (size_t)batch * dx.vox() * xld, aux.words, s);
-  const int tiles = (A / 32) * (Bc / 32);
+  f.gmax_bits = op.aux.gmax ? op.aux.gmax : launch_absmax_bits(op.g, (size_t)op.batch * dg.vox() * op.A, op.aux.words, s);
+  f.xmax_bits = op.aux.xmax ? op.aux.xmax : launch_absmax_bits(op.x, (size_t)op.batch * dx.vox() * op.xld, op.aux.words, s);
+  const int tiles = (op.A / 32) * (op.Bc / 32);
   int nblk = 128 / tiles;  // x two tap groups = one round of the 256 CUs
   if (nblk < 16) nblk = 16;
   if (nblk > f.total_units) nblk = f.total_units;

@@ -1,5 +1,5 @@
-// Internal interface of the library's host units (plan.hip, forward.hip, sampler.hip, train.hip, ops.hip, misc_abi.hip): the
-// plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
+// Internal interface of the library's host units (plan.hip, forward.hip, conv_backward.hip, sampler.hip, train.hip, ops.hip,
+// misc_abi.hip): the plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
 // every C-ABI entry point runs in.  The public ABI is include/calodiff.h.
 #pragma once
 #include "../../include/calodiff.h"
@@ -321,12 +321,14 @@ float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1
 float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
                  float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr, float* h1_side = nullptr);
 float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpart = nullptr, int xunits = 0);
+// conv_backward.hip
 void bias_grad(Run& r, const float* dy, int C, int64_t vox, float* db);
 void conv_backward(Run& r, const float* x0, int c0, const float* x1, int c1, const float* w_raw, const float* dy, float* dx,
                    float* dw, float* db, int cout, const ConvGeom& g, const DgImg* img = nullptr, const float* xcoef = nullptr,
                    const float* dx_add = nullptr, int* dx_added = nullptr, const unsigned* dy_max = nullptr);
 void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const float* dy, float* dx, float* dw, float* db, int c,
                              Dims3 din, Dims3 dout, int kz, int sz, const DgImg* img = nullptr);
+// forward.hip
 EmbedArgs embed_args(CdPlan* p, int B, const float* cond, const float* t, int kind, float* emb, float* scal);
 void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const float* t, float* out, bool raw, hipStream_t s,
                   const FwdOpts* opt = nullptr);

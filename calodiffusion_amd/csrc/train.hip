@@ -228,6 +228,7 @@ float* unet_body_train(CdPlan* p, Run& r, const float* emb, float* h, TrainTape&
 }
 
 // ---- backward pieces ---------------------------------------------------------------------------------------------
+static ConvGeom conv1x1_geom(Dims3 d) { return ConvGeom{d, d, 1, 1, 1, 1, 1, 1}; }
 // returns the gradient of the (concatenated) block input: (B, vox, c0+c1); consumes nothing of the tape
 float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const Grads& G, float* demb) {
   Arena* ws = r.ws;
@@ -245,7 +246,7 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
   // a1 = silu(gn1(h1)) + emb was only ever formed inside conv2's LDS staging: the weight gradient re-forms it the same way while
   // it stages h1 (round 4; a gn_apply pass and a tensor per block before), or it is recomputed here for the kernels that cannot
   static const bool no_xnorm = getenv("CD_NO_WGRAD_XNORM") != nullptr;
-  const bool xnorm = !no_xnorm && wgrad_x_norm_supported(t.dims, t.dims, 3, 3, 3, 1, 1);
+  const bool xnorm = !no_xnorm && wgrad_x_norm_supported(g);
   float* a1 = (xnorm || !r.param_grads) ? nullptr : ws->get<float>((size_t)r.B * vox * C);
   if (!r.dry() && a1) launch_gn_apply(t.h1, a1, t.coef1, r.B, C, vox, 1, nullptr, nullptr, 0, nullptr, r.s);
   float* da1 = ws->get<float>((size_t)r.B * vox * C);
@@ -283,9 +284,12 @@ float* res_block_bwd(Run& r, CdPlan* p, const ResTape& t, const float* dy, const
     const int cs[2] = {t.c0, t.c1};
     for (int k = 0; k < 2 && cs[k] && r.param_grads; ++k) {
       float* part = r.wgrad_part(wgrad_partial_floats(vox, r.B, false, C, cs[k], 1));
-      if (!r.dry())
-        launch_wgrad(dy, C, t.dims, xs[k], cs[k], cs[k], 0, t.dims, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.rw), false, false, r.s, cin,
-                     k ? t.c0 : 0, nullptr, r.wgrad_aux());
+      if (!r.dry()) {
+        WgradOp op;
+        op.g = dy; op.A = C; op.x = xs[k]; op.Bc = cs[k]; op.xld = cs[k]; op.geom = conv1x1_geom(t.dims); op.batch = r.B;
+        op.partial = part; op.dw = G.at(W.rw); op.b_total = cin; op.b_off = k ? t.c0 : 0; op.aux = r.wgrad_aux();
+        launch_wgrad(op, r.s);
+      }
       r.release_wgrad_part(part);
     }
     if (wp) ws->release(wp);
@@ -323,8 +327,10 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
       PointwiseArgs a;
       a.in0 = qs; a.ld0 = 32; a.c0 = 32; a.wpk = pk; a.w_batch_stride = 1024; a.out = o; a.batch = r.B; a.cout = 32; a.vox = vox;
       launch_pointwise(a, r.s);
-      launch_wgrad(dy0, C, d1, o, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.ow), false, false, r.s, 0, 0, nullptr,
-                   r.wgrad_aux());
+      WgradOp op;
+      op.g = dy0; op.A = C; op.x = o; op.Bc = 32; op.xld = 32; op.geom = conv1x1_geom(d1); op.batch = r.B; op.partial = part;
+      op.dw = G.at(W.ow); op.aux = r.wgrad_aux();
+      launch_wgrad(op, r.s);
     }
   }
   if (pg) {
@@ -349,7 +355,10 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   float* dqkv = ws->get<float>((size_t)rows * 96);
   float* tmp = ws->get<float>((size_t)rows * 32);
   if (!r.dry()) {
-    launch_wgrad(qs, 32, d1, dO, 32, 32, 0, d1, 1, 1, 1, 1, 1, r.B, true, ppart, dctx, false, false, r.s);
+    WgradOp op;  // (per sample: not queued, no aux)
+    op.g = qs; op.A = 32; op.x = dO; op.Bc = 32; op.xld = 32; op.geom = conv1x1_geom(d1); op.batch = r.B; op.per_sample = true;
+    op.partial = ppart; op.dw = dctx;
+    launch_wgrad(op, r.s);
     // dqs[n][d] = sum_e scale*ctx[d][e] do[n][e]  -> W[co=d][ci=e] = scale*ctx[d][e]: the transposed image packed above
     PointwiseArgs a;
     a.in0 = dO; a.ld0 = 32; a.c0 = 32; a.wpk = pkT; a.w_batch_stride = 1024; a.out = tmp; a.batch = r.B; a.cout = 32; a.vox = vox;
@@ -385,8 +394,10 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   if (!r.dry()) {
     if (pg) {
       launch_gn_apply(t.x, xn, t.coefn, r.B, C, vox, 0, nullptr, nullptr, 0, nullptr, r.s);
-      launch_wgrad(dqkv, 96, d1, xn, C, C, 0, d1, 1, 1, 1, 1, 1, r.B, false, part, G.at(W.qkv), false, false, r.s, 0, 0, nullptr,
-                   r.wgrad_aux());
+      WgradOp op;
+      op.g = dqkv; op.A = 96; op.x = xn; op.Bc = C; op.xld = C; op.geom = conv1x1_geom(d1); op.batch = r.B; op.partial = part;
+      op.dw = G.at(W.qkv); op.aux = r.wgrad_aux();
+      launch_wgrad(op, r.s);
     }
     if (!iq.pk) launch_pack_weights(p->raw(W.qkv), wq, C, 96, 1, true, r.s);
     PointwiseArgs a;

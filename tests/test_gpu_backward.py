@@ -66,6 +66,29 @@ def test_conv_backward(ops):
     _conv_case(ops, 32, 32, (1, 2, 16, 9), (3, 3, 3), (1, 1, 1), gen, dy_scale=2e4)
 
 
+def test_conv_weight_gradient_ladder_rungs(ops):
+    """The rungs of launch_wgrad (kernels_wgrad.hip) below the fp16-pipe kernels, each at the smallest shape that selects it.  The
+    test cannot see which kernel ran; the guards, with 144-byte fp16 records and a plane of PV = H W voxels:
+      * fp16 pipe, stride 1 (wgrad_f16x2_eligible): PV >= 8 and (RP + 1 + 4 (H + 2)(W + 1)) 144 B <= 160 KiB, RP = 2 PV rounded up
+        to 16.  12 x 21: (513 + 1232) 144 = 251 280 B, 18 x 17: (625 + 1440) 144 = 297 360 B -- both too large; 2 x 3: PV = 6 < 8.
+      * fp32 flat (try_launch_wgrad_flat): R = 256 halved while R / 2 >= voxels, P = (R - 1) / PV + 4 planes, tile of
+        (32 R + 32 P PV + R) 4 B, R halved again down to 32 while that exceeds 150 KiB = 153 600 B.
+        12 x 21 (756 voxels): R = 256, P = 5: 195 072 B; R = 128, P = 4: 145 920 B -> taken.
+        2 x 3 (24 voxels): R = 32, P = 31 / 6 + 4 = 9: 11 136 B -> taken.
+        18 x 17 (612 voxels, P = 4 throughout): 190 464, 173 568, 165 120 and, at R = 32, 160 896 B -> declined: wgrad_kernel<3>,
+        5 chunks x 2 samples = 10 slots, single-level reduction (under 256 slots wgrad_prereduce_kernel is not launched: it and
+        wgrad_reduce_kernel's slot_step stay covered by the full-size training tests of test_gpu_grad_batch.py).
+      * fp16 pipe, strided (try_launch_wgrad_strided_f16x2): (RP + 1 + ((nz - 1) sz + kd)(H + 3)(W + 2)) 144 B <= 160 KiB for nz in
+        {4, 2, 1} coarse planes (nz <= coarse depth), RP = nz x coarse plane rounded up to 16.  Fine 3 x 18 x 17 -> coarse 2 x 9 x 8:
+        nz = 2: (145 + 5 x 399) 144 = 308 160 B, nz = 1: (81 + 3 x 399) 144 = 184 032 B -> declined: wgrad_kernel<4>, 48 taps."""
+    gen = torch.Generator().manual_seed(29)
+    _conv_case(ops, 32, 32, (2, 3, 12, 21), (3, 3, 3), (1, 1, 1), gen)            # fp32 flat, R = 128, P = 4 (HGCal's 252-voxel plane)
+    _conv_case(ops, 64, 32, (1, 3, 12, 21), (3, 3, 3), (1, 1, 1), gen, split=32)  # fp32 flat, concat: the second launch writes columns 32.. of dw
+    _conv_case(ops, 32, 32, (1, 4, 2, 3), (3, 3, 3), (1, 1, 1), gen)              # fp32 flat, R = 32, P = 9 (plane under the fp16 floor)
+    _conv_case(ops, 32, 32, (2, 2, 18, 17), (3, 3, 3), (1, 1, 1), gen)            # generic wgrad_kernel<3>: no 3x3x3 kernel holds a 306-voxel plane
+    _conv_case(ops, 32, 32, (1, 3, 18, 17), (3, 4, 4), (2, 2, 2), gen)            # generic wgrad_kernel<4>, 48 taps: strided fp16 image too large
+
+
 def test_pointwise_conv_weight_gradient_streaming_kernel(ops):
     """1x1x1 convs: dW comes from wgrad1x1_kernel (round 4): one, three (96 x 32), four (64 x 64) and nine (96 x 96: three tile groups)
     32 x 32 output tiles; row counts that are no multiple of a 128-row unit; more units than workgroups, so that a workgroup loops and
