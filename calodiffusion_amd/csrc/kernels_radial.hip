@@ -16,6 +16,12 @@
 // The weight gradients ride in the same launch, in the workgroups after the row ones: a workgroup owns kRadTile consecutive
 // elements of the concatenated gradient, its kRadSlices thread groups walk the showers b = slice, slice + kRadSlices, ... each in
 // ascending (b, a), and a fixed tree over the slices in LDS finishes the element.  No atomics, no workspace.
+//
+// Dataset-0/1 pre-processing (cd_preprocess_ds1 / cd_reverse_norm_ds1; preprocess_shower and ReverseNormCaloChall of the
+// reference, utils.py:315-436, 446-573) sits on the same layout.  Its grid form is the two row programs with the loader's
+// arithmetic in their staging and epilogue (Ds1Args::on): expand<ENC> scales the staged shower and ends in logit-norm, collapse<DEC>
+// stages reverse_logit and ends in the energy scaling and the read-out threshold.  Its flat form needs no matrices: two kernels of
+// their own over the ragged segments [bound[i], bound[i+1]), a shower in LDS and a wave per layer.
 #include "plan_internal.h"
 
 #include <vector>
@@ -30,6 +36,19 @@ constexpr int kRadMaxRow = 6144;      // floats of one staged shower, flat or on
 constexpr int kRadMaxRowBlocks = 1024;
 constexpr int kRadTile = 32, kRadSlices = kRadThreads / kRadTile;  // weight gradient: elements per workgroup, batch slices
 static_assert(kRadSlices == 8, "the tree below sums eight slices");
+
+// The loader's arithmetic around a shower (cd_preprocess_ds1 / cd_reverse_norm_ds1)
+struct Ds1Args {
+  int on;                 // the row programs: 0 = the plain map
+  int logE;
+  const float* energy;    // (batch) forward: raw incident energies; reverse: in physical units
+  float* layerE_out;      // forward, flat form: (batch, 1 + L), or null ('logit-norm')
+  const float* layerE_in; // reverse, flat form: (batch, 1 + L), or null
+  float* e_out;           // forward: (batch, 1)
+  int32_t* status;        // forward: 0, or 1 + the highest index of a shower without energy
+  float scale, max_deposit, emin, emax, ecut;
+  double logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std;
+};
 
 struct RadialArgs {
   const int4* lay;
@@ -51,6 +70,7 @@ struct RadialArgs {
   float* upd_x_next;
   float* upd_xs;
   float* upd_x0s;
+  Ds1Args pp;          // expand<ENC>: forward pre-processing around enc;  collapse<DEC>: reverse around dec
 };
 enum { kEpiNone = 0, kEpiDenoise = 1, kEpiDirect = 2 };
 
@@ -60,6 +80,47 @@ __device__ __forceinline__ float* rad_row(char* smem, int L, int wtotal) { retur
 
 __device__ __forceinline__ void rad_stage_layers(const RadialArgs& a, int4* lay_s) {
   for (int i = threadIdx.x; i < a.L; i += kRadThreads) lay_s[i] = a.lay[i];
+}
+
+// The voxel maps, written as kernels_misc.hip writes them (pre_voxel of preprocess_kernel, rev_logit of reverse_norm_kernel): the
+// grid forms are held bitwise equal to compositions with those kernels (tests/test_gpu_ds1_preprocess.py).
+constexpr float kDs1Alpha = 1e-6f;                        // utils.py:233-243; numpy rounds the python scalars to the
+constexpr float kDs1LogitScale = (float)(1.0 - 2.0 * 1e-6);  // array's float32 before it multiplies
+constexpr float kDs1LayerEps = 1e-6f;                     // utils.py:535
+
+__device__ __forceinline__ float ds1_pre_voxel(float q, float mean, float std) {
+  const float o = kDs1Alpha + kDs1LogitScale * q;
+  return (logf(o / (1.f - o)) - mean) / std;
+}
+// Where expf overflows (x > 88.7: an untrained model's samples reach it) the reference's exp / (1 + exp) is inf / inf, and in
+// layer mode that one NaN takes its whole layer along; here it is the logistic function's limit, 1.  Every other x: rev_logit's bits.
+__device__ __forceinline__ float ds1_rev_logit(float x, float alpha) {
+  const float ex = expf(x);
+  const float o = isinf(ex) ? 1.f : ex / (1.f + ex);
+  return (o - alpha) / (1.f - 2.f * alpha);
+}
+// logit of a masked array (float64, np.ma.log(o / (1 - o)).filled(0)): 0 where the argument is not positive or the log not finite
+__device__ __forceinline__ double ds1_logit64(double x) {
+#pragma clang fp contract(off)
+  const double o = 1e-6 + (1.0 - 2.0 * 1e-6) * x;
+  const double r = o / (1.0 - o);
+  const double lg = log(r);
+  return (r > 0.0 && isfinite(lg)) ? lg : 0.0;
+}
+// The incident energy of shower b in the loader's units, and its conditioning value (utils.py:290, 307-310: float32 quotient and
+// float32 log10, divided by the python float log10(emax / emin)).  False: no energy, reported through status.
+__device__ __forceinline__ bool ds1_energy(const Ds1Args& p, int b, float* e_scaled) {
+  const float e = p.energy[b] * p.scale;
+  if (!(e > 0.f) || isinf(e)) {  // uniform over the workgroup
+    if (threadIdx.x == 0) atomicMax(p.status, b + 1);
+    return false;
+  }
+  if (threadIdx.x == 0) {
+    if (p.logE) p.e_out[b] = (float)((double)(float)log10((double)(e / p.emin)) / log10((double)p.emax / (double)p.emin));
+    else p.e_out[b] = (e - p.emin) / (p.emax - p.emin);
+  }
+  *e_scaled = e;
+  return true;
 }
 
 // The matrices into LDS.  TRANSPOSE: a layer's (rows, cols) row-major matrix lands column-major; otherwise a straight copy.
@@ -142,7 +203,14 @@ __global__ void __launch_bounds__(kRadThreads) radial_expand_kernel(RadialArgs a
   const int AR = a.A * a.R, LAR = a.L * AR;
   for (int b = blockIdx.x; b < a.batch; b += a.row_blocks) {
     const float* in = a.in + (size_t)b * a.V;
-    if (ENC && a.scal) {  // embed-in: the scaling first, then the dot product (x * scales['c_in'], then NN_embed.enc)
+    float denom = 0.f;
+    int nonzero = 0;
+    if (ENC && a.pp.on) {  // the loader: x shower_scale first (utils.py:291), then convert (:331-333)
+      float e;
+      if (!ds1_energy(a.pp, b, &e)) continue;  // (before this pass's first barrier)
+      denom = a.pp.max_deposit * e;
+      for (int v = threadIdx.x; v < a.V; v += kRadThreads) row[v] = __fmul_rn(in[v], a.pp.scale);
+    } else if (ENC && a.scal) {  // embed-in: the scaling first, then the dot product (x * scales['c_in'], then NN_embed.enc)
       const float c_in = a.scal[(size_t)b * 4];
       for (int v = threadIdx.x; v < a.V; v += kRadThreads) row[v] = __fmul_rn(in[v], c_in);
     } else {
@@ -159,9 +227,19 @@ __global__ void __launch_bounds__(kRadThreads) radial_expand_kernel(RadialArgs a
       float acc = 0.f;
       for (int j = 0; j < ly.z; ++j) acc = fmaf(wk[j * a.R], xr[j], acc);
       if (ENC && one) acc = __fdiv_rn(acc, (float)a.A);
+      if (ENC && a.pp.on) {  // preprocess_kernel's 'logit-norm' on the grid value
+        const float q = acc / denom;
+        nonzero |= q != 0.f;
+        acc = ds1_pre_voxel(q, (float)a.pp.logit_mean, (float)a.pp.logit_std);
+      }
       out[o] = acc;
     }
-    __syncthreads();  // the row is consumed before the next one is staged
+    // the row is consumed before the next one is staged; a shower with no deposit at all is found here
+    if (ENC && a.pp.on) {
+      if (!__syncthreads_or(nonzero) && threadIdx.x == 0) atomicMax(a.pp.status, b + 1);
+    } else {
+      __syncthreads();
+    }
   }
 }
 
@@ -183,7 +261,12 @@ __global__ void __launch_bounds__(kRadThreads) radial_collapse_kernel(RadialArgs
   const int AR = a.A * a.R, LAR = a.L * AR;
   for (int b = blockIdx.x; b < a.batch; b += a.row_blocks) {
     const float* in = a.in + (size_t)b * LAR;
-    for (int o = threadIdx.x; o < LAR; o += kRadThreads) row[o] = in[o];
+    if (DEC && a.pp.on) {  // reverse_norm_kernel's stage 1 on the way in
+      const float mean = (float)a.pp.logit_mean, std = (float)a.pp.logit_std;
+      for (int o = threadIdx.x; o < LAR; o += kRadThreads) row[o] = ds1_rev_logit(in[o] * std + mean, kDs1Alpha);
+    } else {
+      for (int o = threadIdx.x; o < LAR; o += kRadThreads) row[o] = in[o];
+    }
     __syncthreads();
     float* out = a.out + (size_t)b * a.V;
     for (int v = threadIdx.x; v < a.V; v += kRadThreads) {
@@ -218,11 +301,133 @@ __global__ void __launch_bounds__(kRadThreads) radial_collapse_kernel(RadialArgs
         }
       } else if (a.epi == kEpiDirect) {  // init_dgrad_kernel's epilogue: res carries c_in already
         out[v] = a.objective == 2 ? res : fmaf(a.objective == 0 ? a.scal[b * 4 + 1] : 1.f, a.xflat[(size_t)b * a.V + v], res);
+      } else if (DEC && a.pp.on) {  // reverse_norm_kernel's last loop, without a layer factor
+        float d = res * a.pp.max_deposit * a.pp.energy[b];
+        if (a.pp.ecut > 0.f && d < a.pp.ecut) d = 0.f;
+        out[v] = d;
       } else {
         out[v] = res;
       }
     }
     __syncthreads();
+  }
+}
+
+// The flat form of preprocess_shower (orig_shape: utils.py:341-342, 358-410), include/calodiff.h "cd_preprocess_ds1".  LDS: the
+// layer table, L layer sums (fp64), q of one shower.
+__global__ void __launch_bounds__(kRadThreads) ds1_flat_forward_kernel(RadialArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char rad_smem[];
+  int4* lay_s = (int4*)rad_smem;
+  double* lsum = (double*)(lay_s + a.L);
+  float* q_s = (float*)(lsum + a.L);
+  const Ds1Args& p = a.pp;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  rad_stage_layers(a, lay_s);
+  __syncthreads();
+  for (int b = blockIdx.x; b < a.batch; b += a.row_blocks) {
+    float e;
+    if (!ds1_energy(p, b, &e)) continue;  // (before this pass's first barrier)
+    const float denom = p.max_deposit * e;
+    const float* in = a.in + (size_t)b * a.V;
+    float* out = a.out + (size_t)b * a.V;
+    for (int v = tid; v < a.V; v += kRadThreads) q_s[v] = (in[v] * p.scale) / denom;
+    __syncthreads();
+    if (p.layerE_out) {
+      for (int i = wave; i < a.L; i += kRadThreads / 64) {
+        const int4 ly = lay_s[i];
+        const float* seg = q_s + ly.x;
+        double acc = 0.0;
+        for (int k = lane; k < ly.y * ly.z; k += 64) acc += (double)seg[k];
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) lsum[i] = acc;
+      }
+      __syncthreads();
+      double total = 0.0;
+      for (int i = 0; i < a.L; ++i) total += lsum[i];  // every thread, layer order
+      if (!(total > 0.0)) {  // uniform: no deposit at all
+        if (tid == 0) atomicMax(p.status, b + 1);
+        __syncthreads();  // lsum is read before the next shower's sums land
+        continue;
+      }
+      // the reference holds the sums and their quotient in float32 (:372-380, 389); from there its masked arrays are float64
+      const float total32 = (float)total;
+      float* le = p.layerE_out + (size_t)b * (a.L + 1);
+      if (tid == 0) le[0] = (float)(((double)total32 - p.totalE_mean) / p.totalE_std);
+      for (int i = tid; i < a.L; i += kRadThreads) {
+        const float share = __fdiv_rn((float)lsum[i], total32);
+        le[1 + i] = (float)((ds1_logit64((double)share) - p.layers_mean) / p.layers_std);
+      }
+      for (int v = tid; v < a.V; v += kRadThreads) out[v] = (float)((ds1_logit64((double)q_s[v]) - p.logit_mean) / p.logit_std);
+      __syncthreads();
+    } else {
+      const float mean = (float)p.logit_mean, std = (float)p.logit_std;
+      int nonzero = 0;
+      for (int v = tid; v < a.V; v += kRadThreads) {
+        const float q = q_s[v];
+        nonzero |= q != 0.f;
+        out[v] = ds1_pre_voxel(q, mean, std);
+      }
+      if (!__syncthreads_or(nonzero) && tid == 0) atomicMax(p.status, b + 1);
+    }
+  }
+}
+
+// The flat form of ReverseNormCaloChall (utils.py:494-505, 520-560, 570-571), include/calodiff.h "cd_reverse_norm_ds1", in
+// reverse_norm_kernel's arithmetic.  LDS: the layer table, L layer energies, one shower.
+__global__ void __launch_bounds__(kRadThreads) ds1_flat_reverse_kernel(RadialArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char rad_smem[];
+  int4* lay_s = (int4*)rad_smem;
+  float* lay_e = (float*)(lay_s + a.L);
+  float* row = lay_e + a.L;
+  const Ds1Args& p = a.pp;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float mean = (float)p.logit_mean, std = (float)p.logit_std;
+  const float layers_mean = (float)p.layers_mean, layers_std = (float)p.layers_std;
+  rad_stage_layers(a, lay_s);
+  __syncthreads();
+  for (int b = blockIdx.x; b < a.batch; b += a.row_blocks) {
+    const float* in = a.in + (size_t)b * a.V;
+    float* out = a.out + (size_t)b * a.V;
+    const float en = p.energy[b];
+    if (p.layerE_in && wave == 0) {
+      // this shower's layer energies: reverse transform, normalise to the total deposited energy (utils.py:522-530); L <= 64
+      const float* le = p.layerE_in + (size_t)b * (a.L + 1);
+      const float r = lane < a.L ? ds1_rev_logit(le[1 + lane] * layers_std + layers_mean, kDs1Alpha) : 0.f;
+      float sum = r;
+      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+      const float total = le[0] * (float)p.totalE_std + (float)p.totalE_mean;
+      if (lane < a.L) lay_e[lane] = r / sum * total;
+    }
+    for (int v = tid; v < a.V; v += kRadThreads) {
+      float d = ds1_rev_logit(in[v] * std + mean, kDs1Alpha);
+      if (p.layerE_in) d = d < 0.f ? 0.f : d;
+      row[v] = d;
+    }
+    __syncthreads();
+    if (p.layerE_in) {
+      for (int i = wave; i < a.L; i += kRadThreads / 64) {  // a wave sums its segment, then rescales it
+        const int4 ly = lay_s[i];
+        const int n = ly.y * ly.z;
+        float prev = 0.f;
+        for (int k = lane; k < n; k += 64) prev += row[ly.x + k];
+        for (int o = 32; o > 0; o >>= 1) prev += __shfl_xor(prev, o);
+        const float layer_e = lay_e[i];
+        float fac = layer_e / (prev + 1e-10f);
+        if (layer_e < kDs1LayerEps || prev < kDs1LayerEps) fac = 1.f;
+        for (int k = lane; k < n; k += 64) {
+          float d = row[ly.x + k] * fac * p.max_deposit * en;
+          if (p.ecut > 0.f && d < p.ecut) d = 0.f;
+          out[ly.x + k] = d;
+        }
+      }
+    } else {
+      for (int v = tid; v < a.V; v += kRadThreads) {
+        float d = row[v] * p.max_deposit * en;
+        if (p.ecut > 0.f && d < p.ecut) d = 0.f;
+        out[v] = d;
+      }
+    }
+    __syncthreads();  // the row and the layer energies are consumed before the next shower's land
   }
 }
 
@@ -250,6 +455,23 @@ void radial_launch(RadialOp op, const CdRadialMap* m, const float* w, const floa
     case kDecVjp: hipLaunchKernelGGL(radial_expand_kernel<false>, grid, dim3(kRadThreads), smem, s, a); break;
   }
   CD_HIP(hipGetLastError());
+}
+
+// the flat forms: no matrices, LDS = the layer table, L sums (8 bytes cover both kernels' use) and one shower
+void ds1_flat_launch(bool forward, const CdRadialMap* m, const float* in, float* out, const Ds1Args& pp, int batch, hipStream_t s) {
+  RadialArgs a{};
+  a.lay = m->lay; a.in = in; a.out = out; a.L = m->layers; a.A = m->A; a.R = m->R; a.V = m->V; a.batch = batch;
+  a.row_blocks = batch < kRadMaxRowBlocks ? batch : kRadMaxRowBlocks;
+  a.pp = pp;
+  const size_t smem = (sizeof(int4) + sizeof(double)) * (size_t)m->layers + sizeof(float) * (size_t)m->V;
+  if (forward) hipLaunchKernelGGL(ds1_flat_forward_kernel, dim3((unsigned)a.row_blocks), dim3(kRadThreads), smem, s, a);
+  else hipLaunchKernelGGL(ds1_flat_reverse_kernel, dim3((unsigned)a.row_blocks), dim3(kRadThreads), smem, s, a);
+  CD_HIP(hipGetLastError());
+}
+
+void ds1_consts(Ds1Args* p, const double consts[6]) {
+  p->logit_mean = consts[0]; p->logit_std = consts[1]; p->totalE_mean = consts[2]; p->totalE_std = consts[3];
+  p->layers_mean = consts[4]; p->layers_std = consts[5];
 }
 
 }  // namespace
@@ -405,6 +627,54 @@ int cd_radial_dec_vjp(const CdRadialMap* map, const float* d, const float* g, co
     CD_REQUIRE(map && d && g && gx && dg, "cd_radial_dec_vjp: map, d, g, gx and dg must not be null");
     CD_REQUIRE(batch > 0, "cd_radial_dec_vjp: batch must be positive");
     radial_launch(kDecVjp, map, d, gx, dg, g, dd, batch, (hipStream_t)stream);
+  });
+}
+
+int cd_preprocess_ds1(const CdRadialMap* map, const float* conv_w, const float* showers, const float* energy, float* out,
+                      float* layerE, float* e_out, int32_t* status, int batch, const double consts[6], float max_deposit, float emin,
+                      float emax, int logE, float shower_scale, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(map && showers && energy && out && e_out && status && consts && batch > 0, "bad argument");
+    CD_REQUIRE(max_deposit > 0.f && shower_scale > 0.f && emax > emin && (!logE || emin > 0.f),
+               "cd_preprocess_ds1: max_deposit and shower_scale must be positive, emax > emin (> 0 with logE)");
+    CD_REQUIRE(consts[1] != 0.0 && consts[3] != 0.0 && consts[5] != 0.0, "cd_preprocess_ds1: the three std constants must not be 0");
+    CD_REQUIRE(!(conv_w && layerE),
+               "cd_preprocess_ds1: the grid form (conv_w) takes no layerE: the reference's own preprocess_shower fails on a "
+               "'layer' map after the geometry conversion");
+    hipStream_t s = (hipStream_t)stream;
+    Ds1Args p{};
+    p.on = 1; p.logE = logE ? 1 : 0; p.energy = energy; p.layerE_out = layerE; p.e_out = e_out; p.status = status;
+    p.scale = shower_scale; p.max_deposit = max_deposit; p.emin = emin; p.emax = emax;
+    ds1_consts(&p, consts);
+    CD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    if (conv_w) {
+      RadialArgs f{};
+      f.pp = p;
+      radial_launch(kEnc, map, conv_w, showers, out, nullptr, nullptr, batch, s, &f);
+    } else {
+      ds1_flat_launch(true, map, showers, out, p, batch, s);
+    }
+  });
+}
+
+int cd_reverse_norm_ds1(const CdRadialMap* map, const float* unconv_w, const float* voxels, const float* energy, const float* layerE,
+                        float* out, int batch, const double consts[6], float max_deposit, float ecut, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(map && voxels && energy && out && consts && batch > 0, "bad argument");
+    CD_REQUIRE(max_deposit > 0.f, "cd_reverse_norm_ds1: max_deposit must be positive");
+    CD_REQUIRE(!(unconv_w && layerE),
+               "cd_reverse_norm_ds1: the grid form (unconv_w) takes no layerE: the reference's own preprocess_shower fails on a "
+               "'layer' map after the geometry conversion, so there is nothing to invert");
+    Ds1Args p{};
+    p.on = 1; p.energy = energy; p.layerE_in = layerE; p.max_deposit = max_deposit; p.ecut = ecut;
+    ds1_consts(&p, consts);
+    if (unconv_w) {
+      RadialArgs f{};
+      f.pp = p;
+      radial_launch(kDec, map, unconv_w, voxels, out, nullptr, nullptr, batch, (hipStream_t)stream, &f);
+    } else {
+      ds1_flat_launch(false, map, voxels, out, p, batch, (hipStream_t)stream);
+    }
   });
 }
 

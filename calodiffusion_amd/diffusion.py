@@ -111,7 +111,8 @@ class Diffusion(torch.nn.Module, ABC):
         (e.g. the reference's own function for the geometry-converted datasets); ``reverse_norm=False`` returns the
         normalised-space showers.  ``geometry`` = an ``hgcal.HGCalConverter``: an HGCal config with a [layer-]logit-norm map
         ends in physical showers (batch, layers, cells) too, decoded on the device (``postprocess.ReverseNormHGCal``, with
-        ``sparse_decoding`` / ``sparse_per_batch``).
+        ``sparse_decoding`` / ``sparse_per_batch``).  ``geometry`` = a ``geom1.GeomConverter`` or ``NNConverter`` (typically
+        ``model.NN_embed``): a Dataset-0/1 config ends in physical showers shaped SHAPE_ORIG (``cd_reverse_norm_ds1``).
         """
         self._physical_form(reverse_norm, geometry)  # raises NOW, not after minutes of sampling, if there is no inverse pre-processing
         generated, energies, layers = [], [], []
@@ -146,6 +147,14 @@ class Diffusion(torch.nn.Module, ABC):
                     raise TypeError("generate(geometry=) takes an hgcal.HGCalConverter; pass any other decoder through "
                                     "reverse_norm=<callable>")
                 return "device"
+            if cfg.get("DATASET_NUM", 2) in (0, 1) and not self.hgcal and geometry is not None:
+                from .geom1 import GeomConverter, NNConverter
+                from .postprocess import refuse_uncovered_ds1
+                if not isinstance(geometry, (GeomConverter, NNConverter)):
+                    raise TypeError("generate(geometry=) on a Dataset-0/1 config takes a geom1.GeomConverter or NNConverter "
+                                    "(typically model.NN_embed)")
+                refuse_uncovered_ds1("generate()", cfg["SHOWERMAP"], "orig" in cfg.get("SHOWER_EMBED", ""))
+                return "device"
         # the reference always applies utils.ReverseNorm (diffusion.py:171-195): never hand back normalised-space showers
         # silently.  HGCal / Dataset-1 need geometry files outside this package: pass the reference's function.
         raise ValueError(
@@ -169,9 +178,10 @@ class Diffusion(torch.nn.Module, ABC):
                                               sparse_decoding=sparse_decoding, sparse_per_batch=sparse_per_batch)
         elif device_form:
             from .postprocess import ReverseNorm
+            ds1 = dict(geometry=geometry, orig_shape="orig" in cfg.get("SHOWER_EMBED", "")) if cfg.get("DATASET_NUM", 2) in (0, 1) else {}
             generated, energies = ReverseNorm(generated, energies, shape=cfg["SHAPE_FINAL"], config=cfg, emax=cfg["EMAX"],
                                               emin=cfg["EMIN"], layerE=layers, logE=cfg["logE"], max_deposit=cfg["MAXDEP"],
                                               showerMap=cfg["SHOWERMAP"], dataset_num=cfg.get("DATASET_NUM", 2),
-                                              ecut=float(cfg["ECUT"]))
+                                              ecut=float(cfg["ECUT"]), **ds1)
             generated = generated.reshape(cfg["SHAPE_ORIG"])
         return generated, np.reshape(energies, (energies.shape[0], -1))

@@ -119,6 +119,9 @@ _SIGNATURES = {
     "cd_radial_dec": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "cd_radial_enc_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "cd_radial_dec_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "cd_preprocess_ds1": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_float, C.c_float,
+                                    C.c_int, C.c_float, _P]),
+    "cd_reverse_norm_ds1": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_float, _P]),
     "cd_plan_set_radial": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),

@@ -3,8 +3,13 @@
 device (``cd_preprocess``).  The inverse of ``postprocess.ReverseNorm``, for the same configurations.
 
 Supported: ``dataset_num`` 2 / 3, ``showerMap`` 'layer-logit-norm' / 'logit-norm' (the shipped Dataset-2 / Dataset-3 configs),
-regular grid (``orig_shape=False``).  Dataset-0/1 (geometry conversion from the binning XML), ``orig_shape`` and the quantile /
-log / sqrt / scaled maps are not provided.  Reading the HDF5 file stays the caller's.
+regular grid (``orig_shape=False``).  The quantile / log / sqrt / scaled maps are not provided.  Reading the HDF5 file stays
+the caller's.
+
+Dataset 0 / 1 (the irregular CaloChallenge binning) have their own pair, ``preprocess_shower(..., binning_file, dataset_num=0|1)``
+and ``PreprocessDS1`` (on ``cd_preprocess_ds1`` over a ``geom1.GeomConverter``): the flat form (``orig_shape=True``, SHOWER_EMBED
+'orig...': both maps, layer energies over the ragged layer segments) and the grid form (``orig_shape=False``: ``convert`` inside
+the launch, 'logit-norm' only -- the reference's own function fails on a 'layer' map there).
 
 HGCal has its own pair, ``preprocess_hgcal_shower`` and ``PreprocessHGCal`` (``DataLoaderHGCal``, utils/HGCal_utils.py:20-164,
 on ``cd_preprocess_hgcal``): raw cells through the geometry map of an ``hgcal.HGCalConverter`` to a loader batch in one launch.
@@ -18,25 +23,22 @@ import numpy as np
 import torch
 
 from . import engine
-from .postprocess import DATASET_PARAMS
-
-SHOWER_MAPS = ("layer-logit-norm", "logit-norm")
+from .postprocess import (DATASET1_PARAMS, DATASET_PARAMS, SHOWER_MAPS, ds1_geometry, refuse_uncovered_ds1,  # noqa: F401
+                          refuse_uncovered_map)
 
 
 def _refuse_uncovered(who, showerMap, dataset_num, orig_shape):
-    if orig_shape:
-        raise NotImplementedError("%s: orig_shape=True (the irregular Dataset-0/1 binning) is not provided" % who)
     if dataset_num in (0, 1):
-        raise NotImplementedError("%s: dataset_num %r needs the geometry conversion from the binning XML (GeomConverter), which "
-                                  "is not provided; only the regular-grid datasets 2 and 3 are" % (who, dataset_num))
+        raise NotImplementedError("%s: dataset_num %r needs the irregular geometry of the binning XML: pass binning_file to "
+                                  "preprocess_shower, or use PreprocessDS1(config, geometry); without one only the regular-grid "
+                                  "datasets 2 and 3 are provided" % (who, dataset_num))
+    if orig_shape:
+        raise NotImplementedError("%s: orig_shape=True is the irregular Dataset-0/1 binning; dataset_num %r is not provided in it"
+                                  % (who, dataset_num))
     if dataset_num not in (2, 3):
         raise NotImplementedError("%s: no pre-processing for dataset_num %r (regular-grid datasets 2 and 3 only; HGCal's "
                                   "preprocess_hgcal_shower is not provided)" % (who, dataset_num))
-    if showerMap not in SHOWER_MAPS:
-        missing = [k for k in ("quantile", "scaled", "sqrt", "log") if k in showerMap.replace("logit", "")]
-        what = "the %s map" % missing[0] if missing else "this map"
-        raise NotImplementedError("%s: showerMap '%s' is not provided (%s is missing; %s only)"
-                                  % (who, showerMap, what, " / ".join(SHOWER_MAPS)))
+    refuse_uncovered_map(who, showerMap)
 
 
 def _device_f32(a, name):
@@ -79,12 +81,53 @@ def _run(shower, e, dims, showerMap, dataset_num, max_deposit, emin, emax, logE,
     return out, layerE, e_out
 
 
+def _run_ds1(shower, e, gc, grid_form, showerMap, dataset_num, max_deposit, emin, emax, logE, shower_scale):
+    """(data (B, V) or (B,1,L,A,R), layerE (B,1+L) or None, E (B,1)): device tensors, one cd_preprocess_ds1 call and one flag
+    read.  ``gc``: the geom1.GeomConverter; ``grid_form``: convert inside the launch."""
+    rm = gc.radial_map()
+    v = _device_f32(shower, "shower")
+    if v.dim() < 2 or v.numel() != v.shape[0] * rm.V:
+        raise ValueError("preprocess: showers of %s do not hold the geometry's %d voxels each" % (tuple(v.shape), rm.V))
+    B = v.shape[0]
+    if B == 0:
+        raise ValueError("preprocess: no showers")
+    en = _device_f32(e, "e").reshape(-1)
+    if en.numel() != B:
+        raise ValueError("preprocess: %d incident energies for %d showers" % (en.numel(), B))
+    c = DATASET1_PARAMS[dataset_num + (0 if grid_form else 10)]
+    out = torch.empty((B, 1, rm.L, rm.A, rm.R) if grid_form else (B, rm.V), dtype=torch.float32, device="cuda")
+    layerE = torch.empty((B, rm.L + 1), dtype=torch.float32, device="cuda") if "layer" in showerMap else None
+    e_out = torch.empty((B, 1), dtype=torch.float32, device="cuda")
+    status = torch.empty((1,), dtype=torch.int32, device="cuda")
+    w = gc._fixed_weights()[0] if grid_form else None
+    consts = (C.c_double * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
+    engine._check(engine.load_library().cd_preprocess_ds1(rm.handle, engine._ptr(w), v.data_ptr(), en.data_ptr(), out.data_ptr(),
+                                                          engine._ptr(layerE), e_out.data_ptr(), status.data_ptr(), B, consts,
+                                                          float(max_deposit), float(emin), float(emax), int(bool(logE)),
+                                                          float(shower_scale), engine._stream()))
+    bad = int(status.item())
+    if bad:
+        raise ValueError("preprocess: shower %d (the last such row of this call) has no energy -- incident energy <= 0 or no "
+                         "deposit at all; the reference's masked arrays return unspecified fill values there.  Drop such rows "
+                         "before the call" % (bad - 1))
+    return out, layerE, e_out
+
+
 def preprocess_shower(shower, e, shape, binning_file="", showerMap="log-norm", dataset_num=2, orig_shape=False, ecut=0,
                       max_deposit=2):
     """``utils.preprocess_shower`` (utils.py:315-436), same arguments and return values: (shower (B, D*H*W) float32 ndarray,
     layerE (B, 1+D) float32 ndarray or None).  ``shower`` and ``e`` are already in the loader's units (the reference's loader
     multiplies by shower_scale before this call); ``shape`` is the config's SHAPE_PAD, (-1, 1, D, H, W).  ``ecut`` only
-    matters to the quantile maps, which are not provided."""
+    matters to the quantile maps, which are not provided.
+
+    ``dataset_num`` 0 / 1 with a ``binning_file``: the geometry is read from it (pions / photons); returns (B, V) with
+    ``orig_shape=True`` and (B, L*A*R) -- the converted grid -- without, and layerE (B, 1 + L)."""
+    if dataset_num in (0, 1) and binning_file:
+        refuse_uncovered_ds1("preprocess_shower", showerMap, orig_shape)
+        gc = ds1_geometry("preprocess_shower", dataset_num, binning_file)
+        # the incident-energy map is not part of this function: emin / emax only have to be valid
+        out, layerE, _ = _run_ds1(shower, e, gc, not orig_shape, showerMap, dataset_num, max_deposit, 1.0, 2.0, False, 1.0)
+        return out.reshape(out.shape[0], -1).cpu().numpy(), None if layerE is None else layerE.cpu().numpy()
     _refuse_uncovered("preprocess_shower", showerMap, dataset_num, orig_shape)
     dims = tuple(shape)[-3:]
     # the incident-energy map is not part of this function: emin / emax only have to be valid
@@ -126,6 +169,48 @@ class Preprocess:
         return E, layers, data
 
 
+class PreprocessDS1:
+    """Raw CaloChallenge Dataset-0/1 showers -> one loader batch on the device: what ``DataLoaderCaloChall`` (utils.py:260-312)
+    does after reading the file, in one ``cd_preprocess_ds1`` call.  The peer of ``PreprocessHGCal``.
+
+    Built from the config keys EMAX, EMIN, logE, MAXDEP, SHOWERMAP, DATASET_NUM (0 pions, 1 photons), SHAPE_ORIG, SHAPE_FINAL and
+    SHOWER_EMBED: with 'orig' in it (the shipped configs) the flat form, ``data`` (B, V), the state of a model with an
+    ``NN_embed``; otherwise the grid form, ``data`` (B, 1, L, A, R), ``GeomConverter.convert`` inside the launch.  ``geometry`` is
+    a ``geom1.GeomConverter``, a ``geom1.NNConverter`` (its ``.gc`` gives the layout; the fixed area-weighted matrices convert,
+    as in the reference's loader) or None: built from BIN_FILE.  Called with ``showers`` (B, V) and ``incident_energies`` (B,) or
+    (B, 1), numpy arrays or tensors; returns device tensors ``(E (B, 1), layers (B, 1+L) or None, data)`` -- ready for
+    ``compute_loss(data, E, noise, layers)``."""
+
+    def __init__(self, config, geometry=None, shower_scale=0.001):
+        missing = [k for k in ("EMAX", "EMIN", "logE", "MAXDEP", "SHOWERMAP", "DATASET_NUM") if k not in config]
+        if missing:
+            raise ValueError("PreprocessDS1: the config lacks %s" % ", ".join(missing))
+        self.dataset_num, self.showerMap = config["DATASET_NUM"], config["SHOWERMAP"]
+        if self.dataset_num not in (0, 1):
+            raise NotImplementedError("PreprocessDS1: dataset_num %r is not an irregular CaloChallenge set (0 pions, 1 photons); "
+                                      "use Preprocess or PreprocessHGCal" % (self.dataset_num,))
+        self.grid_form = "orig" not in config.get("SHOWER_EMBED", "")
+        refuse_uncovered_ds1("PreprocessDS1", self.showerMap, not self.grid_form)
+        if geometry is None and not config.get("BIN_FILE"):
+            raise ValueError("PreprocessDS1: the config lacks BIN_FILE and no geometry was given")
+        self.geometry = gc = ds1_geometry("PreprocessDS1", self.dataset_num, config.get("BIN_FILE", ""), geometry)
+        bound, _, _ = gc.descriptor()
+        if "SHAPE_ORIG" in config and int(config["SHAPE_ORIG"][-1]) != bound[-1]:
+            raise ValueError("PreprocessDS1: the geometry has %d voxels, SHAPE_ORIG says %d" % (bound[-1], config["SHAPE_ORIG"][-1]))
+        have = (int(gc.num_layers), int(gc.alpha_out), int(gc.dim_r_out))
+        if "SHAPE_FINAL" in config and tuple(int(d) for d in config["SHAPE_FINAL"][-3:]) != have:
+            raise ValueError("PreprocessDS1: the geometry maps onto (layers, alpha_out, dim_r_out) = %s, SHAPE_FINAL says %s"
+                             % (have, tuple(config["SHAPE_FINAL"][-3:])))
+        self.emax, self.emin, self.logE = float(config["EMAX"]), float(config["EMIN"]), bool(config["logE"])
+        self.max_deposit = float(config["MAXDEP"])
+        self.shower_scale = float(shower_scale)
+
+    def __call__(self, showers, incident_energies):
+        data, layers, E = _run_ds1(showers, incident_energies, self.geometry, self.grid_form, self.showerMap, self.dataset_num,
+                                   self.max_deposit, self.emin, self.emax, self.logE, self.shower_scale)
+        return E, layers, data
+
+
 # ---- HGCal ---------------------------------------------------------------------------------------------------------------------
 HGCAL_SETS = (100, 101, 111, 120, 121)
 # the on-chip limits of cd_preprocess_hgcal's fused form (include/calodiff.h)
@@ -138,11 +223,7 @@ def _refuse_uncovered_hgcal(who, showerMap, dataset_num, orig_shape):
     if dataset_num not in HGCAL_SETS:
         raise NotImplementedError("%s: no HGCal constants for dataset_num %r (the HGCal sets are %s)"
                                   % (who, dataset_num, ", ".join(str(n) for n in HGCAL_SETS)))
-    if showerMap not in SHOWER_MAPS:
-        missing = [k for k in ("quantile", "scaled", "sqrt", "log") if k in showerMap.replace("logit", "")]
-        what = "the %s map" % missing[0] if missing else "this map"
-        raise NotImplementedError("%s: showerMap '%s' is not provided (%s is missing; %s only)"
-                                  % (who, showerMap, what, " / ".join(SHOWER_MAPS)))
+    refuse_uncovered_map(who, showerMap)
 
 
 def _run_hgcal(showers, gen_info, bins, showerMap, dataset_num, max_deposit, emin, emax, conv=None, max_cells=None,

@@ -414,6 +414,44 @@ int cd_radial_enc_vjp(const CdRadialMap* map, const float* w, const float* x, co
 int cd_radial_dec_vjp(const CdRadialMap* map, const float* d, const float* g, const float* gx, float* dg, float* dd /* nullable */,
                       int batch, void* stream);
 
+/* Dataset-0/1 forward pre-processing, raw showers to a loader batch: utils.preprocess_shower (calodiffusion/utils/utils.py:
+ * 315-436) and the incident-energy map of DataLoaderCaloChall (:290-312, shower_scale included) over the irregular layout of
+ * `map`, one launch.  showers (batch, V) and energy (batch) are raw, both multiplied by shower_scale first; e_out (batch, 1),
+ * status, shower_scale and the no-energy rule are cd_preprocess's: ONE device int32, zeroed by the call, then 1 + the highest
+ * index of a shower with e <= 0, NaN or inf, or without any deposit; an empty layer of a shower that has energy elsewhere is
+ * ordinary data.  consts = {logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std} (utils/consts.py:4-80).
+ *   conv_w == NULL  the flat form (orig_shape, :341-342, 369-380): out (batch, V) = (logit(q) - logit_mean) / logit_std,
+ *                   q = showers / (max_deposit e) in float32, logit's alpha 1e-6.  layerE (batch, 1 + L) or NULL: the sum of q
+ *                   over each ragged segment [bound[i], bound[i+1]) -- a wave per layer, lanes strided, a xor butterfly, in fp64
+ *                   -- and their total in layer order, both rounded to float32 as the reference holds them; then, as the
+ *                   reference's masked arrays promote to float64, layerE = {(total - totalE_mean) / totalE_std,
+ *                   (logit(layer / total) - layers_mean) / layers_std} and every voxel's logit and normalisation in fp64,
+ *                   rounded to float32 once.  Without layerE ('logit-norm') everything is float32, as cd_preprocess does it.
+ *   conv_w != NULL  the grid form (:331-333): conv_w holds GeomConverter.weight_mats in cd_radial_enc's layout, out is
+ *                   (batch, 1, L, A, R); layerE must be NULL (the reference's own preprocess_shower fails on a 'layer' map
+ *                   here).  The steps in the reference's order: cd_radial_enc's dot products on the scaled shower, the division
+ *                   by max_deposit e, logit-norm -- bitwise cd_radial_enc of the scaled showers into a temporary followed by
+ *                   cd_preprocess on dims {L, A, R}.
+ * A shower is staged in LDS once and has one owner workgroup, which walks showers blockIdx, blockIdx + grid, ...: a row's bits
+ * do not depend on the batch.  No atomics but the status word; nothing is allocated and the stream is not synchronised. */
+int cd_preprocess_ds1(const CdRadialMap* map, const float* conv_w /* nullable */, const float* showers, const float* energy,
+                      float* out, float* layerE /* nullable */, float* e_out, int32_t* status, int batch, const double consts[6],
+                      float max_deposit, float emin, float emax, int logE, float shower_scale, void* stream);
+/* Its inverse, utils.ReverseNormCaloChall (:446-573) for Dataset 0/1; energy (batch) in physical units as for cd_reverse_norm.
+ *   unconv_w == NULL  the flat form: voxels (batch, V); un-normalise and reverse_logit (alpha 1e-6); with layerE (batch, 1 + L)
+ *                     negatives are clamped to 0 and every ragged segment is rescaled to its layer energy, the factor 1 where
+ *                     the layer or the segment sum is below 1e-6 (:549-557); then x max_deposit x energy and the ecut threshold.
+ *   unconv_w != NULL  the grid form (:562-564): voxels (batch, 1, L, A, R), unconv_w holds GeomConverter.pinv_mats in
+ *                     cd_radial_dec's layout, layerE must be NULL; reverse_logit in the staging of cd_radial_dec's row program,
+ *                     its dot products, then x max_deposit x energy and ecut on the flat row; negatives are not clamped.
+ *                     Bitwise cd_reverse_norm_staged(stage 1), cd_radial_dec, cd_reverse_norm_staged(stage 2, dims {1, 1, V}).
+ * reverse_logit where float32 exp(x) overflows (x > 88.7) is the logistic function's limit 1; the reference's exp / (1 + exp) is
+ * inf / inf there, which in layer mode turns the whole layer into NaN.
+ * out (batch, V).  One launch, no atomics; nothing is allocated and the stream is not synchronised. */
+int cd_reverse_norm_ds1(const CdRadialMap* map, const float* unconv_w /* nullable */, const float* voxels, const float* energy,
+                        const float* layerE /* nullable */, float* out, int batch, const double consts[6], float max_deposit,
+                        float ecut, void* stream);
+
 /* A plan's flat-state embedding: CaloDiffusion.forward with an NN_embed (calodiffusion/models/calodiffusion.py:86-98) runs enc
  * before and dec after the U-Net, and the EDM preconditioning, the samplers and the loss act on the flat shower.  With a map
  * set, the per-sample state of cd_denoise, cd_denoise_safe, cd_ddim_sample, cd_sampler_run, cd_loss_hybrid*, cd_train_step and
