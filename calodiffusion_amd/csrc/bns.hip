@@ -11,6 +11,190 @@
 
 namespace cd {
 
+// ------------------------------------------------------------------------------------------------------------
+// The kernels.  theta (2, n_steps) device.  Every reduction runs over a grid whose size depends on the element count only, in
+// fp64, partials (2 * kBnsMaxBlocks doubles) summed by one block in index order: repeated calls are bitwise equal.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kBnsMaxBlocks = 1024;
+constexpr int kBnsThreads = 256;
+int bns_blocks(int64_t n) {
+  int64_t b = (n + 4 * kBnsThreads - 1) / (4 * kBnsThreads);
+  return (int)(b < 1 ? 1 : b > kBnsMaxBlocks ? kBnsMaxBlocks : b);
+}
+// sum of v over the block (every thread gets it); sh: kBnsThreads doubles
+__device__ double bns_block_sum(double v, double* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = kBnsThreads / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+}  // namespace
+
+// x_next = x * a_i + u * b_i as the reference writes it (two products and a sum, each rounded on its own)
+__global__ void __launch_bounds__(256) bns_step_kernel(float* __restrict__ x_next, const float* __restrict__ x,
+                                                       const float* __restrict__ u, const float* __restrict__ theta, int n_steps,
+                                                       int i, int64_t n) {
+#pragma clang fp contract(off)
+  const float a = theta[i], b = theta[n_steps + i];
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
+    const float xa = x[k] * a;
+    const float ub = u[k] * b;
+    x_next[k] = xa + ub;
+  }
+}
+static void launch_bns_step(float* x_next, const float* x, const float* u, const float* theta, int n_steps, int i, int64_t n,
+                            hipStream_t s) {
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(bns_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x_next, x, u, theta, n_steps, i, n);
+  CD_HIP(hipGetLastError());
+}
+
+// per-row maxima of data over its last axis (width w) and per-block partial sums of (data - x)^2
+__global__ void __launch_bounds__(kBnsThreads) bns_loss_partial_kernel(const float* __restrict__ data, const float* __restrict__ x,
+                                                                       int64_t n, int w, float* __restrict__ rowmax,
+                                                                       double* __restrict__ partial) {
+  __shared__ double sh[kBnsThreads];
+  double acc = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * kBnsThreads + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBnsThreads) {
+    const double d = (double)data[k] - (double)x[k];
+    acc += d * d;
+  }
+  const int64_t rows = n / w;
+  for (int64_t r = (int64_t)blockIdx.x * kBnsThreads + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kBnsThreads) {
+    const float* row = data + r * w;
+    float m = row[0];
+    for (int j = 1; j < w; ++j) m = fmaxf(m, row[j]);  // (torch.max propagates NaN; data is finite)
+    rowmax[r] = m;
+  }
+  const double t = bns_block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+// one block: mse, the loss (the reference's PSNR loss) and the seed coefficient scal[0] of g_N = scal[0] * (x_N - data)
+__global__ void __launch_bounds__(kBnsThreads) bns_loss_final_kernel(const double* __restrict__ partial, int nparts,
+                                                                     const float* __restrict__ rowmax, int64_t rows, int64_t n,
+                                                                     double* __restrict__ loss_out, float* __restrict__ scal) {
+  __shared__ double sh[kBnsThreads];
+  __shared__ double mse_s;
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += kBnsThreads) acc += partial[k];
+  const double sse = bns_block_sum(acc, sh);
+  if (threadIdx.x == 0) mse_s = sse / (double)n;
+  __syncthreads();
+  const double mse = mse_s;
+  if (mse == 0.0) {  // the reference returns the int 100 (on which its torch.mean raises): loss 100, zero gradient
+    if (threadIdx.x == 0) {
+      *loss_out = 100.0;
+      scal[0] = 0.f;
+    }
+    return;
+  }
+  const double root = sqrt(mse);
+  double lsum = 0.0;
+  int zero = 0;
+  for (int64_t r = threadIdx.x; r < rows; r += kBnsThreads) {
+    const double m = (double)rowmax[r];
+    lsum += 20.0 * log10(m / root);  // NaN for m < 0, -inf for m == 0
+    zero |= m == 0.0;
+  }
+  const double tot = bns_block_sum(lsum, sh);
+  const double any_zero = bns_block_sum((double)zero, sh);
+  if (threadIdx.x == 0) {
+    *loss_out = tot / (double)rows;
+    // d loss / d x_N = -20 / (ln 10 mse numel) (x_N - data); a zero maximum makes log10's backward 1/0 times a zero factor:
+    // torch's gradient is NaN everywhere
+    scal[0] = any_zero != 0.0 ? __builtin_nanf("") : (float)(-20.0 / (2.302585092994045684 * mse * (double)n));
+  }
+}
+static void launch_bns_loss(const float* data, const float* x_n, int64_t n, int w, float* rowmax, double* partial, double* loss_out,
+                            float* scal, hipStream_t s) {
+  const int nb = bns_blocks(n);
+  hipLaunchKernelGGL(bns_loss_partial_kernel, dim3(nb), dim3(kBnsThreads), 0, s, data, x_n, n, w, rowmax, partial);
+  CD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(bns_loss_final_kernel, dim3(1), dim3(kBnsThreads), 0, s, partial, nb, rowmax, n / w, n, loss_out, scal);
+  CD_HIP(hipGetLastError());
+}
+
+// g = scal[0] * (x_N - data)
+__global__ void __launch_bounds__(256) bns_seed_kernel(float* __restrict__ g, const float* __restrict__ x_n,
+                                                       const float* __restrict__ data, const float* __restrict__ scal, int64_t n) {
+  const float c = scal[0];
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) g[k] = c * (x_n[k] - data[k]);
+}
+static void launch_bns_seed(float* g, const float* x_n, const float* data, const float* scal, int64_t n, hipStream_t s) {
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(bns_seed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, x_n, data, scal, n);
+  CD_HIP(hipGetLastError());
+}
+
+// step i of the reverse chain, g = g_{i+1} on entry: partials of <g, x_i> and <g, U_i>; with `chain`, gy = b_i g (the denoiser's
+// upstream gradient) and g = a_i g (g_i once the VJP's dx is added)
+__global__ void __launch_bounds__(kBnsThreads) bns_dtheta_partial_kernel(float* __restrict__ g, const float* __restrict__ x,
+                                                                         const float* __restrict__ u, const float* __restrict__ theta,
+                                                                         int n_steps, int i, float* __restrict__ gy, int chain,
+                                                                         int64_t n, double* __restrict__ partial) {
+  __shared__ double sh[kBnsThreads];
+  const float a = theta[i], b = theta[n_steps + i];
+  double ax = 0.0, au = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * kBnsThreads + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBnsThreads) {
+    const float gv = g[k];
+    ax += (double)gv * (double)x[k];
+    au += (double)gv * (double)u[k];
+    if (chain) {
+      gy[k] = b * gv;
+      g[k] = a * gv;
+    }
+  }
+  const double tx = bns_block_sum(ax, sh);
+  const double tu = bns_block_sum(au, sh);
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = tx;
+    partial[2 * blockIdx.x + 1] = tu;
+  }
+}
+__global__ void __launch_bounds__(kBnsThreads) bns_dtheta_final_kernel(const double* __restrict__ partial, int nparts, int n_steps,
+                                                                       int i, float* __restrict__ dtheta) {
+  __shared__ double sh[kBnsThreads];
+  double ax = 0.0, au = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += kBnsThreads) {
+    ax += partial[2 * k];
+    au += partial[2 * k + 1];
+  }
+  const double tx = bns_block_sum(ax, sh);
+  const double tu = bns_block_sum(au, sh);
+  if (threadIdx.x == 0) {
+    dtheta[i] = (float)tx;
+    dtheta[n_steps + i] = (float)tu;
+  }
+}
+static void launch_bns_dtheta(float* g, const float* x, const float* u, const float* theta, int n_steps, int i, float* gy, bool chain,
+                              int64_t n, double* partial, float* dtheta, hipStream_t s) {
+  const int nb = bns_blocks(n);
+  hipLaunchKernelGGL(bns_dtheta_partial_kernel, dim3(nb), dim3(kBnsThreads), 0, s, g, x, u, theta, n_steps, i, gy, chain ? 1 : 0, n,
+                     partial);
+  CD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(bns_dtheta_final_kernel, dim3(1), dim3(kBnsThreads), 0, s, partial, nb, n_steps, i, dtheta);
+  CD_HIP(hipGetLastError());
+}
+
+// g += dx
+__global__ void __launch_bounds__(256) bns_accum_kernel(float* __restrict__ g, const float* __restrict__ dx, int64_t n) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) g[k] = g[k] + dx[k];
+}
+static void launch_bns_accum(float* g, const float* dx, int64_t n, hipStream_t s) {
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(bns_accum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, dx, n);
+  CD_HIP(hipGetLastError());
+}
+
 // The call's own blocks at the front of the workspace; the network (forward or VJP) gets the rest, reset for every use
 struct BnsFront {
   float* xs = nullptr;  // x_1 .. x_N

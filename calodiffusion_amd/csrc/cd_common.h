@@ -546,7 +546,7 @@ struct HeadArgs {
   const float* res = nullptr;
   // DDim.__call__'s update of the running sample (models/sample.py:88-107) in the same pass (needs x and scal): with
   // stepvals = {sigma, sigma_prev*[t>0], ddim_sigma, denom}:  x_next = x0 + sigma_prev (x - x0) / sigma + ddim_sigma noise / denom
-  // -- the arithmetic of launch_ddim_update, whose launch and pass over x / x0 it saves.  upd_x_next may alias x.
+  // -- in place of a launch and a pass over x / x0 of its own.  upd_x_next may alias x.
   const float* upd_stepvals = nullptr;  // null: no update
   const float* upd_noise = nullptr;
   float* upd_x_next = nullptr;
@@ -555,9 +555,6 @@ struct HeadArgs {
 };
 void launch_head(const HeadArgs& a, hipStream_t s);
 
-// x_next = x0 + sigma_prev*((x - x0)/sigma) + ddim_sigma*noise/denom, scalars read from stepvals[0..3]
-void launch_ddim_update(const float* x, const float* x0, const float* noise, const float* stepvals, float* x_next,
-                        float* xs_slot, float* x0s_slot, int64_t n, hipStream_t s);
 // stepvals <- table[*counter]; sigma_b[0..B) <- stepvals.sigma; (*counter)++.  chunk (optional): the step's slice of the
 // embeddings / scalings computed a chunk of steps ahead -- slot (*counter) % chunk_steps of emb_src / scal_src -> emb_dst / scal_dst
 struct StepChunk {
@@ -589,27 +586,12 @@ void launch_fill_from_table(float* dst, int count, const float* table, int ncol,
 // dst[b] = table[row][col + b], b < count (CD_SOP_DENOISE_PS: a sigma per sample)
 void launch_fill_row_from_table(float* dst, int count, const float* table, int ncol, int col, const int* step_counter,
                                 hipStream_t s);
-// out[i] = sum_k table[row][col + k] * src[k][i]   (nsrc <= 6; out may alias a source)
+// out[i] = sum_k table[row][col + k] * src[k][i]   (nsrc <= 6; out may alias a source); div (CD_SOP_LINDIV): every product and sum
+// rounded on its own, then divided by table[row][col + nsrc]
 void launch_lincomb(float* out, const float* const* src, int nsrc, const float* table, int ncol, int col, const int* step_counter,
-                    int64_t n, hipStream_t s);
-void launch_lincomb_div(float* out, const float* const* src, int nsrc, const float* table, int ncol, int col, const int* step_counter,
-                    int64_t n, hipStream_t s);
+                    int64_t n, bool div, hipStream_t s);
 // traj[(*step_counter - 1) * n + i] = src[i]
 void launch_record_step(float* traj, const float* src, const int* step_counter, int64_t n, hipStream_t s);
-// BespokeNonStationary theta gradient (cd_bns_theta_grad).  theta (2, n_steps) device; partial: 2 * kBnsMaxBlocks doubles.
-constexpr int kBnsMaxBlocks = 1024;
-// x_next = x * a_i + u * b_i (products and sum rounded on their own, as the reference's torch ops)
-void launch_bns_step(float* x_next, const float* x, const float* u, const float* theta, int n_steps, int i, int64_t n,
-                     hipStream_t s);
-// rowmax (n / w floats) = maxima of data over its last axis (width w); *loss_out = the reference's PSNR loss; scal[0] = the seed
-// coefficient of g_N = scal[0] * (x_N - data)
-void launch_bns_loss(const float* data, const float* x_n, int64_t n, int w, float* rowmax, double* partial, double* loss_out,
-                     float* scal, hipStream_t s);
-void launch_bns_seed(float* g, const float* x_n, const float* data, const float* scal, int64_t n, hipStream_t s);
-// dtheta[0][i] = <g, x>, dtheta[1][i] = <g, u>; with chain, gy = b_i g and g = a_i g
-void launch_bns_dtheta(float* g, const float* x, const float* u, const float* theta, int n_steps, int i, float* gy, bool chain,
-                       int64_t n, double* partial, float* dtheta, hipStream_t s);
-void launch_bns_accum(float* g, const float* dx, int64_t n, hipStream_t s);  // g += dx
 void launch_axpy_sigma(const float* data, const float* noise, const float* sigma_b, float* out, int batch, int64_t per,
                        hipStream_t s);
 // The training objectives of models/loss.py on top of the denoiser's output `out` (calodiffusion.py:161-169), objective =
@@ -656,37 +638,6 @@ void launch_loss_partial(const float* x0, const float* data, const float* noise,
                          int64_t per, hipStream_t s, int loss_type = 0, int objective = 0);
 void launch_loss_final(const double* partial, const float* sigma_b, double* loss, int batch, int64_t per, hipStream_t s,
                        int loss_type = 0, int objective = 0);
-void launch_transpose_to_cl(const float* ncdhw, float* ndhwc, int batch, int channels, int64_t vox, hipStream_t s);
-void launch_transpose_to_planar(const float* ndhwc, float* ncdhw, int batch, int channels, int64_t vox, hipStream_t s);
-
-struct ReverseNormArgs {
-  const float* voxels;  // (B, 1, D, H, W) normalised-space showers
-  const float* energy;  // (B) incident energies (physical units)
-  const float* layerE;  // (B, 1 + D) normalised {total, layers} or null
-  float* out;           // (B, D*H*W)
-  int batch, D, H, W, layer_mode;
-  float logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std, max_deposit, ecut;
-  // 0: everything (CaloChallenge regular grids); 1: un-normalise + inverse logit only; 2: layer renormalisation + scaling of
-  // already-decoded showers (the two halves of ReverseNormHGCal around its geometry decode, utils/HGCal_utils.py:167-292)
-  int stage = 0;
-  float alpha = 1e-6f;      // reverse_logit's alpha (utils.py:233: 1e-6; HGCal_utils.py:13: 1e-8)
-  float layer_eps = 1e-6f;  // "essentially zero" layer (utils.py:539-547: 1e-6; HGCal_utils.py:262-268: 1e-8)
-};
-void launch_reverse_norm(const ReverseNormArgs& a, hipStream_t s);
-
-// Forward pre-processing of raw showers (preprocess_shower + the incident-energy map of DataLoaderCaloChall,
-// calodiffusion/utils/utils.py:290-312, 315-436), the inverse of the above for the same regular-grid configurations
-struct PreprocessArgs {
-  const float* showers;  // (B, D*H*W) raw voxel energies
-  const float* energy;   // (B) raw incident energies, same unit as the showers
-  float* out;            // (B, 1, D, H, W) normalised-space showers
-  float* layerE;         // (B, 1 + D) normalised {total, layers}, or null: 'logit-norm'
-  float* e_out;          // (B, 1) conditioning energy
-  int32_t* status;       // 0, or 1 + the highest index of a shower without energy (see cd_preprocess)
-  int batch, D, H, W, layer_mode, logE;
-  float logit_mean, logit_std, totalE_mean, totalE_std, layers_mean, layers_std, max_deposit, emin, emax, scale;
-};
-void launch_preprocess(const PreprocessArgs& a, hipStream_t s);
 
 // LayerDiffusion's layer-energy MLP: raw forward (mode 0), EDM denoise (mode 1) or a whole sampler trajectory (mode 2)
 struct LayerMlpArgs {
@@ -757,17 +708,6 @@ void launch_layer_mlp_train(LayerMlpTrainArgs a, float* grads, double* loss_out,
 size_t layer_vjp_workspace_bytes(const LayerMlpTrainArgs& a, bool with_param_grads);
 // dx and, with grads, every parameter gradient from the caller's gy (cd_layer_denoise_vjp)
 void launch_layer_mlp_vjp(LayerMlpTrainArgs a, float* grads, void* workspace, hipStream_t s);
-
-// fused Adam over up to 48 tensors per launch (kernel-argument table)
-struct AdamChunk {
-  float* p[48];
-  const float* g[48];
-  float* m[48];
-  float* v[48];
-  int64_t n[48];
-};
-void launch_adam(const AdamChunk& c, int ntensors, int64_t max_numel, double lr, double beta1, double beta2, float eps,
-                 float weight_decay, int step, hipStream_t s);
 
 size_t init_wgrad_partial_floats(int batch, int64_t vox, int cin, int cout);
 void launch_init_wgrad(const InitConvArgs& a, const float* g, float* part, float* dw, hipStream_t s);

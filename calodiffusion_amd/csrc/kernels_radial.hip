@@ -82,7 +82,7 @@ __device__ __forceinline__ void rad_stage_layers(const RadialArgs& a, int4* lay_
   for (int i = threadIdx.x; i < a.L; i += kRadThreads) lay_s[i] = a.lay[i];
 }
 
-// The voxel maps, written as kernels_misc.hip writes them (pre_voxel of preprocess_kernel, rev_logit of reverse_norm_kernel): the
+// The voxel maps, written as kernels_preprocess.hip writes them (pre_voxel of preprocess_kernel, rev_logit of reverse_norm_kernel): the
 // grid forms are held bitwise equal to compositions with those kernels (tests/test_gpu_ds1_preprocess.py).
 constexpr float kDs1Alpha = 1e-6f;                        // utils.py:233-243; numpy rounds the python scalars to the
 constexpr float kDs1LogitScale = (float)(1.0 - 2.0 * 1e-6);  // array's float32 before it multiplies
@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(kRadThreads) radial_collapse_kernel(RadialArgs
         if (a.objective == 0) pred = a.scal[b * 4 + 1] * xv + a.scal[b * 4 + 2] * pred;
         else if (a.objective == 1) pred = xv - a.scal[b * 4 + 3] * pred;
         out[v] = pred;
-        if (a.upd_stepvals) {  // (ddim_update_kernel's arithmetic)
+        if (a.upd_stepvals) {  // (DDim.__call__'s update: HeadArgs::upd_*)
           const float sigma = a.upd_stepvals[0], sprev = a.upd_stepvals[1], dsig = a.upd_stepvals[2], denom = a.upd_stepvals[3];
           const float eps = (xv - pred) / sigma;
           float r = pred + sprev * eps;

@@ -2,6 +2,44 @@
 // passes) on caller-owned buffers, for the tests' layer-by-layer comparison with the reference.
 #include "plan_internal.h"
 
+namespace cd {
+
+// ------------------------------------------------------------------------------------------------------------
+// layout transposes (tests / generic unet_forward input only; the denoise path never transposes: its I/O has C = 1)
+// ------------------------------------------------------------------------------------------------------------
+__global__ void to_cl_kernel(const float* __restrict__ src, float* __restrict__ dst, int channels, int64_t vox) {
+  const int b = blockIdx.y;
+  const int64_t total = vox * channels;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % channels);
+    const int64_t v = i / channels;
+    dst[(size_t)b * total + i] = src[(size_t)b * total + (size_t)c * vox + v];
+  }
+}
+__global__ void to_planar_kernel(const float* __restrict__ src, float* __restrict__ dst, int channels, int64_t vox) {
+  const int b = blockIdx.y;
+  const int64_t total = vox * channels;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t v = i % vox;
+    const int c = (int)(i / vox);
+    dst[(size_t)b * total + i] = src[(size_t)b * total + (size_t)v * channels + c];
+  }
+}
+static void launch_transpose_to_cl(const float* ncdhw, float* ndhwc, int batch, int channels, int64_t vox, hipStream_t s) {
+  int64_t bx = (vox * channels + 255) / 256;
+  if (bx > 1024) bx = 1024;
+  hipLaunchKernelGGL(to_cl_kernel, dim3((unsigned)bx, batch), dim3(256), 0, s, ncdhw, ndhwc, channels, vox);
+  CD_HIP(hipGetLastError());
+}
+static void launch_transpose_to_planar(const float* ndhwc, float* ncdhw, int batch, int channels, int64_t vox, hipStream_t s) {
+  int64_t bx = (vox * channels + 255) / 256;
+  if (bx > 1024) bx = 1024;
+  hipLaunchKernelGGL(to_planar_kernel, dim3((unsigned)bx, batch), dim3(256), 0, s, ndhwc, ncdhw, channels, vox);
+  CD_HIP(hipGetLastError());
+}
+
+}  // namespace cd
+
 extern "C" {
 
 // the zeroed max-|x| words of a primitive's convolution backward, from its own workspace (at most two measured tensors per source)

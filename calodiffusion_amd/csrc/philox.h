@@ -1,4 +1,4 @@
-// Philox4x32-10 + Box-Muller unit normals, shared by cd_randn (kernels_misc.hip) and the layer model's sampler programs
+// Philox4x32-10 + Box-Muller unit normals, shared by cd_randn (kernels_sampler.hip) and the layer model's sampler programs
 // (kernels_mlp.hip).  Element g of a stream is a pure function of (seed, g): counter = g / 4, lane = g % 4, so batch shards on
 // different GPUs draw disjoint slices of one stream.
 // (The reference's torch.randn CPU stream (mt19937) cannot be reproduced on device; parity tests pass noise in.)

@@ -272,6 +272,20 @@ int cd_device_check(char* name, int cap) {
   });
 }
 
+int cd_set_conv_precision(const char* mode) {
+  return guarded([&] {
+    CD_REQUIRE(mode, "null argument");
+    if (!std::strcmp(mode, "f16x2")) set_conv_precision(PREC_F16X2);
+    else if (!std::strcmp(mode, "bf16x3")) set_conv_precision(PREC_BF16X3);
+    else if (!std::strcmp(mode, "f32")) set_conv_precision(PREC_F32);
+    else throw Fail{CD_EINVAL, std::string("unknown convolution precision '") + mode + "' (f16x2, bf16x3, f32)"};
+  });
+}
+const char* cd_get_conv_precision(void) {
+  static const char* names[3] = {"f16x2", "bf16x3", "f32"};
+  return names[conv_precision()];
+}
+
 int cd_plan_create(const CdUnetDesc* desc, CdPlan** plan) {
   return guarded([&] {
     CD_REQUIRE(desc && plan, "null argument");

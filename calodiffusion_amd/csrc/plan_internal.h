@@ -1,5 +1,5 @@
 // Internal interface of the library's host units (plan.hip, forward.hip, conv_backward.hip, sampler.hip, train.hip, ops.hip,
-// misc_abi.hip): the plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
+// bns.hip, layer.hip and the entry points that share a file with their kernels): the plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
 // every C-ABI entry point runs in.  The public ABI is include/calodiff.h.
 #pragma once
 #include "../../include/calodiff.h"
@@ -349,6 +349,13 @@ void launch_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float*
                           const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s);
 // plan.hip
 void check_ready(CdPlan* p, bool need_coords);
+// sampler.hip: the one check of a step program (host arrays; op_begin null = uniform), for cd_sampler_run and cd_layer_sampler_run
+struct SamplerProgramCounts {
+  int randn_per_step = 0;  // RANDN ops in the op list
+  int64_t n_denoise = 0;   // DENOISE ops the program executes
+};
+SamplerProgramCounts validate_sampler_program(const CdSamplerOp* ops, const int32_t* op_begin, int n_steps, int n_ops, int n_bufs,
+                                              int n_coef, int batch);
 // train.hip
 void dgrad_images(CdPlan* p);  // lays out the input-gradient weight images once per plan (before any backward pass)
 void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,

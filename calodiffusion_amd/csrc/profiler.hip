@@ -1,6 +1,6 @@
 // Per-launch timing with HIP events on the launch stream (used by bench.py to price the dominant kernel live, in the
 // same process and on the same shapes as the timed run).  Disabled by default; never active during graph capture.
-#include "cd_common.h"
+#include "plan_internal.h"
 
 #include <cstdio>
 #include <map>
@@ -81,3 +81,17 @@ int end(char* buf, int cap) {
 
 }  // namespace prof
 }  // namespace cd
+
+extern "C" {
+
+int cd_profile_begin(void) {
+  return guarded([&] { prof::begin(); });
+}
+int cd_profile_end(char* json, int cap) {
+  return guarded([&] {
+    CD_REQUIRE(json && cap > 2, "bad argument");
+    if (prof::end(json, cap) < 0) throw Fail{CD_EINVAL, "profile buffer too small"};
+  });
+}
+
+}  // extern "C"

@@ -36,6 +36,36 @@ void upload_noise_words(uint64_t* noise_dev, uint64_t seed, uint64_t offset, uin
   CD_HIP(hipStreamSynchronize(s));
 }
 
+// A sampler step program is checked on the host before anything is enqueued: a bad buffer index would be a wild device pointer
+// (cd_sampler_run) or address outside the on-chip buffers (cd_layer_sampler_run).  The callers have checked the sizes.
+SamplerProgramCounts validate_sampler_program(const CdSamplerOp* ops, const int32_t* op_begin, int n_steps, int n_ops, int n_bufs,
+                                              int n_coef, int batch) {
+  if (op_begin) {
+    CD_REQUIRE(op_begin[0] == 0 && op_begin[n_steps] == n_ops, "op_begin must run from 0 to n_ops");
+    for (int i = 0; i < n_steps; ++i) CD_REQUIRE(op_begin[i] <= op_begin[i + 1], "op_begin must be non-decreasing");
+  }
+  SamplerProgramCounts c;
+  for (int k = 0; k < n_ops; ++k) {
+    const CdSamplerOp& o = ops[k];
+    CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_DENOISE_PS, "sampler op: unknown kind");
+    const bool lin = o.kind == CD_SOP_LINCOMB || o.kind == CD_SOP_LINDIV;
+    const int ns = lin ? o.nsrc : (o.kind == CD_SOP_RANDN ? 0 : 1);
+    CD_REQUIRE(ns >= 0 && ns <= 6 && (!lin || ns >= 1), "sampler op: 1..6 sources");
+    for (int j = 0; j < ns; ++j) CD_REQUIRE(o.src[j] >= 0 && o.src[j] < n_bufs, "sampler op: source buffer out of range");
+    if (o.kind == CD_SOP_RECORD) CD_REQUIRE(o.dst == 0 || o.dst == 1, "record op: dst is 0 (xs) or 1 (x0s)");
+    else CD_REQUIRE(o.dst >= 0 && o.dst < n_bufs, "sampler op: destination buffer out of range");
+    if (lin) CD_REQUIRE(o.col >= 0 && o.col + ns + (o.kind == CD_SOP_LINDIV ? 1 : 0) <= n_coef, "lincomb op: coefficient columns out of range");
+    if (o.kind == CD_SOP_DENOISE || o.kind == CD_SOP_DENOISE_PS) {
+      if (o.kind == CD_SOP_DENOISE) CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
+      else CD_REQUIRE(o.col >= 0 && o.col + batch <= n_coef, "per-sample denoise op: sigma columns out of range (col + batch > n_coef)");
+      CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
+      c.n_denoise += op_begin ? 1 : n_steps;  // once per step of a uniform program, once otherwise
+    }
+    if (o.kind == CD_SOP_RANDN) ++c.randn_per_step;
+  }
+  return c;
+}
+
 }  // namespace cd
 
 extern "C" {
@@ -218,32 +248,7 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = (int64_t)batch * plan->state_per();
     const bool uniform = op_begin == nullptr;
-    if (!uniform) {
-      CD_REQUIRE(op_begin[0] == 0 && op_begin[n_steps] == n_ops, "op_begin must run from 0 to n_ops");
-      for (int i = 0; i < n_steps; ++i) CD_REQUIRE(op_begin[i] <= op_begin[i + 1], "op_begin must be non-decreasing");
-    }
-    // validate the program before anything is enqueued: a bad buffer index would be a wild device pointer
-    int randn_per_step = 0;
-    for (int k = 0; k < n_ops; ++k) {
-      const CdSamplerOp& o = ops[k];
-      CD_REQUIRE(o.kind >= CD_SOP_LINCOMB && o.kind <= CD_SOP_DENOISE_PS, "sampler op: unknown kind");
-      const bool lin = o.kind == CD_SOP_LINCOMB || o.kind == CD_SOP_LINDIV;
-      const int ns = lin ? o.nsrc : (o.kind == CD_SOP_RANDN ? 0 : 1);
-      CD_REQUIRE(ns >= 0 && ns <= 6 && (!lin || ns >= 1), "sampler op: 1..6 sources");
-      for (int j = 0; j < ns; ++j) CD_REQUIRE(o.src[j] >= 0 && o.src[j] < n_bufs, "sampler op: source buffer out of range");
-      if (o.kind == CD_SOP_RECORD) CD_REQUIRE(o.dst == 0 || o.dst == 1, "record op: dst is 0 (xs) or 1 (x0s)");
-      else CD_REQUIRE(o.dst >= 0 && o.dst < n_bufs, "sampler op: destination buffer out of range");
-      if (lin) CD_REQUIRE(o.col >= 0 && o.col + ns + (o.kind == CD_SOP_LINDIV ? 1 : 0) <= n_coef, "lincomb op: coefficient columns out of range");
-      if (o.kind == CD_SOP_DENOISE) {
-        CD_REQUIRE(o.col >= 0 && o.col < n_coef, "denoise op: sigma column out of range");
-        CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
-      }
-      if (o.kind == CD_SOP_DENOISE_PS) {
-        CD_REQUIRE(o.col >= 0 && o.col + batch <= n_coef, "per-sample denoise op: sigma columns out of range (col + batch > n_coef)");
-        CD_REQUIRE(o.dst != o.src[0], "denoise op: output must not alias its input");
-      }
-      if (o.kind == CD_SOP_RANDN) ++randn_per_step;
-    }
+    const int randn_per_step = validate_sampler_program(ops, op_begin, n_steps, n_ops, n_bufs, n_coef, batch).randn_per_step;
 
     plan->ws.reset((char*)workspace, workspace_bytes, false);
     float* bufs[16] = {nullptr};
@@ -263,16 +268,11 @@ int cd_sampler_run(CdPlan* plan, int batch, const float* start, float start_scal
     int64_t draws = 0;
     auto run_op = [&](hipStream_t st, const CdSamplerOp& o, int index_in_step, bool from_counter) {
       switch (o.kind) {
-        case CD_SOP_LINCOMB: {
-          const float* src[6];
-          for (int j = 0; j < o.nsrc; ++j) src[j] = bufs[o.src[j]];
-          launch_lincomb(bufs[o.dst], src, o.nsrc, table, n_coef, o.col, counter, n, st);
-          break;
-        }
+        case CD_SOP_LINCOMB:
         case CD_SOP_LINDIV: {
           const float* src[6];
           for (int j = 0; j < o.nsrc; ++j) src[j] = bufs[o.src[j]];
-          launch_lincomb_div(bufs[o.dst], src, o.nsrc, table, n_coef, o.col, counter, n, st);
+          launch_lincomb(bufs[o.dst], src, o.nsrc, table, n_coef, o.col, counter, n, o.kind == CD_SOP_LINDIV, st);
           break;
         }
         case CD_SOP_DENOISE:

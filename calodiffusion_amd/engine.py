@@ -235,6 +235,41 @@ def _i32x3(v: Sequence[int]):
     return (C.c_int32 * 3)(*[int(a) for a in v])
 
 
+def _sigma_b(sigma, B: int) -> torch.Tensor:
+    """sigma as a flat fp32 device tensor; a single value stands for the whole batch."""
+    sigma = _dev32(sigma, "sigma").reshape(-1)
+    if sigma.numel() == 1 and B > 1:
+        sigma = sigma.expand(B).contiguous()
+    return sigma
+
+
+def _pack_ops(program) -> np.ndarray:
+    """program.ops as int32 rows in CdSamplerOp's field order (kind, dst, nsrc, src[6], col)."""
+    ops = np.zeros((len(program.ops), C.sizeof(CdSamplerOp) // 4), dtype=np.int32)
+    for row, (kind, dst, src, col) in zip(ops, program.ops):
+        row[0], row[1], row[2], row[9] = kind, dst, len(src), col
+        row[3:3 + len(src)] = src
+    return ops
+
+
+def _trajectories(start, n_steps: int, want_xs: bool, want_x0s: bool, zeroed: bool):
+    """The (n_steps,) + start.shape trajectory tensors a sampler entry point fills, None where not wanted."""
+    new = torch.zeros if zeroed else torch.empty
+    shape = (n_steps,) + tuple(start.shape)
+    return tuple(new(shape, dtype=torch.float32, device=start.device) if want else None for want in (want_xs, want_x0s))
+
+
+def _program_io(start, program, n_steps: int, step_noise, debug: bool, what: str):
+    """What both sampler_run methods derive from a program: the trajectories its RECORD ops fill (``debug`` only; zeroed, a
+    program need not record every step) and the checked step_noise."""
+    recorded = {d for k, d, _, _ in program.ops if k == SOP_RECORD}
+    xs, x0s = _trajectories(start, n_steps, debug and 0 in recorded, debug and 1 in recorded, zeroed=True)
+    if step_noise is not None:
+        step_noise = _dev32(step_noise, "step_noise")
+        assert step_noise.numel() == program.n_randn * start.numel(), f"step_noise: one {what} tensor per RANDN op executed"
+    return xs, x0s, step_noise
+
+
 class UnetEngine:
     """One HIP plan bound to one CondUnet parameter set on one device."""
 
@@ -434,9 +469,7 @@ class UnetEngine:
     def denoise(self, x, sigma, cond):
         x, cond = _dev32(x, "x"), _dev32(cond, "cond")
         B = x.shape[0]
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        if sigma.numel() == 1 and B > 1:
-            sigma = sigma.expand(B).contiguous()
+        sigma = _sigma_b(sigma, B)
         if tuple(x.shape[1:]) != self.state_shape or sigma.numel() != B or cond.shape != (B, self.unet.cond_size):
             raise ValueError(f"denoise shapes: x {tuple(x.shape)} (expected (B,) + {self.state_shape}), sigma {tuple(sigma.shape)}, "
                              f"cond {tuple(cond.shape)}")
@@ -468,10 +501,7 @@ class UnetEngine:
         self.sync_weights()
         ws = self.workspace(B)
         x_out = torch.empty_like(start) if out is None else out
-        xs = x0s = None
-        if debug:
-            xs = torch.empty((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-            x0s = torch.empty_like(xs)
+        xs, x0s = _trajectories(start, n_steps, debug, debug, zeroed=False)
         if step_noise is not None:
             step_noise = _dev32(step_noise, "step_noise")
             assert step_noise.shape[0] == n_steps and step_noise[0].numel() == start.numel()
@@ -490,11 +520,7 @@ class UnetEngine:
         self._check_state(start, "sampler_run", "start")
         coefs = np.ascontiguousarray(program.coefs, dtype=np.float32)
         n_steps, n_coef = coefs.shape
-        ops = (CdSamplerOp * len(program.ops))()
-        for o, (kind, dst, src, col) in zip(ops, program.ops):
-            o.kind, o.dst, o.nsrc, o.col = kind, dst, len(src), col
-            for j, v in enumerate(src):
-                o.src[j] = v
+        ops = _pack_ops(program)
         op_begin = None
         if program.op_begin is not None:
             assert len(program.op_begin) == n_steps + 1
@@ -509,20 +535,11 @@ class UnetEngine:
             ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws
         x_out = torch.empty_like(start)
-        xs = x0s = None
-        if debug:
-            kinds = [(k, d) for k, d, _, _ in program.ops if k == SOP_RECORD]
-            if (SOP_RECORD, 0) in kinds:
-                xs = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-            if (SOP_RECORD, 1) in kinds:
-                x0s = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-        if step_noise is not None:
-            step_noise = _dev32(step_noise, "step_noise")
-            assert step_noise.numel() == program.n_randn * start.numel(), "step_noise: one (B,1,D,H,W) tensor per RANDN op executed"
+        xs, x0s, step_noise = _program_io(start, program, n_steps, step_noise, debug, "(B,1,D,H,W)")
         _check(self.lib.cd_sampler_run(self.plan, B, start.data_ptr(), float(program.start_scale), cond.data_ptr(), program.n_bufs,
-                                       n_steps, ops, len(program.ops), op_begin, coefs.ctypes.data, n_coef, _ptr(step_noise),
-                                       int(seed), int(offset), int(noise_stride), x_out.data_ptr(), _ptr(xs), _ptr(x0s),
-                                       int(bool(use_graph)), ws.data_ptr(), ws.numel(), _stream()))
+                                       n_steps, ops.ctypes.data_as(C.POINTER(CdSamplerOp)), len(program.ops), op_begin,
+                                       coefs.ctypes.data, n_coef, _ptr(step_noise), int(seed), int(offset), int(noise_stride),
+                                       x_out.data_ptr(), _ptr(xs), _ptr(x0s), int(bool(use_graph)), ws.data_ptr(), ws.numel(), _stream()))
         self.check_status()
         return x_out, xs, x0s
 
@@ -601,9 +618,7 @@ class UnetEngine:
         gradient of every parameter as a flat fp32 buffer (see grad_layout), else None.  sigma and cond are constants."""
         x, cond, gy = _dev32(x, "x"), _dev32(cond, "cond"), _dev32(gy, "gy")
         B = x.shape[0]
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        if sigma.numel() == 1 and B > 1:
-            sigma = sigma.expand(B).contiguous()
+        sigma = _sigma_b(sigma, B)
         if (tuple(x.shape[1:]) != self.state_shape or gy.shape != x.shape or sigma.numel() != B
                 or cond.shape != (B, self.unet.cond_size)):
             raise ValueError(f"denoise_vjp shapes: x {tuple(x.shape)}, gy {tuple(gy.shape)}, sigma {tuple(sigma.shape)}, "
@@ -733,9 +748,7 @@ class LayerMlpEngine:
 
     def denoise(self, x, sigma, cond):
         x, cond, B = self._io(x, cond)
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        if sigma.numel() == 1 and B > 1:
-            sigma = sigma.expand(B).contiguous()
+        sigma = _sigma_b(sigma, B)
         if sigma.numel() != B:
             raise ValueError("sigma must be (B,)")
         w, n = self._weights()
@@ -813,9 +826,7 @@ class LayerMlpEngine:
         gradient of every parameter as a flat fp32 buffer (see grad_layout), else None.  sigma and cond are constants."""
         x, cond, B = self._io(x, cond)
         gy = _dev32(gy, "gy")
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        if sigma.numel() == 1 and B > 1:
-            sigma = sigma.expand(B).contiguous()
+        sigma = _sigma_b(sigma, B)
         if gy.shape != x.shape or sigma.numel() != B:
             raise ValueError(f"denoise_vjp shapes: x {tuple(x.shape)}, gy {tuple(gy.shape)}, sigma {tuple(sigma.shape)}")
         w, n = self._weights()
@@ -850,27 +861,14 @@ class LayerMlpEngine:
         start, cond, B = self._io(start, cond)
         coefs = np.ascontiguousarray(program.coefs, dtype=np.float32)
         n_steps, n_coef = coefs.shape
-        ops = np.zeros((len(program.ops), C.sizeof(CdSamplerOp) // 4), dtype=np.int32)  # rows in CdSamplerOp's field order
-        for row, (kind, dst, src, col) in zip(ops, program.ops):
-            row[0], row[1], row[2], row[9] = kind, dst, len(src), col
-            row[3:3 + len(src)] = src
-        ops_dev = torch.from_numpy(ops).to(start.device)
+        ops_dev = torch.from_numpy(_pack_ops(program)).to(start.device)
         coefs_dev = torch.from_numpy(coefs).to(start.device)
         op_begin = None
         if program.op_begin is not None:
             assert len(program.op_begin) == n_steps + 1
             op_begin = torch.tensor(program.op_begin, dtype=torch.int32, device=start.device)
         x_out = torch.empty_like(start)
-        xs = x0s = None
-        if debug:
-            kinds = [(k, d) for k, d, _, _ in program.ops if k == SOP_RECORD]
-            if (SOP_RECORD, 0) in kinds:
-                xs = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-            if (SOP_RECORD, 1) in kinds:
-                x0s = torch.zeros((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-        if step_noise is not None:
-            step_noise = _dev32(step_noise, "step_noise")
-            assert step_noise.numel() == program.n_randn * start.numel(), "step_noise: one (B, dim) tensor per RANDN op executed"
+        xs, x0s, step_noise = _program_io(start, program, n_steps, step_noise, debug, "(B, dim)")
         w, n = self._weights()
         _check(self.lib.cd_layer_sampler_run(C.byref(self.desc), w, n, B, start.data_ptr(), float(program.start_scale),
                                              cond.data_ptr(), program.n_bufs, n_steps, ops_dev.data_ptr(), len(program.ops),
@@ -893,10 +891,7 @@ class LayerMlpEngine:
             step_noise = _dev32(step_noise, "step_noise")
             assert step_noise.numel() == n_steps * start.numel()
         x_out = torch.empty_like(start) if out is None else out
-        xs = x0s = None
-        if debug:
-            xs = torch.empty((n_steps,) + tuple(start.shape), dtype=torch.float32, device=start.device)
-            x0s = torch.empty_like(xs)
+        xs, x0s = _trajectories(start, n_steps, debug, debug, zeroed=False)
         w, n = self._weights()
         _check(self.lib.cd_layer_sample(C.byref(self.desc), w, n, B, start.data_ptr(), cond.data_ptr(), table.data_ptr(),
                                         n_steps, _ptr(step_noise), x_out.data_ptr(), _ptr(xs), _ptr(x0s), _stream()))

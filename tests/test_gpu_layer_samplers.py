@@ -372,3 +372,51 @@ def test_bad_programs_are_refused_before_any_launch():
     prof = engine.profile_end()
     assert prof["layer_program"]["launches"] == 1 and set(prof) == {"layer_program"}, prof
     assert torch.isfinite(x).all()
+
+
+def test_unet_engine_refuses_the_same_bad_programs_with_the_same_messages():
+    """cd_sampler_run and cd_layer_sampler_run check a program with one function: on the tiny U-Net every bad program of the test
+    above is refused before anything is enqueued, in the words the layer model refuses it with."""
+    from calodiffusion_amd import engine
+    from calodiffusion_amd.calodiffusion import CaloDiffusion
+    from calodiffusion_amd.configs import load_config
+    from calodiffusion_amd.engine import SOP_DENOISE, SOP_LINCOMB, SOP_LINDIV, SOP_RECORD
+    cfg = copy.deepcopy(load_config("tiny"))
+    torch.manual_seed(1234)
+    um = CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
+    ueng = um.engine()
+    gen = torch.Generator().manual_seed(61)
+    ucond = torch.rand((2, ueng.unet.cond_size), generator=gen).cuda()
+    ustart = torch.randn((2,) + tuple(ueng.state_shape), generator=gen).cuda()
+    leng = _model().layer_model.engine()
+    lstart, lE, _ = _inputs(2, 60)
+    lstart, lE = lstart.cuda(), lE.cuda()
+    good = [(SOP_DENOISE, 1, (0,), 0), (SOP_LINCOMB, 0, (0, 1), 1)]
+    bad = {
+        "dst buffer": _Prog([(SOP_LINCOMB, 4, (0, 1), 0)]),
+        "src buffer": _Prog([(SOP_LINCOMB, 0, (0, 4), 0)]),
+        "negative buffer": _Prog([(SOP_DENOISE, 1, (-1,), 0)]),
+        "record src": _Prog([(SOP_RECORD, 0, (9,), 0)]),
+        "lincomb column": _Prog([(SOP_LINCOMB, 0, (0, 1), 2)]),
+        "lindiv column": _Prog([(SOP_LINDIV, 0, (0, 1), 1)]),
+        "denoise column": _Prog([(SOP_DENOISE, 1, (0,), 3)]),
+        "nsrc 0": _Prog([(SOP_LINCOMB, 0, (), 0)]),
+        "nsrc 7": _Prog([(SOP_LINCOMB, 0, (0, 1, 2, 3, 0, 1, 2), 0)]),
+        "unknown kind": _Prog([(9, 0, (0,), 0)]),
+        "op_begin decreasing": _Prog(good + good, op_begin=[0, 3, 2]),
+        "op_begin short of n_ops": _Prog(good + good, op_begin=[0, 2, 3]),
+    }
+    x, _, _ = ueng.sampler_run(ustart, ucond, _Prog(good))  # the good program runs
+    assert torch.isfinite(x).all()
+    engine.profile_begin()
+    for what, prog in bad.items():
+        with pytest.raises(ValueError) as from_unet:
+            ueng.sampler_run(ustart, ucond, prog)
+        with pytest.raises(ValueError) as from_layer:
+            leng.sampler_run(lstart, lE, prog)
+        print(what, "refused:", from_unet.value)
+        assert str(from_unet.value) == str(from_layer.value), what
+        if what.startswith("op_begin"):
+            assert "op_begin" in str(from_unet.value)
+    prof = engine.profile_end()
+    assert prof == {}, prof

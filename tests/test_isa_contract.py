@@ -58,7 +58,7 @@ def test_lindiv_op_is_not_contracted(tmp_path):
         pytest.skip("hipcc not available")
     from calodiffusion_amd.build import FLAGS
     out = tmp_path / "misc.s"
-    src = os.path.join(ROOT, "calodiffusion_amd", "csrc", "kernels_misc.hip")
+    src = os.path.join(ROOT, "calodiffusion_amd", "csrc", "kernels_sampler.hip")
     subprocess.run([HIPCC, *[f for f in FLAGS if f != "-fPIC"], "-S", "--cuda-device-only", "-o", str(out), src], check=True,
                    capture_output=True)
     s = open(out).read()
