@@ -25,8 +25,12 @@ class CaloDiffusion(Diffusion):
         if self.fully_connected:
             raise NotImplementedError("the FCN/ResNet layer model is outside the HIP hot path (SURVEY.md 8f rank 3)")
         if self.hgcal and not self.pre_embed:
-            raise NotImplementedError("HGCal's in-model embedding (HGCalConverter inside forward) is not on the device path; use a "
-                                      "pre-embedded ('...-pre-embed') dataset")
+            # HGCalConverter inside forward (calodiffusion.py:86-98, 113-117): the state is the cell-space shower
+            pad, grid = list(config["SHAPE_PAD"]), [int(v) for v in config["SHAPE_FINAL"][2:]]
+            if len(pad) != 4 or int(pad[1]) != 1 or int(pad[2]) != grid[0]:
+                raise NotImplementedError(f"HGCal's in-model embedding (HGCalConverter inside forward) acts on the cell-space shower: "
+                                          f"SHAPE_PAD must be [-1, 1, {grid[0]}, cells], not {pad}; a dataset that is already on "
+                                          "the grid uses the pre-embedded form of the config (SHOWER_EMBED '...-pre-embed')")
         if self.time_embed not in ("log", "sigma"):
             raise KeyError(self.time_embed)  # the reference's do_time_embed raises the same way (calodiffusion.py:148-152)
         self.model = self.init_model()
@@ -53,13 +57,36 @@ class CaloDiffusion(Diffusion):
         return unet.to(self.device)
 
     def init_embedding_model(self):
-        """calodiffusion.py:100-119, the non-HGCal 'NN' case: an ``NNConverter`` over the binning file.  Without an XML at hand,
-        ``config['NN_EMBED']`` may hold an already built ``geom1.NNConverter`` (taken as it is: no RNG draws)."""
+        """calodiffusion.py:100-119.  The non-HGCal 'NN' case: an ``NNConverter`` over the binning file.  HGCal without
+        'pre-embed': an ``HGCalConverter`` over the geometry file, initialised without norm -- or, with TRAINABLE_EMBED, left as
+        the reference leaves it (:116-117): zero maps and empty masks, for ``init()`` or a checkpoint to fill.  Without the file
+        at hand, ``config['NN_EMBED']`` may hold an already built converter of the kind (taken as it is: no RNG draws)."""
         cfg = self.config
-        if "NN" not in cfg.get("SHOWER_EMBED", "") or self.hgcal or self.pre_embed:
+        if self.pre_embed or ("NN" not in cfg.get("SHOWER_EMBED", "") and not self.hgcal):
             return None
-        from .geom1 import NNConverter
+        grid = tuple(int(v) for v in cfg["SHAPE_FINAL"][2:])
         nn_embed = cfg.get("NN_EMBED")
+        if self.hgcal:
+            from .hgcal import HGCalConverter
+            if nn_embed is None:
+                trainable = bool(cfg.get("TRAINABLE_EMBED", False))
+                nn_embed = HGCalConverter(bins=cfg["SHAPE_FINAL"], geom_file=cfg["BIN_FILE"], device=self.device, trainable=trainable)
+                if not trainable:
+                    nn_embed.init(norm=self.pre_embed, dataset_num=self.dataset_num)
+            elif not isinstance(nn_embed, HGCalConverter):
+                raise TypeError("config['NN_EMBED'] takes a calodiffusion_amd.hgcal.HGCalConverter on an HGCAL config")
+            have = (nn_embed.num_layers, nn_embed.num_alpha_bins, nn_embed.num_r_bins)
+            if have != grid:
+                raise ValueError(f"the geometry embedding maps onto (layers, alpha, r) = {have}, but SHAPE_FINAL gives the U-Net "
+                                 f"the grid {grid}")
+            cells = int(nn_embed.embeder.mat.shape[-1])
+            if [int(v) for v in cfg["SHAPE_PAD"][1:]] != [1, grid[0], cells]:
+                raise ValueError(f"the geometry embedding has {cells} cells a layer: SHAPE_PAD must be [-1, 1, {grid[0]}, {cells}], "
+                                 f"not {list(cfg['SHAPE_PAD'])}")
+            if nn_embed.norm:
+                raise ValueError("an in-model HGCalConverter is initialised without norm (calodiffusion.py:117)")
+            return nn_embed.to(self.device)
+        from .geom1 import NNConverter
         if nn_embed is None:
             from .xml_handler import XMLHandler
             bins = XMLHandler("photon" if cfg.get("DATASET_NUM", 2) == 1 else "pion", cfg["BIN_FILE"])
@@ -67,7 +94,6 @@ class CaloDiffusion(Diffusion):
         elif not isinstance(nn_embed, NNConverter):
             raise TypeError("config['NN_EMBED'] takes a calodiffusion_amd.geom1.NNConverter")
         gc = nn_embed.gc
-        grid = tuple(int(v) for v in cfg["SHAPE_FINAL"][2:])
         have = (int(gc.num_layers), int(gc.alpha_out), int(gc.dim_r_out))
         if have != grid:
             raise ValueError(f"the geometry embedding maps onto (layers, alpha_out, dim_r_out) = {have}, but SHAPE_FINAL gives the "
@@ -137,7 +163,7 @@ class CaloDiffusion(Diffusion):
 
     def denoise(self, x, E=None, sigma=None, layers=None, controls=None):
         """EDM-preconditioned denoiser (calodiffusion.py:154-169): one C-ABI call.  With a geometry embedding (``do_embed``) x is
-        the flat shower (B, V): enc and dec run inside the call, and the embedding's weights take gradients as the U-Net's do.
+        the flat shower -- (B, V) for Dataset 1, the cells (B, 1, layers, cells) for HGCal -- : enc and dec run inside the call, and the embedding's weights take gradients as the U-Net's do.
 
         Differentiable when ``torch.is_grad_enabled()`` and ``x.requires_grad``: backward then gives x its gradient and, if a
         parameter requires grad, every parameter too (cd_denoise_vjp recomputes the forward on the device).  Any other call is

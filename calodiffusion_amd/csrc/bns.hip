@@ -220,7 +220,7 @@ static size_t bns_front(CdPlan* p, int B, int N, BnsFront& f) {
 static void bns_check(CdPlan* plan, int batch, int n_steps) {
   CD_REQUIRE(plan && batch > 0 && n_steps >= 1 && n_steps <= 4096, "bad argument (n_steps 1..4096)");
   CD_REQUIRE(!plan->desc.time_sin && !plan->desc.cond_sin, "the theta gradient needs the Linear time/cond embeddings");
-  CD_REQUIRE(!plan->rad.map, "the theta gradient runs on the grid: not for a plan with a flat-state embedding (cd_plan_set_radial)");
+  CD_REQUIRE(!plan->flat(), "the theta gradient runs on the grid: not for a plan with a flat-state embedding (cd_plan_set_radial / cd_plan_set_geom)");
 }
 
 }  // namespace cd

@@ -521,22 +521,22 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
   float* emb = pre ? opt->emb_pre : p->ws.get<float>((size_t)B * p->emb_ld);
   float* scal = pre ? opt->scal_pre : p->ws.get<float>((size_t)B * 4);
   float* h = p->ws.get<float>((size_t)B * dims.vox() * d.layer_sizes[0]);
-  // flat-state embedding (cd_plan_set_radial): x and out are (B, V); the network runs on g_in = enc(c_in x) and leaves its raw
+  // flat-state embedding (cd_plan_set_radial / cd_plan_set_geom): x and out are (B, V); the network runs on g_in = enc(c_in x) and leaves its raw
   // output on the grid, which embed-out decodes and combines with x
-  const CdRadialMap* rad = raw ? nullptr : p->rad.map;
-  float* g_in = rad ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
-  float* f_grid = rad ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
+  const CdPlan::FlatEmbed* fe = raw ? nullptr : p->flat();
+  float* g_in = fe ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
+  float* f_grid = fe ? p->ws.get<float>((size_t)B * dims.vox()) : nullptr;
   if (!r.dry()) {
     // (running this launch beside the init conv on a second stream was measured: no gain inside the step graph)
     if (!pre) launch_embed(embed_args(p, B, cond, t, raw ? CD_TIME_RAW : d.time_embed_kind, emb, raw ? nullptr : scal), s);
-    if (rad) launch_embed_in(rad, p->rad.enc_w, x, scal, g_in, B, s);
+    if (fe) launch_embed_in(*fe, x, scal, g_in, B, s);
     InitConvArgs a;
-    a.x = rad ? g_in : x; a.cin = d.in_channels; a.wpk = p->packed(p->init_w); a.bias = p->raw(p->init_b); a.out = h; a.batch = B;
+    a.x = fe ? g_in : x; a.cin = d.in_channels; a.wpk = p->packed(p->init_w); a.bias = p->raw(p->init_b); a.out = h; a.batch = B;
     a.cout = d.layer_sizes[0]; a.dims = dims;
     if (raw) {
       a.cx = d.in_channels;
     } else {
-      a.cx = 1; a.sigma_b = rad ? nullptr : t; a.sigma_data = d.sigma_data; a.use_rz = d.rz_input; a.use_phi = d.phi_input;  // (g_in carries c_in)
+      a.cx = 1; a.sigma_b = fe ? nullptr : t; a.sigma_data = d.sigma_data; a.use_rz = d.rz_input; a.use_phi = d.phi_input;  // (g_in carries c_in)
       a.r_w = p->d_coords; a.z_d = p->d_coords + d.grid[2]; a.phi_h = p->d_coords + d.grid[2] + d.grid[0];
       a.coord_table = p->d_init_table; a.table_ready = true; a.status = r.status;
     }
@@ -548,18 +548,18 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
   float* hf = unet_body(p, r, emb, h, head_fused ? &lazy : nullptr, &xin);
   if (!r.dry()) {
     HeadArgs ha;
-    ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = rad ? f_grid : out; ha.batch = B; ha.vox = dims.vox();
-    if (!raw && !rad) { ha.x = x; ha.scal = scal; ha.objective = d.objective; }
+    ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = fe ? f_grid : out; ha.batch = B; ha.vox = dims.vox();
+    if (!raw && !fe) { ha.x = x; ha.scal = scal; ha.objective = d.objective; }
     if (lazy.on) { ha.defer = lazy.gn; ha.res = xin; }
-    if (opt && opt->upd && !rad) {
+    if (opt && opt->upd && !fe) {
       ha.upd_stepvals = opt->upd->upd_stepvals; ha.upd_noise = opt->upd->upd_noise; ha.upd_x_next = opt->upd->upd_x_next;
       ha.upd_xs = opt->upd->upd_xs; ha.upd_x0s = opt->upd->upd_x0s;
     }
     launch_head(ha, s);
     // (the sampler's fused update moves with the combination: it acts on the flat state)
-    if (rad) launch_embed_out(rad, p->rad.dec_w, f_grid, x, scal, d.objective, out, opt ? opt->upd : nullptr, B, s);
+    if (fe) launch_embed_out(*fe, f_grid, x, scal, d.objective, out, opt ? opt->upd : nullptr, B, s);
   }
-  if (rad) {
+  if (fe) {
     r.ws->release(f_grid);
     r.ws->release(g_in);
   }

@@ -6,21 +6,7 @@
 #include "plan_internal.h"
 
 #include <climits>
-
-// row_ptr / col_ptr run over all layers: row i of layer l holds entries [row_ptr[l rows + i], row_ptr[l rows + i + 1])
-struct CdGeomMap {
-  int layers = 0, rows = 0, cols = 0;
-  int* row_ptr = nullptr;  // layers * rows + 1
-  int* col_idx = nullptr;  // nnz, ascending within a row
-  float* val = nullptr;
-  int* col_ptr = nullptr;  // layers * cols + 1, or null: no column view
-  int* row_idx = nullptr;  // entries > SPARSE_EPS, ascending within a column
-  float* cval = nullptr;
-  ~CdGeomMap() {
-    for (void* p : {(void*)row_ptr, (void*)col_idx, (void*)val, (void*)col_ptr, (void*)row_idx, (void*)cval})
-      if (p) (void)hipFree(p);
-  }
-};
+#include <type_traits>
 
 namespace cd {
 
@@ -29,23 +15,26 @@ constexpr float SPARSE_EPS = 1e-6f;  // generate_sparse_mat's eps (HGCal_utils.p
 // ---- packing: count, exclusive scan, fill --------------------------------------------------------------------------
 // One wave per row: 64 consecutive columns per step, the kept ones numbered by the ballot's prefix count, so a row's entries
 // come out in ascending column order.  fill == false: the row's count goes to ptr[row]; true: ptr is the scanned array.
+// `pat` decides which entries are kept (the dense map itself, or a trainable map's mask); ent_row (nullable): the row of every entry.
 template <bool FILL>
-__global__ void __launch_bounds__(256) geom_pack_rows_kernel(const float* __restrict__ dense, int n_rows, int cols, int* ptr,
-                                                             int* __restrict__ col_idx, float* __restrict__ val) {
+__global__ void __launch_bounds__(256) geom_pack_rows_kernel(const float* __restrict__ dense, const float* __restrict__ pat,
+                                                             int n_rows, int cols, int* ptr, int* __restrict__ col_idx,
+                                                             float* __restrict__ val, int* __restrict__ ent_row) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;  // whole waves leave together
   const float* d = dense + (int64_t)row * cols;
+  const float* m = pat + (int64_t)row * cols;
   int n = FILL ? ptr[row] : 0;
   for (int j0 = 0; j0 < cols; j0 += 64) {
     const int j = j0 + lane;
-    const float v = j < cols ? d[j] : 0.f;
-    const bool keep = v != 0.f;
+    const bool keep = j < cols && m[j] != 0.f;
     const unsigned long long mk = __ballot(keep);
     if (FILL && keep) {
       const int p = n + __popcll(mk & ((1ull << lane) - 1ull));
       col_idx[p] = j;
-      val[p] = v;
+      val[p] = d[j];
+      if (ent_row) ent_row[p] = row;
     }
     n += __popcll(mk);
   }
@@ -340,25 +329,105 @@ __global__ void __launch_bounds__(kHgThreads) preprocess_hgcal_kernel(PreHgcalAr
   }
 }
 
-static void pack(const float* dense, int n_lines, bool columns, int layers, int rows, int cols, int** ptr_out, int** idx_out,
-                 float** val_out, hipStream_t s) {
+// The transposed view of the packed entries: one thread per (layer, column) walks the pattern down the rows and, in the fill pass,
+// finds each kept entry's place in its CSR row (ascending columns: a binary search).  Rows come out ascending within a column.
+template <bool FILL>
+__global__ void __launch_bounds__(256) geom_pack_transposed_kernel(const float* __restrict__ pat, int layers, int rows, int cols,
+                                                                   const int* __restrict__ row_ptr, const int* __restrict__ col_idx,
+                                                                   int* ptr, int* __restrict__ t_row, int* __restrict__ t_pos) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= layers * cols) return;
+  const int l = c / cols, j = c - l * cols;
+  const float* m = pat + (int64_t)l * rows * cols + j;
+  int n = FILL ? ptr[c] : 0;
+  for (int i = 0; i < rows; ++i) {
+    if (m[(int64_t)i * cols] == 0.f) continue;
+    if (FILL) {
+      int lo = row_ptr[l * rows + i], hi = row_ptr[l * rows + i + 1] - 1;
+      while (lo < hi) {  // (the entry is there: both passes read one pattern)
+        const int mid = (lo + hi) >> 1;
+        if (col_idx[mid] < j) lo = mid + 1;
+        else hi = mid;
+      }
+      t_row[n] = i;
+      t_pos[n] = lo;
+    }
+    ++n;
+  }
+  if (!FILL) ptr[c] = n;
+}
+
+// val[p] = dense[row of p, column of p]: a trainable map's values from its live parameter (cd_geom_refresh)
+__global__ void __launch_bounds__(256) geom_refresh_kernel(const float* __restrict__ dense, const int* __restrict__ ent_row,
+                                                           const int* __restrict__ col_idx, float* __restrict__ val, int nnz, int cols) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p < nnz) val[p] = dense[(int64_t)ent_row[p] * cols + col_idx[p]];
+}
+
+enum GeomPack { kPackRows, kPackColumns, kPackTransposed };
+
+// counts, scan, fill.  Returns the number of entries.  kPackRows fills m->row_ptr / col_idx / val / ent_row, kPackColumns the column
+// view of the entries > SPARSE_EPS, kPackTransposed the transposed view of the rows' entries (after kPackRows).
+static int pack(CdGeomMap* m, GeomPack kind, const float* dense, const float* pat, hipStream_t s) {
+  const int layers = m->layers, rows = m->rows, cols = m->cols;
+  const int n_lines = layers * (kind == kPackRows ? rows : cols);
   int* ptr = nullptr;
   CD_HIP(hipMalloc(&ptr, sizeof(int) * ((size_t)n_lines + 1)));
-  *ptr_out = ptr;
+  (kind == kPackRows ? m->row_ptr : kind == kPackColumns ? m->col_ptr : m->t_ptr) = ptr;
   const dim3 grid_rows((unsigned)((n_lines + 3) / 4)), grid_cols((unsigned)((n_lines + 255) / 256));
-  if (columns) hipLaunchKernelGGL(geom_pack_cols_kernel<false>, grid_cols, dim3(256), 0, s, dense, layers, rows, cols, ptr, nullptr, nullptr);
-  else hipLaunchKernelGGL(geom_pack_rows_kernel<false>, grid_rows, dim3(256), 0, s, dense, n_lines, cols, ptr, nullptr, nullptr);
-  CD_HIP(hipGetLastError());
+  auto launch = [&](auto fill) {
+    constexpr bool F = decltype(fill)::value;
+    if (kind == kPackColumns)
+      hipLaunchKernelGGL(geom_pack_cols_kernel<F>, grid_cols, dim3(256), 0, s, dense, layers, rows, cols, ptr, m->row_idx, m->cval);
+    else if (kind == kPackRows)
+      hipLaunchKernelGGL(geom_pack_rows_kernel<F>, grid_rows, dim3(256), 0, s, dense, pat, n_lines, cols, ptr, m->col_idx, m->val, m->ent_row);
+    else
+      hipLaunchKernelGGL(geom_pack_transposed_kernel<F>, grid_cols, dim3(256), 0, s, pat, layers, rows, cols, m->row_ptr, m->col_idx, ptr,
+                         m->t_row, m->t_pos);
+    CD_HIP(hipGetLastError());
+  };
+  launch(std::false_type{});
   hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(1024), 0, s, ptr, n_lines);
   CD_HIP(hipGetLastError());
   int nnz = 0;
   CD_HIP(hipMemcpyAsync(&nnz, ptr + n_lines, sizeof(int), hipMemcpyDeviceToHost, s));
   CD_HIP(hipStreamSynchronize(s));
-  CD_HIP(hipMalloc(idx_out, sizeof(int) * (size_t)(nnz > 0 ? nnz : 1)));
-  CD_HIP(hipMalloc(val_out, sizeof(float) * (size_t)(nnz > 0 ? nnz : 1)));
-  if (columns) hipLaunchKernelGGL(geom_pack_cols_kernel<true>, grid_cols, dim3(256), 0, s, dense, layers, rows, cols, ptr, *idx_out, *val_out);
-  else hipLaunchKernelGGL(geom_pack_rows_kernel<true>, grid_rows, dim3(256), 0, s, dense, n_lines, cols, ptr, *idx_out, *val_out);
-  CD_HIP(hipGetLastError());
+  const size_t n = (size_t)(nnz > 0 ? nnz : 1);
+  if (kind == kPackRows) {
+    CD_HIP(hipMalloc(&m->col_idx, sizeof(int) * n));
+    CD_HIP(hipMalloc(&m->val, sizeof(float) * n));
+    CD_HIP(hipMalloc(&m->ent_row, sizeof(int) * n));
+  } else if (kind == kPackColumns) {
+    CD_HIP(hipMalloc(&m->row_idx, sizeof(int) * n));
+    CD_HIP(hipMalloc(&m->cval, sizeof(float) * n));
+  } else {
+    CD_HIP(hipMalloc(&m->t_row, sizeof(int) * n));
+    CD_HIP(hipMalloc(&m->t_pos, sizeof(int) * n));
+  }
+  launch(std::true_type{});
+  return nnz;
+}
+
+static void geom_create(const float* dense, const float* mask, int layers, int rows, int cols, int flags, CdGeomMap** out,
+                        hipStream_t s) {
+  CD_REQUIRE(dense && out && layers > 0 && rows > 0 && cols > 0, "bad argument");
+  CD_REQUIRE((flags & ~(CD_GEOM_COLUMNS | CD_GEOM_TRANSPOSED)) == 0, "cd_geom_create_ex: unknown flag");
+  CD_REQUIRE(!(mask && (flags & CD_GEOM_COLUMNS)),
+             "cd_geom_create_ex: no column view over a mask (the sampled decode's view holds values, which a refresh would leave stale)");
+  CD_REQUIRE((int64_t)layers * rows * cols <= INT_MAX && (int64_t)layers * (rows > cols ? rows : cols) <= (1 << 30),
+             "cd_geom_create: layers * rows * cols must stay below 2^31 (and layers * max(rows, cols) within 2^30)");
+  struct Owner {
+    CdGeomMap* m;
+    ~Owner() { delete m; }
+  } own{new CdGeomMap};
+  CdGeomMap* m = own.m;
+  m->layers = layers; m->rows = rows; m->cols = cols; m->masked = mask != nullptr;
+  m->nnz = pack(m, kPackRows, dense, mask ? mask : dense, s);
+  if (flags & CD_GEOM_COLUMNS) pack(m, kPackColumns, dense, nullptr, s);
+  if (flags & CD_GEOM_TRANSPOSED) pack(m, kPackTransposed, dense, mask ? mask : dense, s);
+  CD_HIP(hipStreamSynchronize(s));  // the caller may free `dense` and `mask` when this returns
+  *out = m;
+  own.m = nullptr;
 }
 
 // grid of the two per-row kernels: x covers the rows, y the layers, z the batch rows (both strided past the grid limit)
@@ -372,22 +441,22 @@ static dim3 row_grid(const CdGeomMap* m, int64_t batch_rows) {
 extern "C" {
 
 int cd_geom_create(const float* dense_dev, int layers, int rows, int cols, int want_columns, CdGeomMap** out, void* stream) {
+  return guarded([&] { geom_create(dense_dev, nullptr, layers, rows, cols, want_columns ? CD_GEOM_COLUMNS : 0, out, (hipStream_t)stream); });
+}
+
+int cd_geom_create_ex(const float* dense_dev, const float* mask_dev, int layers, int rows, int cols, int flags, CdGeomMap** out,
+                      void* stream) {
+  return guarded([&] { geom_create(dense_dev, mask_dev, layers, rows, cols, flags, out, (hipStream_t)stream); });
+}
+
+int cd_geom_refresh(CdGeomMap* map, const float* dense_dev, void* stream) {
   return guarded([&] {
-    CD_REQUIRE(dense_dev && out && layers > 0 && rows > 0 && cols > 0, "bad argument");
-    CD_REQUIRE((int64_t)layers * rows * cols <= INT_MAX && (int64_t)layers * (rows > cols ? rows : cols) <= (1 << 30),
-               "cd_geom_create: layers * rows * cols must stay below 2^31 (and layers * max(rows, cols) within 2^30)");
-    hipStream_t s = (hipStream_t)stream;
-    struct Owner {
-      CdGeomMap* m;
-      ~Owner() { delete m; }
-    } own{new CdGeomMap};
-    CdGeomMap* m = own.m;
-    m->layers = layers; m->rows = rows; m->cols = cols;
-    pack(dense_dev, layers * rows, false, layers, rows, cols, &m->row_ptr, &m->col_idx, &m->val, s);
-    if (want_columns) pack(dense_dev, layers * cols, true, layers, rows, cols, &m->col_ptr, &m->row_idx, &m->cval, s);
-    CD_HIP(hipStreamSynchronize(s));  // the caller may free `dense_dev` when this returns
-    *out = m;
-    own.m = nullptr;
+    CD_REQUIRE(map && dense_dev, "bad argument");
+    if (map->nnz > 0) {
+      hipLaunchKernelGGL(geom_refresh_kernel, dim3((unsigned)((map->nnz + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dense_dev,
+                         map->ent_row, map->col_idx, map->val, map->nnz, map->cols);
+      CD_HIP(hipGetLastError());
+    }
   });
 }
 

@@ -479,13 +479,13 @@ void ds1_consts(Ds1Args* p, const double consts[6]) {
 // ------------------------------------------------------------------------------------------------------------
 // The forms of a plan with a flat-state embedding (forward.hip, train.hip)
 // ------------------------------------------------------------------------------------------------------------
-void launch_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s) {
+void radial_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s) {
   RadialArgs f{};
   f.scal = scal;
   radial_launch(kEnc, m, enc_w, x, g, nullptr, nullptr, batch, s, &f);
 }
 
-void launch_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
+void radial_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
                       float* out, const HeadArgs* upd, int batch, hipStream_t s) {
   RadialArgs f{};
   f.scal = scal; f.epi = kEpiDenoise; f.objective = objective; f.xflat = x;
@@ -497,12 +497,12 @@ void launch_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, 
   radial_launch(kDec, m, dec_w, F, out, nullptr, nullptr, batch, s, &f);
 }
 
-void launch_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
+void radial_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
                           hipStream_t s) {
   radial_launch(kDecVjp, m, dec_w, gf, dF, F, dd, batch, s);
 }
 
-void launch_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
+void radial_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
                           const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s) {
   RadialArgs f{};
   if (gy) {

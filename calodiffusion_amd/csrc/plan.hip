@@ -437,13 +437,32 @@ int cd_plan_grad_layout(const CdPlan* plan, int idx, int64_t* offset, int64_t* t
   return guarded([&] {
     CD_REQUIRE(plan, "null argument");
     const int nw = (int)plan->weights.size();
-    if (total_floats) *total_floats = (int64_t)(plan->grad_floats + 2 * plan->rad_grad_floats());
+    if (total_floats) *total_floats = (int64_t)(plan->grad_floats + 2 * plan->embed_grad_floats());
     if (offset) {
-      CD_REQUIRE(idx >= 0 && idx < nw + (plan->rad.map ? 2 : 0), "weight index out of range");
+      CD_REQUIRE(idx >= 0 && idx < nw + (plan->embed_grad_floats() ? 2 : 0), "weight index out of range");
       *offset = idx < nw ? (int64_t)plan->weights[idx].grad_off
                          : (int64_t)(idx == nw ? plan->enc_grad_off() : plan->dec_grad_off());
     }
   });
+}
+
+// Sets one kind of flat-state embedding (clearing the other) or, with neither map, clears whichever is set.
+// A cached step graph holds the launches, the state size and the layout of the embedding it was captured with, and the kernels
+// of an earlier call may still read the maps.  Equal pointers do not mean an equal embedding (a freed map's or buffer's
+// address may be handed out again for another geometry), so every call with a map, and every call that clears one, drops them.
+static void set_flat_embedding(CdPlan* plan, const CdRadialMap* map, const float* enc_w, const float* dec_w, const CdGeomMap* genc,
+                               const CdGeomMap* gdec, int want_grads, hipStream_t stream) {
+  const bool any = map || genc;
+  if (any || plan->flat()) {
+    CD_HIP(hipStreamSynchronize(stream));
+    plan->ddim_graph.destroy();
+    plan->prog_graph.destroy();
+  }
+  CdPlan::FlatEmbed fe;
+  fe.map = map; fe.enc_w = map ? enc_w : nullptr; fe.dec_w = map ? dec_w : nullptr;
+  fe.genc = genc; fe.gdec = gdec;
+  fe.want_grads = any ? want_grads != 0 : true;
+  plan->fe = fe;
 }
 
 int cd_plan_set_radial(CdPlan* plan, const CdRadialMap* map, const float* enc_w, const float* dec_w, int want_grads, void* stream) {
@@ -457,18 +476,28 @@ int cd_plan_set_radial(CdPlan* plan, const CdRadialMap* map, const float* enc_w,
                                   std::to_string(map->A) + ", " + std::to_string(map->R) + ") is not the plan's grid (" +
                                   std::to_string(d.grid[0]) + ", " + std::to_string(d.grid[1]) + ", " + std::to_string(d.grid[2]) + ")"};
     }
-    // A cached step graph holds the launches, the state size and the layout of the embedding it was captured with, and the kernels
-    // of an earlier call may still read the matrices.  Equal pointers do not mean an equal embedding (a freed map's or buffer's
-    // address may be handed out again for another geometry), so every call with a map, and every call that clears one, drops them.
-    if (map || plan->rad.map) {
-      CD_HIP(hipStreamSynchronize((hipStream_t)stream));
-      plan->ddim_graph.destroy();
-      plan->prog_graph.destroy();
+    set_flat_embedding(plan, map, enc_w, dec_w, nullptr, nullptr, want_grads, (hipStream_t)stream);
+  });
+}
+
+int cd_plan_set_geom(CdPlan* plan, const CdGeomMap* enc_map, const CdGeomMap* dec_map, int want_grads, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan, "null argument");
+    if (enc_map) {  // refused before anything touches the device
+      CD_REQUIRE(dec_map, "cd_plan_set_geom: an encoder map needs a decoder map");
+      const CdUnetDesc& d = plan->desc;
+      const int L = d.grid[0], E = d.grid[1] * d.grid[2];
+      if (enc_map->layers != L || enc_map->rows != E || dec_map->layers != L || dec_map->cols != E)
+        throw Fail{CD_EINVAL, "cd_plan_set_geom: enc_map is (" + std::to_string(enc_map->layers) + ", " + std::to_string(enc_map->rows) +
+                                  ", cells) and dec_map (" + std::to_string(dec_map->layers) + ", cells, " +
+                                  std::to_string(dec_map->cols) + "), the plan's grid gives (" + std::to_string(L) + ", " +
+                                  std::to_string(E) + ")"};
+      if (enc_map->cols != dec_map->rows)
+        throw Fail{CD_EINVAL, "cd_plan_set_geom: enc_map has " + std::to_string(enc_map->cols) + " cells a layer, dec_map " +
+                                  std::to_string(dec_map->rows)};
+      CD_REQUIRE(enc_map->t_ptr && dec_map->t_ptr, "cd_plan_set_geom: both maps need their transposed view (CD_GEOM_TRANSPOSED)");
     }
-    plan->rad.map = map;
-    plan->rad.enc_w = map ? enc_w : nullptr;
-    plan->rad.dec_w = map ? dec_w : nullptr;
-    plan->rad.want_grads = map ? want_grads != 0 : true;
+    set_flat_embedding(plan, nullptr, nullptr, nullptr, enc_map, enc_map ? dec_map : nullptr, want_grads, (hipStream_t)stream);
   });
 }
 

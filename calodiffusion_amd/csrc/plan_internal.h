@@ -156,6 +156,28 @@ struct CdRadialMap {
   }
 };
 
+// One packed HGCal map (cd_geom_create*, kernels_geom.hip).  row_ptr / col_ptr / t_ptr run over all layers: row i of layer l
+// holds entries [row_ptr[l rows + i], row_ptr[l rows + i + 1])
+struct CdGeomMap {
+  int layers = 0, rows = 0, cols = 0, nnz = 0;
+  bool masked = false;     // the pattern is a mask (a trainable map), not the values != 0
+  int* row_ptr = nullptr;  // layers * rows + 1
+  int* col_idx = nullptr;  // nnz, ascending within a row
+  float* val = nullptr;
+  int* ent_row = nullptr;  // nnz: l rows + i of every entry
+  int* col_ptr = nullptr;  // layers * cols + 1, or null: no column view
+  int* row_idx = nullptr;  // entries > SPARSE_EPS, ascending within a column
+  float* cval = nullptr;
+  int* t_ptr = nullptr;    // layers * cols + 1, or null: no transposed view
+  int* t_row = nullptr;    // nnz: all entries, rows ascending within a column
+  int* t_pos = nullptr;    // nnz: the entry's place in col_idx / val
+  ~CdGeomMap() {
+    for (void* p : {(void*)row_ptr, (void*)col_idx, (void*)val, (void*)ent_row, (void*)col_ptr, (void*)row_idx, (void*)cval,
+                    (void*)t_ptr, (void*)t_row, (void*)t_pos})
+      if (p) (void)hipFree(p);
+  }
+};
+
 struct CdPlan {
   CdUnetDesc desc{};
   int nres = 0;
@@ -225,18 +247,29 @@ struct CdPlan {
   std::vector<LinearWgradJob> lin_jobs_host;
   LinearWgradJob* d_lin_jobs = nullptr;
 
-  // flat-state embedding (cd_plan_set_radial): the caller's map and its live matrices; map null = none.  With one, the state of
-  // every denoise-based entry point is (B, V) and the gradients of enc_w / dec_w follow the U-Net's in the flat gradient buffer
-  struct RadialEmbed {
+  // flat-state embedding: enc before and dec after the U-Net, in one of two kinds -- Dataset 1's radial matrices
+  // (cd_plan_set_radial: the caller's map and its live matrices) or HGCal's packed maps (cd_plan_set_geom); neither = none.  With
+  // one, the state of every denoise-based entry point is the flat shower and the gradients of the two maps follow the U-Net's
+  // in the flat gradient buffer.  forward.hip and train.hip reach it through launch_embed_* below only.
+  struct FlatEmbed {
     const CdRadialMap* map = nullptr;
     const float* enc_w = nullptr;
     const float* dec_w = nullptr;
+    const CdGeomMap* genc = nullptr;
+    const CdGeomMap* gdec = nullptr;
     bool want_grads = true;
-  } rad;
-  int64_t state_per() const { return rad.map ? (int64_t)rad.map->V : shapes[0].vox(); }
-  size_t rad_grad_floats() const { return rad.map ? ((size_t)rad.map->wtotal + 63) & ~(size_t)63 : 0; }
+    int64_t state() const { return map ? (int64_t)map->V : (int64_t)genc->layers * genc->cols; }
+    // floats of one gradient slot (enc's and dec's are equal); a frozen pair of HGCal maps has none
+    size_t grad_floats() const {
+      const size_t n = map ? (size_t)map->wtotal : (want_grads ? (size_t)genc->layers * genc->rows * genc->cols : 0);
+      return (n + 63) & ~(size_t)63;
+    }
+  } fe;
+  const FlatEmbed* flat() const { return (fe.map || fe.genc) ? &fe : nullptr; }
+  int64_t state_per() const { return flat() ? fe.state() : shapes[0].vox(); }
+  size_t embed_grad_floats() const { return flat() ? fe.grad_floats() : 0; }
   size_t enc_grad_off() const { return grad_floats; }
-  size_t dec_grad_off() const { return grad_floats + rad_grad_floats(); }
+  size_t dec_grad_off() const { return grad_floats + embed_grad_floats(); }
 
   Arena ws;
 
@@ -332,21 +365,49 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
 EmbedArgs embed_args(CdPlan* p, int B, const float* cond, const float* t, int kind, float* emb, float* scal);
 void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const float* t, float* out, bool raw, hipStream_t s,
                   const FwdOpts* opt = nullptr);
-// kernels_radial.hip: the launches of a plan's flat-state embedding around its U-Net.  scal: (B, 4) of launch_embed
-// g (B, 1, L, A, R) = enc(c_in x)
-void launch_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s);
-// out (B, V) = the objective's combination of x and dec(F), as launch_head forms it on the grid; upd: its fused sampler update
-void launch_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
+// The launches of a plan's flat-state embedding around its U-Net, one set per kind (kernels_radial.hip, kernels_geom_embed.hip).
+// scal: (B, 4) of launch_embed
+void radial_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s);
+void radial_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
                       float* out, const HeadArgs* upd, int batch, hipStream_t s);
+void radial_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
+                          hipStream_t s);
+void radial_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
+                          const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s);
+void geom_embed_in(const CdGeomMap* enc, const float* x, const float* scal, float* g, int batch, hipStream_t s);
+void geom_embed_out(const CdGeomMap* dec, const float* F, const float* x, const float* scal, int objective, float* out,
+                    const HeadArgs* upd, int batch, hipStream_t s);
+void geom_embed_dec_vjp(const CdGeomMap* dec, const float* F, const float* gf, float* dF, float* dd, int batch, hipStream_t s);
+void geom_embed_enc_vjp(const CdGeomMap* enc, const float* x, const float* dg, const float* gy, const float* scal, int objective,
+                        float* dx, float* dw, int batch, hipStream_t s);
+// ... and the one interface forward.hip and train.hip call.
+// g (B, grid) = enc(c_in x)
+inline void launch_embed_in(const CdPlan::FlatEmbed& e, const float* x, const float* scal, float* g, int batch, hipStream_t s) {
+  if (e.map) radial_embed_in(e.map, e.enc_w, x, scal, g, batch, s);
+  else geom_embed_in(e.genc, x, scal, g, batch, s);
+}
+// out (B, V) = the objective's combination of x and dec(F), as launch_head forms it on the grid; upd: its fused sampler update
+inline void launch_embed_out(const CdPlan::FlatEmbed& e, const float* F, const float* x, const float* scal, int objective, float* out,
+                             const HeadArgs* upd, int batch, hipStream_t s) {
+  if (e.map) radial_embed_out(e.map, e.dec_w, F, x, scal, objective, out, upd, batch, s);
+  else geom_embed_out(e.gdec, F, x, scal, objective, out, upd, batch, s);
+}
 // gf (B, V), the cotangent of dec(F): from the loss (gy null; x0, data, noise) or from a caller's cotangent gy of the output
 void launch_embed_cotangent(const float* x0, const float* data, const float* noise, const float* gy, const float* scal, float* gf,
                             int batch, int64_t per, int loss_type, int objective, hipStream_t s);
-// dF = dec's VJP of gf, and dd (nullable) = the gradient of dec_w
-void launch_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
-                          hipStream_t s);
-// dx = enc's VJP of dg (which carries c_in) plus, with gy, the preconditioning's direct x term; dw (nullable) = the gradient of enc_w
-void launch_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
-                          const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s);
+// dF = dec's VJP of gf, and dd (nullable) = the gradient of dec's map
+inline void launch_embed_dec_vjp(const CdPlan::FlatEmbed& e, const float* F, const float* gf, float* dF, float* dd, int batch,
+                                 hipStream_t s) {
+  if (e.map) radial_embed_dec_vjp(e.map, e.dec_w, F, gf, dF, dd, batch, s);
+  else geom_embed_dec_vjp(e.gdec, F, gf, dF, dd, batch, s);
+}
+// dx = enc's VJP of dg (which carries c_in) plus, with gy, the preconditioning's direct x term; dw (nullable) = the gradient of
+// enc's map
+inline void launch_embed_enc_vjp(const CdPlan::FlatEmbed& e, const float* x, const float* dg, const float* gy, const float* scal,
+                                 int objective, float* dx, float* dw, int batch, hipStream_t s) {
+  if (e.map) radial_embed_enc_vjp(e.map, e.enc_w, x, dg, gy, scal, objective, dx, dw, batch, s);
+  else geom_embed_enc_vjp(e.genc, x, dg, gy, scal, objective, dx, dw, batch, s);
+}
 // plan.hip
 void check_ready(CdPlan* p, bool need_coords);
 // sampler.hip: the one check of a step program (host arrays; op_begin null = uniform), for cd_sampler_run and cd_layer_sampler_run

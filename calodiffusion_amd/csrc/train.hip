@@ -458,7 +458,7 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
   const CdUnetDesc& d = p->desc;
   const int B = r.B;
   const Dims3 dims = p->shapes[0];
-  const CdRadialMap* rad = p->rad.map;
+  const CdPlan::FlatEmbed* fe = p->flat();
   const int64_t per = p->state_per(), n = (int64_t)B * per;  // the state: the grid, or the flat shower of an embedding
   Arena* ws = r.ws;
   hipStream_t s = r.s;
@@ -475,13 +475,13 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
   T.emb = ws->get<float>((size_t)B * p->emb_ld);
   T.scal = ws->get<float>((size_t)B * 4);
   T.h0 = ws->get<float>((size_t)B * dims.vox() * d.layer_sizes[0]);
-  if (rad) {
+  if (fe) {
     f.g_in = ws->get<float>((size_t)B * dims.vox());
     f.f_grid = ws->get<float>((size_t)B * dims.vox());
     f.gf = ws->get<float>((size_t)n);
   }
   InitConvArgs& ia = f.ia;
-  ia.x = rad ? f.g_in : f.xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = rad ? nullptr : T.scal;  // (g_in carries c_in)
+  ia.x = fe ? f.g_in : f.xn; ia.cin = d.in_channels; ia.cx = 1; ia.scale_b = fe ? nullptr : T.scal;  // (g_in carries c_in)
   ia.scale_stride = 4; ia.use_rz = d.rz_input; ia.use_phi = d.phi_input;
   ia.r_w = p->d_coords; ia.z_d = p->d_coords + d.grid[2]; ia.phi_h = p->d_coords + d.grid[2] + d.grid[0];
   ia.wpk = p->packed(p->init_w); ia.bias = p->raw(p->init_b); ia.out = T.h0; ia.batch = B; ia.cout = d.layer_sizes[0]; ia.dims = dims;
@@ -495,7 +495,7 @@ void taped_forward(CdPlan* p, Run& r, bool training, const float* data, const fl
     }
     if (training) launch_axpy_sigma(data, noise, sigma, xn, B, per, s);
     launch_embed(f.ea, s);
-    if (rad) launch_embed_in(rad, p->rad.enc_w, f.xn, T.scal, f.g_in, B, s);
+    if (fe) launch_embed_in(*fe, f.xn, T.scal, f.g_in, B, s);
     launch_init_conv(ia, s);
   }
   f.hf = unet_body_train(p, r, T.emb, T.h0, T);
@@ -669,7 +669,7 @@ void finish_param_grads(CdPlan* p, Run& r, const TapedForward& f, float* g, cons
 void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, const float* sigma, const float* cond, double* loss_out,
                      float* grads, hipStream_t s, int loss_type = 0) {
   const CdUnetDesc& d = p->desc;
-  const CdRadialMap* rad = p->rad.map;
+  const CdPlan::FlatEmbed* fe = p->flat();
   const int64_t vox = p->shapes[0].vox(), per = p->state_per();
   Run r{&p->ws, s, B, d.groups};
   r.status = p->status_word;
@@ -679,17 +679,17 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   const TrainTape& T = f.T;
   if (!r.dry()) {
     HeadArgs ha;
-    ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = rad ? f.f_grid : T.x0; ha.batch = B; ha.vox = vox;
-    if (!rad) { ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective; }
+    ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = fe ? f.f_grid : T.x0; ha.batch = B; ha.vox = vox;
+    if (!fe) { ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective; }
     launch_head(ha, s);
-    if (rad) launch_embed_out(rad, p->rad.dec_w, f.f_grid, f.xn, T.scal, d.objective, T.x0, nullptr, B, s);
+    if (fe) launch_embed_out(*fe, f.f_grid, f.xn, T.scal, d.objective, T.x0, nullptr, B, s);
     launch_loss_partial(T.x0, data, noise, sigma, f.lpart, B, per, s, loss_type, d.objective);
     launch_loss_final(f.lpart, sigma, loss_out, B, per, s, loss_type, d.objective);
   }
   BackwardState bs;
   begin_backward(p, r, bs);
   float* hpart = r.ws->get<float>((size_t)head_bwd_blocks(B, vox) * 33);
-  if (rad) {
+  if (fe) {
     if (!r.dry()) launch_embed_cotangent(T.x0, data, noise, nullptr, T.scal, f.gf, B, per, loss_type, d.objective, s);
     embed_head_backward(p, r, f, G, bs, hpart);
   } else if (!r.dry()) {
@@ -698,7 +698,7 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   }
   float* g = body_backward(p, r, T, bs.g, G, bs.demb);
   // the embedding's encoder: its weight gradient (the input is data: no input gradient is wanted, the row program's goes to gf)
-  if (rad) embed_input_backward(p, r, f, g, nullptr, f.gf, G);
+  if (fe) embed_input_backward(p, r, f, g, nullptr, f.gf, G);
   // init conv: weight and bias gradients only (its input is data)
   finish_param_grads(p, r, f, g, G, bs);
 }
@@ -706,10 +706,10 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
 void embed_head_backward(CdPlan* p, Run& r, const TapedForward& f, const Grads& G, BackwardState& bs, float* hpart) {
   const int B = r.B;
   const int64_t vox = p->shapes[0].vox();
-  const bool want = r.param_grads && p->rad.want_grads && G.base;
+  const bool want = r.param_grads && p->fe.want_grads && G.base;
   float* dF = r.ws->get<float>((size_t)B * vox);
   if (!r.dry()) {
-    launch_embed_dec_vjp(p->rad.map, p->rad.dec_w, f.f_grid, f.gf, dF, want ? G.base + p->dec_grad_off() : nullptr, B, r.s);
+    launch_embed_dec_vjp(p->fe, f.f_grid, f.gf, dF, want ? G.base + p->dec_grad_off() : nullptr, B, r.s);
     launch_head_vjp(dF, f.T.scal, f.hf, p->raw(p->head_w), bs.g, r.param_grads ? hpart : nullptr,
                     r.param_grads ? G.at(p->head_w) : nullptr, r.param_grads ? G.at(p->head_b) : nullptr, B, vox, CD_OBJ_MEAN_PRED, r.s);
   }
@@ -720,11 +720,11 @@ void embed_input_backward(CdPlan* p, Run& r, const TapedForward& f, const float*
   const CdUnetDesc& d = p->desc;
   const int B = r.B;
   const Dims3 dims = p->shapes[0];
-  const bool want = r.param_grads && p->rad.want_grads && G.base;
+  const bool want = r.param_grads && p->fe.want_grads && G.base;
   float* dg = r.ws->get<float>((size_t)B * dims.vox());
   if (!r.dry() && (gy || want)) {
     launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], nullptr, f.T.scal, CD_OBJ_MEAN_PRED, dg, B, dims, r.s);
-    launch_embed_enc_vjp(p->rad.map, p->rad.enc_w, f.xn, dg, gy, f.T.scal, d.objective, dx, want ? G.base + p->enc_grad_off() : nullptr,
+    launch_embed_enc_vjp(p->fe, f.xn, dg, gy, f.T.scal, d.objective, dx, want ? G.base + p->enc_grad_off() : nullptr,
                          B, r.s);
   }
   r.ws->release(dg);
@@ -736,7 +736,7 @@ void embed_input_backward(CdPlan* p, Run& r, const TapedForward& f, const float*
 void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,
                       bool param_grads, hipStream_t s) {
   const CdUnetDesc& d = p->desc;
-  const CdRadialMap* rad = p->rad.map;
+  const CdPlan::FlatEmbed* fe = p->flat();
   const Dims3 dims = p->shapes[0];
   const int64_t per = dims.vox();
   Run r{&p->ws, s, B, d.groups};
@@ -749,12 +749,12 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
   BackwardState bs;
   begin_backward(p, r, bs);
   float* hpart = param_grads ? r.ws->get<float>((size_t)head_bwd_blocks(B, per) * 33) : nullptr;
-  if (rad) {
+  if (fe) {
     if (!r.dry()) {
       // the head's raw output on the grid, which dec_w's gradient pairs with the cotangent
       HeadArgs ha;
       ha.h = f.hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = f.f_grid; ha.batch = B; ha.vox = per;
-      if (param_grads && p->rad.want_grads) launch_head(ha, s);
+      if (param_grads && p->fe.want_grads) launch_head(ha, s);
       launch_embed_cotangent(nullptr, nullptr, nullptr, gy, T.scal, f.gf, B, p->state_per(), 0, d.objective, s);
     }
     embed_head_backward(p, r, f, G, bs, hpart);
@@ -764,7 +764,7 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
   }
   float* g = body_backward(p, r, T, bs.g, G, bs.demb);
   // init conv: the data channel's input gradient, the preconditioning folded in (the coordinate channels are constants)
-  if (rad) embed_input_backward(p, r, f, g, gy, dx, G);
+  if (fe) embed_input_backward(p, r, f, g, gy, dx, G);
   else if (!r.dry())
     launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], gy, T.scal, d.objective, dx, B, dims, s);
   if (param_grads) {

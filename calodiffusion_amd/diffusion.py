@@ -111,7 +111,8 @@ class Diffusion(torch.nn.Module, ABC):
         (e.g. the reference's own function for the geometry-converted datasets); ``reverse_norm=False`` returns the
         normalised-space showers.  ``geometry`` = an ``hgcal.HGCalConverter``: an HGCal config with a [layer-]logit-norm map
         ends in physical showers (batch, layers, cells) too, decoded on the device (``postprocess.ReverseNormHGCal``, with
-        ``sparse_decoding`` / ``sparse_per_batch``).  ``geometry`` = a ``geom1.GeomConverter`` or ``NNConverter`` (typically
+        ``sparse_decoding`` / ``sparse_per_batch``); an HGCal model with the converter inside (no 'pre-embed') samples the cells
+        themselves and needs no ``geometry``.  ``geometry`` = a ``geom1.GeomConverter`` or ``NNConverter`` (typically
         ``model.NN_embed``): a Dataset-0/1 config ends in physical showers shaped SHAPE_ORIG (``cd_reverse_norm_ds1``).
         """
         self._physical_form(reverse_norm, geometry)  # raises NOW, not after minutes of sampling, if there is no inverse pre-processing
@@ -141,6 +142,8 @@ class Diffusion(torch.nn.Module, ABC):
                 and all(k in cfg for k in ("EMAX", "EMIN", "logE", "MAXDEP", "ECUT"))):
             if cfg.get("DATASET_NUM", 2) in (2, 3):
                 return "device"
+            if self.hgcal and geometry is None and getattr(self, "do_embed", False):
+                return "device"  # the in-model converter: the sampler's state is the cells already, nothing is left to decode
             if self.hgcal and geometry is not None:
                 from .hgcal import HGCalConverter
                 if not isinstance(geometry, HGCalConverter):

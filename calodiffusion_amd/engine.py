@@ -109,7 +109,10 @@ _SIGNATURES = {
                                       C.POINTER(C.c_double), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.c_float, _P]),
     "cd_geom_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
+    "cd_geom_create_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
+    "cd_geom_refresh": (C.c_int, [_P, _P, _P]),
     "cd_geom_destroy": (C.c_int, [_P]),
+    "cd_geom_apply_vjp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "cd_geom_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "cd_geom_sparse_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_geom_decode_sparse": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_uint64, _P, _P]),
@@ -123,6 +126,7 @@ _SIGNATURES = {
                                     C.c_int, C.c_float, _P]),
     "cd_reverse_norm_ds1": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_float, _P]),
     "cd_plan_set_radial": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "cd_plan_set_geom": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
@@ -306,7 +310,8 @@ class UnetEngine:
         self._weight_ids = None
         self._held_weights = []
         self._ws: Dict[tuple, torch.Tensor] = {}
-        self.embedding = None  # set_embedding: the NNConverter whose enc / dec run inside the denoise-based calls
+        self.embedding = None  # set_embedding: the NNConverter / HGCalConverter whose enc / dec run inside the denoise-based calls
+        self._rmap = self._gmaps = None
         self.state_shape = (1,) + self.grid  # per-sample state of those calls
         self.device = next(unet.parameters()).device
         if self.device.type != "cuda":
@@ -337,24 +342,36 @@ class UnetEngine:
 
     # ------------------------------------------------------------------ flat-state embedding
     def set_embedding(self, nn_embed):
-        """Bind a ``geom1.NNConverter`` (None: unbind) to the plan (cd_plan_set_radial): the state of denoise, the samplers, the
-        loss, train_step and denoise_vjp becomes the flat shower (B, V).  The per-layer ``encs[i].weight`` / ``decs[i].weight`` are
-        gathered into two device buffers the plan reads in place, refreshed whenever a weight changed (sync_weights)."""
+        """Bind a geometry embedding (None: unbind) to the plan: the state of denoise, the samplers, the loss, train_step and
+        denoise_vjp becomes the flat shower.  A ``geom1.NNConverter`` (cd_plan_set_radial): state (B, V); the per-layer
+        ``encs[i].weight`` / ``decs[i].weight`` are gathered into two device buffers the plan reads in place.  An
+        ``hgcal.HGCalConverter`` (cd_plan_set_geom): state (B, 1, layers, cells); the plan reads the converter's two packed maps,
+        whose values follow a trainable converter's parameters.  Either is refreshed whenever a weight changed (sync_weights)."""
+        from .hgcal import HGCalConverter
         self._grad_layout = None
         self._ws, self._tws, self._vws = {}, {}, {}
         self._embed_version = None
+        self._rmap = self._enc_flat = self._dec_flat = self._gmaps = None
         if nn_embed is None:
-            _check(self.lib.cd_plan_set_radial(self.plan, None, None, None, 0, _stream()))
+            _check(self.lib.cd_plan_set_radial(self.plan, None, None, None, 0, _stream()))  # (clears either kind)
             self.embedding, self.state_shape = None, (1,) + self.grid
-            self._rmap = self._enc_flat = self._dec_flat = None
             return
-        rmap = nn_embed.gc.radial_map()
-        if (rmap.L, rmap.A, rmap.R) != self.grid:
-            raise ValueError(f"the embedding maps onto the grid {(rmap.L, rmap.A, rmap.R)}, the U-Net runs on {self.grid}")
-        self._rmap = rmap  # (the plan reads the handle: kept alive here)
-        self._enc_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
-        self._dec_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
-        self.embedding, self.state_shape = nn_embed, (rmap.V,)
+        if isinstance(nn_embed, HGCalConverter):
+            have = (nn_embed.num_layers, nn_embed.num_alpha_bins, nn_embed.num_r_bins)
+            if have != self.grid:
+                raise ValueError(f"the embedding maps onto the grid {have}, the U-Net runs on {self.grid}")
+            if nn_embed.norm:
+                raise ValueError("an in-model HGCalConverter has no norm (the reference calls init(norm=pre_embed), "
+                                 "calodiffusion.py:117): bind a converter initialised with norm=False")
+            self.embedding, self.state_shape = nn_embed, (1, have[0], int(nn_embed.embeder.mat.shape[-1]))
+        else:
+            rmap = nn_embed.gc.radial_map()
+            if (rmap.L, rmap.A, rmap.R) != self.grid:
+                raise ValueError(f"the embedding maps onto the grid {(rmap.L, rmap.A, rmap.R)}, the U-Net runs on {self.grid}")
+            self._rmap = rmap  # (the plan reads the handle: kept alive here)
+            self._enc_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
+            self._dec_flat = torch.empty(rmap.wtotal, dtype=torch.float32, device=self.device)
+            self.embedding, self.state_shape = nn_embed, (rmap.V,)
         self._sync_embedding()
 
     def _check_state(self, x, name, what="x"):
@@ -363,14 +380,33 @@ class UnetEngine:
         if tuple(x.shape[1:]) != self.state_shape:
             raise ValueError(f"{name}: {what} has shape {tuple(x.shape)}, expected (B,) + {self.state_shape}")
 
+    def _embed_is_geom(self) -> bool:
+        return self.embedding is not None and self._rmap is None
+
     def _embed_params(self):
-        return [lay.weight for lay in self.embedding.encs] + [lay.weight for lay in self.embedding.decs]
+        """[(name in grad_layout, parameter)] of the bound embedding, in the order of its ``parameters()``"""
+        if self._embed_is_geom():
+            return [(f"NN_embed.{k}", p) for k, p in self.embedding.named_parameters()]
+        return ([(f"NN_embed.encs.{i}", lay.weight) for i, lay in enumerate(self.embedding.encs)] +
+                [(f"NN_embed.decs.{i}", lay.weight) for i, lay in enumerate(self.embedding.decs)])
 
     def embedding_trains(self) -> bool:
-        return self.embedding is not None and any(p.requires_grad for p in self._embed_params())
+        return self.embedding is not None and any(p.requires_grad for _, p in self._embed_params())
 
     def _sync_embedding(self):
-        ps = self._embed_params()
+        if self._embed_is_geom():
+            # packed(): packs on first use, gathers the values again when a trainable parameter changed (one launch); the plan
+            # reads the handles in place, so only a new handle or a change of the gradient flag is a call
+            enc, dec = self.embedding.embeder.packed(), self.embedding.decoder.packed()
+            ver = (enc.handle.value, dec.handle.value, self.embedding_trains())
+            if ver != self._embed_version:
+                _check(self.lib.cd_plan_set_geom(self.plan, enc.handle, dec.handle, int(ver[-1]), _stream()))
+                self._gmaps = (enc, dec)  # (kept alive here)
+                self._grad_layout = None  # (frozen maps have no gradient slots)
+                self._tws, self._vws = {}, {}
+                self._embed_version = ver
+            return
+        ps = [p for _, p in self._embed_params()]
         ver = tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (self.embedding_trains(),)
         if ver == self._embed_version:
             return
@@ -567,10 +603,13 @@ class UnetEngine:
                 _check(self.lib.cd_plan_weight_name(self.plan, i, buf, 256, C.byref(numel)))
                 _check(self.lib.cd_plan_grad_layout(self.plan, i, C.byref(off), C.byref(total)))
                 lay[buf.value.decode()] = (off.value, numel.value)
-            if self.embedding is not None:  # the embedding's two blocks follow the U-Net's (cd_plan_set_radial)
+            # the embedding's two blocks follow the U-Net's (cd_plan_set_radial; cd_plan_set_geom when its maps train)
+            if self.embedding is not None and (not self._embed_is_geom() or self.embedding_trains()):
+                sizes = ((self._rmap.wtotal,) * 2 if not self._embed_is_geom() else
+                         (self.embedding.embeder.mat.numel(), self.embedding.decoder.mat.numel()))
                 for k, name in enumerate(("NN_embed.encs", "NN_embed.decs")):
                     _check(self.lib.cd_plan_grad_layout(self.plan, n.value + k, C.byref(off), C.byref(total)))
-                    lay[name] = (off.value, self._rmap.wtotal)
+                    lay[name] = (off.value, sizes[k])
             self._grad_layout = (lay, total.value)
         return self._grad_layout
 
@@ -668,13 +707,18 @@ class UnetEngine:
 
     def param_grads(self, flat):
         """Views of the flat gradient buffer, one per parameter of the bound CondUnet, in .parameters() order; with an embedding,
-        its ``encs[i].weight`` and then its ``decs[i].weight`` follow (the order of ``NNConverter.parameters()``)."""
+        its ``encs[i].weight`` and then its ``decs[i].weight`` follow (the order of ``NNConverter.parameters()``), or a trainable
+        ``HGCalConverter``'s ``embeder.mat`` and ``decoder.mat`` (None for both while neither requires a gradient: no slots)."""
         lay, _ = self.grad_layout()
         out = []
         for name, p in self.unet.named_parameters():
             off, numel = lay[name]
             out.append(flat[off:off + numel].view(p.shape))
-        if self.embedding is not None:
+        if self._embed_is_geom():  # the two dense maps of a trainable HGCalConverter; a frozen one has no parameters
+            for name, mod in (("NN_embed.encs", self.embedding.embeder), ("NN_embed.decs", self.embedding.decoder)):
+                if mod.trainable:
+                    out.append(flat[lay[name][0]:lay[name][0] + lay[name][1]].view(mod.mat.shape) if name in lay else None)
+        elif self.embedding is not None:
             for name, layers in (("NN_embed.encs", self.embedding.encs), ("NN_embed.decs", self.embedding.decs)):
                 off = lay[name][0]
                 for layer in layers:

@@ -2,12 +2,17 @@
 (calodiffusion/utils/HGCal_utils.py:295-407, 412-486, 517-680) over the packed maps of ``cd_geom_*`` (include/calodiff.h).
 
 The maps between HGCal's irregular cells (layers, cells) and the regular (layers, alpha, r) grid are linear with one or two
-non-zeros per cell, so they are packed once (per-layer CSR, plus a column view for the sampled decode) and applied by
-``cd_geom_apply`` / ``cd_geom_decode_sparse``; nothing is copied to the host.  Building a map from a geometry (``from_geometry``:
-``init_map`` and ``torch.linalg.pinv``, :412-486, 595-634) is construction-time host work.
+non-zeros per cell, so they are packed once (per-layer CSR, a transposed view for the gradients, and a column view for the
+sampled decode) and applied by ``cd_geom_apply`` / ``cd_geom_decode_sparse``; nothing is copied to the host.  Building a map
+from a geometry (``from_geometry``: ``init_map`` and ``torch.linalg.pinv``, :412-486, 595-634) is construction-time host work.
 
-These are inference maps: no gradient flows through them, and TRAINABLE_EMBED training is not provided (``trainable=True`` only
-folds ``mat * mask``, as the reference's forward does, when the map is packed).
+``forward``, ``enc`` and ``dec`` are differentiable (``cd_geom_apply_vjp``) when grad is enabled and the input or a trainable
+``mat`` requires one; any other call is the plain product without a graph.  A trainable converter (``trainable=True``, the
+configs' TRAINABLE_EMBED) holds its two maps as ``nn.Parameter``s trained through ``mat * mask``, as the reference's forward
+does: the packed pattern is then the boolean ``mask`` -- a masked entry whose value is 0 still takes gradient, the gradient
+outside the mask is exactly 0, and parameter values outside the mask never enter a product -- and the packed values are
+gathered again from the live parameter whenever it changed.  Inside a model (``CaloDiffusion`` with HGCAL and no 'pre-embed')
+the maps run within the denoise-based device calls (``cd_plan_set_geom``).  Not provided: ``init(noise_scale > 0)``.
 """
 from __future__ import annotations
 
@@ -16,29 +21,50 @@ import pickle
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import engine
 from .postprocess import HGCAL_EMBED_PARAMS
 
 EPS = 1e-6  # the threshold of HGCalConverter.init's masks and of generate_sparse_mat (HGCal_utils.py:371, 607)
+_GEOM_COLUMNS, _GEOM_TRANSPOSED = 1, 2  # CD_GEOM_* of include/calodiff.h
+
+
+def _to_dev32(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(device="cuda", dtype=torch.float32).contiguous()
 
 
 class _PackedMap:
-    """Owner of one CdGeomMap handle."""
+    """Owner of one CdGeomMap handle.  ``mask``: the pattern of a trainable map (``dense`` then holds the values, read at the
+    masked entries only; see ``refresh``); without one the pattern is ``dense != 0``."""
 
-    def __init__(self, dense: torch.Tensor, want_columns: bool):
-        dense = dense.detach().to(device="cuda", dtype=torch.float32).contiguous()
+    def __init__(self, dense: torch.Tensor, want_columns: bool, mask=None):
+        dense = _to_dev32(dense)
         self.layers, self.rows, self.cols = (int(s) for s in dense.shape)
         self._lib = engine.load_library()
         handle = C.c_void_p()
-        engine._check(self._lib.cd_geom_create(dense.data_ptr(), self.layers, self.rows, self.cols, int(want_columns),
-                                               C.byref(handle), engine._stream()))
+        pattern = None
+        if mask is not None:
+            pattern = _to_dev32(torch.as_tensor(mask) != 0)
+            if pattern.shape != dense.shape:
+                raise ValueError(f"geometry map: mask {tuple(pattern.shape)} must have the map's shape {tuple(dense.shape)}")
+        flags = _GEOM_TRANSPOSED | (_GEOM_COLUMNS if want_columns else 0)
+        engine._check(self._lib.cd_geom_create_ex(dense.data_ptr(), engine._ptr(pattern), self.layers, self.rows, self.cols, flags,
+                                                  C.byref(handle), engine._stream()))
         self.handle = handle
 
     def __del__(self):
         if getattr(self, "handle", None):
             self._lib.cd_geom_destroy(self.handle)
             self.handle = None
+
+    def refresh(self, dense: torch.Tensor):
+        """the packed values again from ``dense`` (a trainable map's live parameter)"""
+        dense = _to_dev32(dense)
+        if tuple(dense.shape) != (self.layers, self.rows, self.cols):
+            raise ValueError(f"geometry map: expected ({self.layers}, {self.rows}, {self.cols}), got {tuple(dense.shape)}")
+        engine._check(self._lib.cd_geom_refresh(self.handle, dense.data_ptr(), engine._stream()))
+        self._held = dense  # (a converted copy must outlive the launch)
 
     def apply(self, x: torch.Tensor, scale: float, shift: float, affine_first: bool) -> torch.Tensor:
         """x (..., L, cols) -> (..., L, rows)"""
@@ -50,6 +76,22 @@ class _PackedMap:
             engine._check(self._lib.cd_geom_apply(self.handle, x.data_ptr(), y.data_ptr(), x.numel() // (self.layers * self.cols),
                                                   float(scale), float(shift), int(affine_first), engine._stream()))
         return y
+
+    def apply_vjp(self, x, gy, scale: float, shift: float, affine_first: bool, want_dx: bool, want_dm: bool):
+        """The gradients of ``apply`` for the cotangent gy (..., L, rows): (dx like x or None, dm (L, rows, cols) dense or None)"""
+        x, gy = engine._dev32(x, "x"), engine._dev32(gy, "gy")
+        if tuple(x.shape[-2:]) != (self.layers, self.cols) or gy.shape != x.shape[:-1] + (self.rows,):
+            raise ValueError(f"geometry map gradient: x {tuple(x.shape)} and gy {tuple(gy.shape)} do not fit "
+                             f"({self.layers}, {self.rows}, {self.cols})")
+        dx = torch.empty_like(x) if want_dx else None
+        dm = torch.empty((self.layers, self.rows, self.cols), dtype=torch.float32, device=x.device) if want_dm else None
+        n = x.numel() // (self.layers * self.cols)
+        if n == 0:
+            return dx, (dm.zero_() if want_dm else None)
+        if want_dx or want_dm:
+            engine._check(self._lib.cd_geom_apply_vjp(self.handle, x.data_ptr(), gy.data_ptr(), engine._ptr(dx), engine._ptr(dm), n,
+                                                      float(scale), float(shift), int(affine_first), engine._stream()))
+        return dx, dm
 
     def decode_sparse(self, x: torch.Tensor, per_batch: bool, rand, seed: int, offset: int) -> torch.Tensor:
         """x (B, C, L, cols) -> (B, C, L, rows)"""
@@ -73,49 +115,102 @@ class _PackedMap:
         return y
 
 
+class _Apply(torch.autograd.Function):
+    """``_PackedMap.apply`` with a backward: one cd_geom_apply_vjp call gives the input its gradient and, for a trainable map,
+    ``mat`` its dense one (zero outside the mask).  ``mat`` is an argument only so that autograd routes that gradient."""
+
+    @staticmethod
+    def forward(ctx, x, mat, pm, scale, shift, affine_first):
+        ctx.pm, ctx.affine = pm, (scale, shift, affine_first)
+        ctx.mat_version = None if mat is None else mat._version
+        ctx.mat = mat
+        ctx.save_for_backward(x)
+        return pm.apply(x.detach(), scale, shift, affine_first)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        if ctx.mat is not None and ctx.mat._version != ctx.mat_version:
+            raise RuntimeError("geometry map: the trainable matrix was modified in place between forward and backward")
+        dx, dm = ctx.pm.apply_vjp(x, gy.contiguous(), *ctx.affine, want_dx=ctx.needs_input_grad[0],
+                                  want_dm=ctx.mat is not None and ctx.needs_input_grad[1])
+        if dm is not None and dm.device != ctx.mat.device:
+            dm = dm.to(ctx.mat.device)
+        return dx, dm, None, None, None, None
+
+
 class _Map(torch.nn.Module):
     """Shared part of Embeder and Decoder: the reference's attributes, and the handle packed on first use (and again after
-    ``set``)."""
+    ``set``).  ``trainable``: ``mat`` is an ``nn.Parameter`` (one passed in is kept as it is), the handle is packed over ``mask`` and its
+    values follow the parameter (its version and pointer are looked at on every use)."""
     _want_columns = False
 
     def __init__(self, dim1, dim2, mat, mask, trainable=False):
         super().__init__()
         self.dim1, self.dim2 = int(dim1), int(dim2)
         self.trainable = bool(trainable)
-        self.mat, self.mask = mat, mask
-        self._packed = None
+        if self.trainable and not isinstance(mat, torch.nn.Parameter):
+            # (a map built on its own from a plain tensor stays frozen until its owner asks: HGCalConverter(trainable=True) does,
+            # a direct caller says ``mat.requires_grad_()`` -- the result of a call then carries a graph, as the reference's)
+            mat = torch.nn.Parameter(torch.as_tensor(mat).to(torch.float32), requires_grad=False)
+        self.mat = mat
+        self.mask = mask
+        self._packed = self._values = self._sampled = None
 
     def set(self, mat, mask):
-        self.mat, self.mask = mat, mask
-        self._packed = None
+        """New values and mask.  A trainable map's Parameter object survives: it is filled in place."""
+        if self.trainable:
+            with torch.no_grad():
+                self.mat.copy_(torch.as_tensor(mat))
+        else:
+            self.mat = mat
+        self.mask = mask
+        self._packed = self._values = self._sampled = None
+
+    def _state(self):
+        return (self.mat._version, self.mat.data_ptr())
 
     def packed(self) -> _PackedMap:
+        if not self.trainable:
+            if self._packed is None:
+                self._packed = _PackedMap(self.mat, self._want_columns)
+            return self._packed
         if self._packed is None:
-            mat = self.mat * self.mask if self.trainable else self.mat
-            self._packed = _PackedMap(mat, self._want_columns)
+            self._packed = _PackedMap(self.mat, False, mask=self.mask)
+            self._values = self._state()
+        elif self._values != self._state():
+            self._packed.refresh(self.mat)
+            self._values = self._state()
         return self._packed
+
+    def _apply_map(self, x, scale, shift, affine_first):
+        pm = self.packed()
+        mat = self.mat if self.trainable and self.mat.requires_grad else None
+        if torch.is_grad_enabled() and (mat is not None or (isinstance(x, torch.Tensor) and x.requires_grad)):
+            return _Apply.apply(engine._dev32(x, "x"), mat, pm, scale, shift, affine_first)
+        return pm.apply(x, scale, shift, affine_first)
 
 
 class Embeder(_Map):
-    """``Embeder`` (HGCal_utils.py:295-324): cells (..., L, N) -> grid (..., L, dim1, dim2) with ``mat`` (L, dim1 * dim2, N).
-    Inference only: the result carries no autograd graph."""
+    """``Embeder`` (HGCal_utils.py:295-324): cells (..., L, N) -> grid (..., L, dim1, dim2) with ``mat`` (L, dim1 * dim2, N)."""
 
     def forward(self, x):
         return self._embed(x, 1.0, 0.0)
 
     def _embed(self, x, std, mean):
-        out = self.packed().apply(x, std, mean, affine_first=False)
+        out = self._apply_map(x, std, mean, affine_first=False)
         return out.reshape(out.shape[:-1] + (self.dim1, self.dim2))
 
 
 class Decoder(_Map):
     """``Decoder`` (HGCal_utils.py:327-353): grid (..., L, dim1, dim2) -> cells (..., L, N) with ``mat`` (L, N, dim1 * dim2).
-    Inference only: the result carries no autograd graph.
 
-    ``sparse_decoding`` (``generate_sparse_mat``, :355-407) takes x (B, C, L, dim1, dim2).  Its uniforms come from the device
-    Philox stream (``seed``, ``offset``): by default the decoder's own (``noise_seed``, and a running ``noise_offset`` that
-    advances by the (B or 1, L, N, E) tensor a call draws); a batch shard passes ``offset`` = that of the global call + first
-    shower * L * N * E.  ``rand`` (B or 1, L, N, E) replaces the draw (parity with a recorded ``torch.rand``)."""
+    ``sparse_decoding`` (``generate_sparse_mat``, :355-407) takes x (B, C, L, dim1, dim2) and carries no autograd graph.  Its
+    uniforms come from the device Philox stream (``seed``, ``offset``): by default the decoder's own (``noise_seed``, and a running
+    ``noise_offset`` that advances by the (B or 1, L, N, E) tensor a call draws); a batch shard passes ``offset`` = that of the
+    global call + first shower * L * N * E.  ``rand`` (B or 1, L, N, E) replaces the draw (parity with a recorded
+    ``torch.rand``)."""
     _want_columns = True
 
     def __init__(self, dim1, dim2, mat, mask, trainable=False):
@@ -125,19 +220,28 @@ class Decoder(_Map):
     def forward(self, x, sparse_decoding=False, sparse_per_batch=False, *, rand=None, seed=None, offset=None):
         return self._decode(x, 1.0, 0.0, sparse_decoding, sparse_per_batch, rand, seed, offset)
 
+    def _sampled_map(self) -> _PackedMap:
+        """the map with its column view: a trainable map's is packed from ``mat * mask`` as it stands (the view holds values)"""
+        if not self.trainable:
+            return self.packed()
+        if self._sampled is None or self._sampled[0] != self._state():
+            mask = torch.as_tensor(self.mask).to(self.mat.device)
+            self._sampled = (self._state(), _PackedMap(self.mat.detach() * mask, True))
+        return self._sampled[1]
+
     def _decode(self, x, std, mean, sparse_decoding, sparse_per_batch, rand=None, seed=None, offset=None):
         if tuple(x.shape[-2:]) != (self.dim1, self.dim2):
             raise ValueError(f"Decoder: expected (..., layers, {self.dim1}, {self.dim2}), got {tuple(x.shape)}")
         x = x.reshape(x.shape[:-2] + (self.dim1 * self.dim2,))
-        pm = self.packed()
         if not sparse_decoding:
-            return pm.apply(x, std, mean, affine_first=True)
+            return self._apply_map(x, std, mean, affine_first=True)
+        pm = self._sampled_map()
         if std != 1.0 or mean != 0.0:  # (every shipped HGCal constant set has embed_mean 0, embed_std 1)
             x = engine._dev32(x, "x") * std + mean
         if rand is None and seed is None and offset is None:
             seed, offset = self.noise_seed, self.noise_offset
             self.noise_offset += (1 if sparse_per_batch else int(x.shape[0])) * pm.layers * pm.rows * pm.cols
-        return pm.decode_sparse(x, bool(sparse_per_batch), rand, seed if seed is not None else self.noise_seed, offset or 0)
+        return pm.decode_sparse(x.detach(), bool(sparse_per_batch), rand, seed if seed is not None else self.noise_seed, offset or 0)
 
 
 def init_map(num_alpha_bins, num_r_bins, geom, ilay):
@@ -209,10 +313,12 @@ def load_geom(geom_filename):
 
 class HGCalConverter(torch.nn.Module):
     """``HGCalConverter`` (HGCal_utils.py:517-680) with the maps on the device: ``enc`` / ``dec`` take and return device
-    tensors, ``enc_batches`` / ``dec_batches`` numpy, as the reference's.  Inference only (see the module docstring).
+    tensors, ``enc_batches`` / ``dec_batches`` numpy, as the reference's; both are differentiable (see the module docstring).
 
     Built as the reference is -- ``HGCalConverter(bins=, geom_file=)`` then ``init(norm=, dataset_num=)`` -- or without the
-    pickle by ``from_geometry``, ``from_matrices`` or ``from_reference``."""
+    pickle by ``from_geometry``, ``from_matrices`` or ``from_reference``.  ``trainable=True``: ``embeder.mat`` and
+    ``decoder.mat`` are Parameters (state_dict keys ``embeder.mat``, ``decoder.mat``, ``nets.0.mat``, ``nets.1.mat``, the
+    reference's), zero with empty masks until ``init()`` or a checkpoint fills them in place."""
 
     def __init__(self, bins=None, geom_file=None, hidden_size=32, device=None, trainable=False, geom=None):
         super().__init__()
@@ -225,24 +331,43 @@ class HGCalConverter(torch.nn.Module):
         self.norm, self.embed_mean, self.embed_std = False, 0.0, 1.0
         E = self.num_alpha_bins * self.num_r_bins
         N = int(self.geom.max_ncell) if self.geom is not None else 1
-        self._set_maps(torch.zeros((self.num_layers, E, N)), torch.zeros((self.num_layers, N, E)), None, None)
+        L = self.num_layers
+        self._set_maps(torch.zeros((L, E, N)), torch.zeros((L, N, E)), torch.zeros((L, E, N), dtype=torch.bool),
+                       torch.zeros((L, N, E), dtype=torch.bool))
+
+    # the reference's four tensors live in the two map modules (a trainable converter's enc_mat / dec_mat: the Parameters' data)
+    enc_mat = property(lambda self: self.embeder.mat.detach() if self.trainable else self.embeder.mat)
+    dec_mat = property(lambda self: self.decoder.mat.detach() if self.trainable else self.decoder.mat)
+    enc_mask = property(lambda self: self.embeder.mask)
+    dec_mask = property(lambda self: self.decoder.mask)
 
     def _set_maps(self, enc_mat, dec_mat, enc_mask, dec_mask):
         L, E = self.num_layers, self.num_alpha_bins * self.num_r_bins
         if enc_mat.dim() != 3 or enc_mat.shape[:2] != (L, E) or tuple(dec_mat.shape) != (L, enc_mat.shape[2], E):
             raise ValueError(f"HGCalConverter: enc_mat must be ({L}, {E}, cells) and dec_mat ({L}, cells, {E}); got "
                              f"{tuple(enc_mat.shape)} and {tuple(dec_mat.shape)}")
-        self.enc_mat, self.dec_mat = enc_mat, dec_mat
-        self.enc_mask = torch.abs(enc_mat) > EPS if enc_mask is None else enc_mask
-        self.dec_mask = torch.abs(dec_mat) > EPS if dec_mask is None else dec_mask
-        self.embeder = Embeder(self.num_alpha_bins, self.num_r_bins, self.enc_mat, self.enc_mask, trainable=self.trainable)
-        self.decoder = Decoder(self.num_alpha_bins, self.num_r_bins, self.dec_mat, self.dec_mask, trainable=self.trainable)
+        enc_mask = torch.abs(enc_mat) > EPS if enc_mask is None else enc_mask
+        dec_mask = torch.abs(dec_mat) > EPS if dec_mask is None else dec_mask
+        if tuple(enc_mask.shape) != tuple(enc_mat.shape) or tuple(dec_mask.shape) != tuple(dec_mat.shape):
+            raise ValueError(f"HGCalConverter: the masks must have the maps' shapes; got {tuple(enc_mask.shape)} and "
+                             f"{tuple(dec_mask.shape)}")
+        have = getattr(self, "embeder", None)
+        if self.trainable and have is not None and have.mat.shape == enc_mat.shape:  # in place: the Parameter objects survive
+            self.embeder.set(enc_mat, enc_mask)
+            self.decoder.set(dec_mat, dec_mask)
+            return
+        self.embeder = Embeder(self.num_alpha_bins, self.num_r_bins, enc_mat, enc_mask, trainable=self.trainable)
+        self.decoder = Decoder(self.num_alpha_bins, self.num_r_bins, dec_mat, dec_mask, trainable=self.trainable)
+        self.nets = torch.nn.ModuleList([self.embeder, self.decoder])
+        if self.trainable:
+            self.embeder.mat.requires_grad_(True)
+            self.decoder.mat.requires_grad_(True)
 
     @classmethod
-    def from_matrices(cls, bins, enc_mat, dec_mat, enc_mask=None, dec_mask=None):
+    def from_matrices(cls, bins, enc_mat, dec_mat, enc_mask=None, dec_mask=None, trainable=False):
         """A converter over given maps: enc_mat (L, alpha * r, cells), dec_mat (L, cells, alpha * r); the masks (used by a
         trainable converter only) default to |mat| > 1e-6."""
-        conv = cls(bins=bins)
+        conv = cls(bins=bins, trainable=trainable)
         as_t = lambda a: None if a is None else torch.as_tensor(a)  # noqa: E731
         conv._set_maps(as_t(enc_mat).to(torch.float32), as_t(dec_mat).to(torch.float32), as_t(enc_mask), as_t(dec_mask))
         return conv
@@ -252,23 +377,25 @@ class HGCalConverter(torch.nn.Module):
         """A converter with the maps and normalisation of an initialised reference ``HGCalConverter`` (or anything with
         ``enc_mat``, ``dec_mat``, ``norm``, ``embed_mean`` and ``embed_std``; ``bins`` if the object has none)."""
         conv = cls.from_matrices(bins if bins is not None else obj.bins, obj.enc_mat.detach(), obj.dec_mat.detach(),
-                                 getattr(obj, "enc_mask", None), getattr(obj, "dec_mask", None))
+                                 getattr(obj, "enc_mask", None), getattr(obj, "dec_mask", None),
+                                 trainable=bool(getattr(obj, "trainable", False)))
         conv.norm, conv.embed_mean, conv.embed_std = bool(obj.norm), float(obj.embed_mean), float(obj.embed_std)
         return conv
 
     @classmethod
-    def from_geometry(cls, geom, bins, norm=False, dataset_num=101):
+    def from_geometry(cls, geom, bins, norm=False, dataset_num=101, trainable=False):
         """A converter initialised from a geometry object: ``ncells``, ``ring_map``, ``theta_map`` (or ``xmap`` / ``ymap``),
         ``nlayers`` and ``max_ncell``."""
-        conv = cls(bins=bins, geom=geom)
+        conv = cls(bins=bins, geom=geom, trainable=trainable)
         conv.init(norm=norm, dataset_num=dataset_num)
         return conv
 
     def init(self, noise_scale=0.0, norm=False, dataset_num=101):
-        """``HGCalConverter.init`` (HGCal_utils.py:595-634): the geometric encoding of every layer and its pseudo-inverse."""
+        """``HGCalConverter.init`` (HGCal_utils.py:595-634): the geometric encoding of every layer and its pseudo-inverse.  A
+        trainable converter's Parameters are filled in place."""
         if noise_scale > 0.0:
-            raise NotImplementedError("HGCalConverter.init(noise_scale > 0) perturbs the maps for TRAINABLE_EMBED training, "
-                                      "which is not provided")
+            raise NotImplementedError("HGCalConverter.init(noise_scale > 0) perturbs the initial maps of TRAINABLE_EMBED training "
+                                      "with torch.randn draws; that form of init is not provided")
         if self.geom is None:
             raise ValueError("HGCalConverter.init needs a geometry (geom_file= or geom=)")
         E, N = self.num_alpha_bins * self.num_r_bins, int(self.geom.max_ncell)

@@ -23,6 +23,10 @@ class LayerDiffusion(CaloDiffusion):
     def __init__(self, config, n_steps=400, loss_type="l2"):
         from .configs import load_config
         embed = load_config(config).get("SHOWER_EMBED", "")
+        if load_config(config).get("HGCAL", False) and "pre-embed" not in embed:
+            raise NotImplementedError("LayerDiffusion over HGCal's in-model geometry embedding (HGCalConverter inside forward): the "
+                                      "two-stage sampling and its layer-energy conditioning are not wired to the cell-space state; "
+                                      "use CaloDiffusion for such a config, or its pre-embedded ('...-pre-embed') form")
         if "NN" in embed and "orig" in embed and "pre-embed" not in embed:
             raise NotImplementedError("LayerDiffusion over an in-model geometry embedding (SHOWER_EMBED 'orig-NN'): the two-stage "
                                       "sampling and its layer-energy conditioning are not wired to the flat Dataset-1 state yet; "

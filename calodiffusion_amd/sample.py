@@ -967,7 +967,8 @@ class BespokeNonStationary(Sample):
         self.check_embedding(model, self.config)
         if getattr(model, "do_embed", False):
             raise NotImplementedError("BespokeNonStationary: theta training on a model with an in-model geometry embedding "
-                                      "(SHOWER_EMBED 'orig-NN') is not provided: cd_bns_theta_grad runs its chain on the grid")
+                                      "(SHOWER_EMBED 'orig-NN', or HGCal's HGCalConverter inside forward) is not provided: "
+                                      "cd_bns_theta_grad runs its chain on the grid")
         eng = model.engine()
         if not hasattr(eng, "bns_theta_grad"):
             raise NotImplementedError("BespokeNonStationary: theta training on the layer stage is not provided (the "

@@ -319,6 +319,20 @@ typedef struct CdGeomMap CdGeomMap;
  * index and value arrays (device memory allocated here); the call synchronises `stream`.  layers * rows * cols < 2^31. */
 int cd_geom_create(const float* dense_dev, int layers, int rows, int cols, int want_columns, CdGeomMap** out, void* stream);
 int cd_geom_destroy(CdGeomMap* map);
+/* The same with a pattern of its own and further views.  mask_dev (nullable): a dense DEVICE tensor of the map's shape whose
+ * non-zeros are the packed entries -- a trainable map's `mask` (:316, :341), so that entries whose value is 0 are kept (they take
+ * gradient) and values outside the mask never enter; NULL: the entries != 0 of dense_dev, as cd_geom_create.  flags:
+ * CD_GEOM_COLUMNS = want_columns (refused with a mask: that view holds values, which a refresh would leave stale);
+ * CD_GEOM_TRANSPOSED builds the transposed view of ALL packed entries cd_geom_apply_vjp and cd_plan_set_geom need: per layer and
+ * column the rows in ascending order, each with its place in the CSR arrays (no second copy of the values).  A mask without a
+ * non-zero is a valid map and gives zeros. */
+#define CD_GEOM_COLUMNS 1
+#define CD_GEOM_TRANSPOSED 2
+int cd_geom_create_ex(const float* dense_dev, const float* mask_dev /* nullable */, int layers, int rows, int cols, int flags,
+                      CdGeomMap** out, void* stream);
+/* Gathers the packed values again from a dense DEVICE tensor of the map's shape (the live `mat` of a trainable map: call it
+ * whenever the parameter changed).  One launch; the pattern and every view stay; the column view, if any, keeps its old values. */
+int cd_geom_refresh(CdGeomMap* map, const float* dense_dev, void* stream);
 /* Embeder.forward (:315-320) and Decoder.forward without sparse decoding (:340-349), with the converter's `norm` (enc :636-640,
  * dec :659-663):  y[r, l, i] = sum_j M[l, i, j] x[r, l, j]  for r < batch_rows (batch x channels);  x (batch_rows, L, cols),
  * y (batch_rows, L, rows).  scale = embed_std, shift = embed_mean: with affine_first the input is x * scale + shift (dec),
@@ -338,6 +352,19 @@ int cd_geom_apply(const CdGeomMap* map, const float* x, float* y, int batch_rows
  * rows * cols and draws its slice of the global tensor.  Two launches, no atomics: the first writes (argmax n, count) per
  * (b, l, e) into count_ws, caller memory of cd_geom_sparse_workspace_bytes; the second gathers per output row.  The map needs
  * its column view (want_columns).  Nothing is allocated and the stream is not synchronised. */
+/* Vector-Jacobian product of cd_geom_apply (same x, scale, shift, affine_first) for a cotangent gy (batch_rows, L, rows); the map
+ * needs its transposed view.  Either output may be NULL.
+ *   dx (batch_rows, L, cols):  dx[r, l, j] = sum_i M[l, i, j] gy[r, l, i], a gather over the transposed view in ascending i with
+ *       fp32 FMAs, no atomics; a row does not depend on batch_rows.  The affine rides along: gy / scale first (enc form), or the
+ *       sum times scale (dec form, affine_first).
+ *   dm (L, rows, cols), dense:  dm[l, i, j] = sum_r gy[r, l, i] x[r, l, j] on every packed entry -- for a map over a mask, every
+ *       masked entry, also where the value is 0 -- and exact zeros everywhere else, which is autograd's gradient of `mat * mask`
+ *       (the slot is cleared by a memset on the stream, then one thread per packed entry writes its sum).  The batch sum is
+ *       plain ascending r, fp32 FMAs, no atomics: repeated calls are bitwise equal.  x enters as cd_geom_apply reads it
+ *       (x * scale + shift with affine_first) and gy as above.
+ * Nothing is allocated and the stream is not synchronised. */
+int cd_geom_apply_vjp(const CdGeomMap* map, const float* x, const float* gy, float* dx /* nullable */, float* dm /* nullable */,
+                      int batch_rows, float scale, float shift, int affine_first, void* stream);
 int cd_geom_sparse_workspace_bytes(const CdGeomMap* map, int batch, size_t* bytes);
 int cd_geom_decode_sparse(const CdGeomMap* map, const float* x, float* y, int batch, int channels, int per_batch,
                           const float* rand /* nullable */, uint64_t seed, uint64_t offset, void* count_ws, void* stream);
@@ -469,6 +496,21 @@ int cd_reverse_norm_ds1(const CdRadialMap* map, const float* unconv_w /* nullabl
  * map, or that clears one, synchronises `stream` and drops the cached step graphs; call cd_plan_grad_layout and the workspace queries after. */
 int cd_plan_set_radial(CdPlan* plan, const CdRadialMap* map /* nullable */, const float* enc_w, const float* dec_w, int want_grads,
                        void* stream);
+
+/* The same seam with HGCal's maps (HGCalConverter inside forward, calodiffusion.py:86-98, 113-117): the per-sample state of the
+ * calls above becomes layers x cells floats, shape (batch, 1, L, cells), and
+ *   denoise(x) = combine(x, dec(F(enc(c_in x))))
+ * with enc = cd_geom_apply(enc_map) and dec = cd_geom_apply(dec_map), both plain (in-model the converter has no `norm`); the same
+ * two launches more per denoise, embed-out with the objective's combination and cd_ddim_sample's fused update.  The maps are
+ * read in place by every later call and must outlive their use; a trainable map's values are refreshed by cd_geom_refresh.
+ * want_grads: two DENSE gradient slots, (L, grid, cells) for enc_map and (L, cells, grid) for dec_map, follow the U-Net's in the
+ * flat gradient buffer (cd_plan_grad_layout: idx = cd_plan_num_weights and + 1), written as cd_geom_apply_vjp's dm.  0 (frozen
+ * maps): the slots do not exist, no weight-gradient work runs, cd_train_step launches dec's input gradient only and
+ * cd_denoise_vjp enc's too.  Refused with CD_EINVAL before anything touches the device: maps whose (layers, rows) -- enc's -- or
+ * (layers, cols) -- dec's -- is not the plan's (L, alpha * r), whose cell counts disagree, or without a transposed view.
+ * Setting one kind of embedding clears the other; enc_map = NULL clears this one.  Synchronises and drops the step graphs as
+ * cd_plan_set_radial does; cd_bns_theta_grad refuses such a plan. */
+int cd_plan_set_geom(CdPlan* plan, const CdGeomMap* enc_map /* nullable */, const CdGeomMap* dec_map, int want_grads, void* stream);
 
 /* ---- LayerDiffusion's layer-energy model --------------------------------------------------------------------------
  * The conditional residual MLP `ResNet` (calodiffusion/models/models.py:391-457) that LayerDiffusion
