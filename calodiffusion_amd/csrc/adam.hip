@@ -1,5 +1,5 @@
 // Fused Adam (cd_adam_step).
-#include "plan_internal.h"
+#include "guarded.h"
 
 #include <cmath>
 

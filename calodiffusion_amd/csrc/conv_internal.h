@@ -6,7 +6,7 @@
 //   kernels_conv_flat16.hip     flat-range kernel on the 16-bit pipes: conv3_flat_bf16x3_kernel (bf16x3 / f16x2)
 //   kernels_conv_transpose.hip  transposed conv;  kernels_pointwise.hip  1x1x1 conv;  kernels_init_conv.hip  init conv
 #pragma once
-#include "cd_common.h"
+#include "kernels_conv.h"
 #include "split16.h"
 #include <cstdio>
 #include <cstdlib>

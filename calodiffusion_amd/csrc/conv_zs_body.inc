@@ -1,5 +1,5 @@
 // Device bodies of the z-slide convolution (see kernels_conv_zs.hip for the scheme): the argument block, the LDS geometry and the
-// wave programs of both forms.  An include fragment, read inside namespace cd after cd_common.h, split16.h and gn_defer.h, by the
+// wave programs of both forms.  An include fragment, read inside namespace cd after kernels_conv.h, split16.h and gn_defer.h, by the
 // translation units that build kernels from these bodies: kernels_conv_zs.hip (the stand-alone launches) and
 // kernels_deep_side.hip (the deepest level's launch, whose spare workgroups run z3_wave on a K-block of a level-0 conv).
 // Both units are compiled with -amdgpu-mfma-vgpr-form (build.py), which z3_wave's register plan assumes.

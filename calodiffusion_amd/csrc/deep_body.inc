@@ -1,5 +1,5 @@
 // Device bodies and launch arguments of the deepest level's one-launch form (see kernels_deep.hip for the scheme).  An include
-// fragment, read inside namespace cd after cd_common.h and split16.h, by the translation units that build kernels from
+// fragment, read inside namespace cd after kernels_conv.h and split16.h, by the translation units that build kernels from
 // deep_level_body: kernels_deep.hip (the level alone) and kernels_deep_side.hip (the level with a side job on the spare CUs).
 namespace {
 

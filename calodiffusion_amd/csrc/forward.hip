@@ -2,6 +2,9 @@
 // run one forward (cd_unet_forward, cd_denoise*, the hybrid_weight loss).  Nothing here allocates or synchronises inside a compute
 // call, so a sampler step is hipGraph-capturable.
 #include "plan_internal.h"
+#include "kernels_attn.h"
+#include "kernels_deep.h"
+#include "kernels_loss.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -260,16 +263,16 @@ float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpa
     yu = nsp;
     ypart = ws->get<float>((size_t)r.B * cap * C * 2);
     if (!r.dry() && single) {
-      launch_attn_small(x, C, coefn, w.qkv16, part, w.ow, 0.17677669529663689f /* 32^-1/2 */, w.ob, w.gg, w.gb, y, ypart, r.B, vox,
+      launch_attn_small(x, C, coefn, w.qkv16, part, w.ow, kAttnScale, w.ob, w.gg, w.gb, y, ypart, r.B, vox,
                         r.s, dnp, r.status, cap, w.coop_sync);
     } else if (!r.dry()) {
       launch_attn_kv_context(x, C, coefn, w.qkv16, part, r.B, vox, nsp, r.s, dnp, r.status, momb);
       if (sep_combine) {
-        launch_attn_combine(part, nsp, w.ow, C, wpb, r.B, 0.17677669529663689f /* 32^-1/2 */, r.s, nullptr, nullptr, true);
+        launch_attn_combine(part, nsp, w.ow, C, wpb, r.B, kAttnScale, r.s, nullptr, nullptr, true);
         launch_attn_out(x, C, coefn, w.qkv16, wpb, w.ob, y, ypart, r.B, vox, nsp, r.s, dnp, nullptr, nullptr, 0.f, r.status);
       } else {
         launch_attn_out(x, C, coefn, w.qkv16, nullptr, w.ob, y, moments ? nullptr : ypart, r.B, vox, nsp, r.s, dnp, part, w.ow,
-                        0.17677669529663689f, r.status, momb, w.gg, w.gb);
+                        kAttnScale, r.status, momb, w.gg, w.gb);
       }
     }
     if (momb) ws->release(momb);
@@ -280,29 +283,16 @@ float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpa
     ws->release(wpb);
   } else {
     float* qkv = ws->get<float>((size_t)r.B * vox * 96);
-    if (!r.dry()) {
-      PointwiseArgs a;
-      a.in0 = x; a.ld0 = C; a.c0 = C; a.wpk = w.qkv; a.out = qkv; a.batch = r.B; a.cout = 96; a.vox = vox;
-      a.prologue = A_AFFINE; a.coef = coefn;
-      launch_pointwise(a, r.s);
-    }
+    // (coefn's block is free for the requests below: only the first launch of the sequence reads the table, and the launches that
+    // write what may then lie there follow it on the stream)
     ws->release(coefn);
     const int nsp = attn_nsplit_for(vox, r.B);
     float* part = ws->get<float>(attn_partial_floats(r.B, nsp));
     float* wpb = ws->get<float>((size_t)r.B * CT * 1024);
-    if (!r.dry()) {
-      launch_attn_context(qkv, part, r.B, vox, nsp, r.s);
-      launch_attn_combine(part, nsp, w.ow, C, wpb, r.B, 0.17677669529663689f /* 32^-1/2 */, r.s);
-    }
     y = ws->get<float>((size_t)r.B * vox * C);
     yu = pointwise_units(vox);
     ypart = ws->get<float>((size_t)r.B * yu * C * 2);
-    if (!r.dry()) {
-      PointwiseArgs a;
-      a.in0 = qkv; a.ld0 = 96; a.off0 = 0; a.c0 = 32; a.wpk = wpb; a.w_batch_stride = (int64_t)CT * 1024; a.bias = w.ob;
-      a.out = y; a.batch = r.B; a.cout = C; a.vox = vox; a.prologue = A_SOFTMAX32; a.ch_part = ypart;
-      launch_pointwise(a, r.s);
-    }
+    if (!r.dry()) launch_attn_unfused(x, C, coefn, w.qkv, w.ow, w.ob, qkv, part, nsp, wpb, y, ypart, r.B, vox, r.s);
     ws->release(part);
     ws->release(wpb);
     ws->release(qkv);

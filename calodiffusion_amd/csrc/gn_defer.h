@@ -6,7 +6,7 @@
 // small reduction for its sample: units x C pairs from L2, fp64, FIXED order (8 interleaved slices per channel combined in a
 // fixed tree) => deterministic and identical in all workgroups.
 #pragma once
-#include "cd_common.h"
+#include "kernels_gn.h"
 
 namespace cd {
 

@@ -5,7 +5,7 @@
 //                                    cores -> exp(k - max) and the un-normalised context  ctx[d][e] = sum_n e^{k[n][d]-m[d]} v[n][e]
 //                                    straight from the accumulator registers (the projection's C layout IS the A/B layout of
 //                                    the context MFMA); per-workgroup {max, sum, ctx} partials, merged log-sum-exp style by
-//                                    attn_combine_kernel (kernels_norm_attn.hip), which also folds W_out into per-sample weights
+//                                    attn_combine_kernel (kernels_attn_unfused.hip), which also folds W_out into per-sample weights
 //   pass 2  attn_out_kernel          x -> xn -> q^T = W_q xn^T (channels in registers => the 32-way softmax over channels is
 //                                    lane-local) -> y = softmax(q) W'^T + b with the q^T registers as the A operand -> y and its
 //                                    channel statistics (for the GroupNorm(1) that follows)
@@ -14,8 +14,7 @@
 // The q / k / v projections run on the fp16 matrix pipe with the convs' f16x2 split (split16.h: fp32-grade rounding, 3 MFMAs
 // per 16 channels instead of 16 f32 MFMAs at half the rate); the context and output products take their operands from
 // accumulator registers and stay on v_mfma_f32_32x32x2_f32.
-#include "cd_common.h"
-#include "conv_internal.h"
+#include "kernels_attn.h"
 #include "gn_defer.h"
 #include "split16.h"
 
@@ -425,7 +424,7 @@ __global__ void __launch_bounds__(512) attn_kv_context_kernel(AttnArgs a) {
 }
 
 // Merge of the pass-1 partials and fold of the context into the output projection, by every workgroup of pass 2 for its own
-// sample (same arithmetic, in the same order, as attn_combine_kernel, kernels_norm_attn.hip: the separate launch was 11 us of
+// sample (same arithmetic, in the same order, as attn_combine_kernel, kernels_attn_unfused.hip: the separate launch was 11 us of
 // pure latency per attention block):  W'[c][d] = scale * sum_e W_out[c][e] ctx[d][e] / sum[d]  in the k-slot order of an
 // accumulator-register A operand, into sW[NCH][4][64][4].
 // MOM: also the closing GroupNorm(1, C) of the block, whose statistics follow from the fold and the pass-1 moments without y ever

@@ -1,8 +1,8 @@
 // Elementwise pieces of the linear attention's backward: the channel softmax of q and its backward, the backward of k's voxel
 // softmax, and the per-sample 32x32 weight images of the context (plain / transposed).  The contractions themselves run on the
-// pointwise conv and the per-sample 1x1 weight gradient (train.hip: attn_block_bwd).  Forward: kernels_norm_attn.hip; reference
+// pointwise conv and the per-sample 1x1 weight gradient (train.hip: attn_block_bwd).  Forward: kernels_attn_unfused.hip; reference
 // LinearAttention.forward, models.py:301-318.
-#include "cd_common.h"
+#include "kernels_bwd.h"
 
 namespace cd {
 

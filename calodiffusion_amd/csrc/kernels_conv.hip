@@ -34,7 +34,7 @@ int conv_precision() {
 void set_conv_precision(int p) { g_conv_precision = p; }
 
 // ------------------------------------------------------------------------------------------------------------
-// weight packing (see cd_common.h for the layout)
+// weight packing (see kernels_conv.h for the layout)
 // ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void pack_weights_elem(size_t idx, const float* __restrict__ w, float* __restrict__ wpk, int cout, int cin,
                                                   int taps, int transposed, int flip) {

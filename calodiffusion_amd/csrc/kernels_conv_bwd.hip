@@ -2,7 +2,7 @@
 // gradients (kernels_wgrad.hip): the bias gradient from channel partials, the fan-in of gradient slices of a channel concat, the
 // input gradient of the strided conv on an odd phi ring, and the phi fold of the transposed conv's odd output ring.  Reference:
 // torch autograd through CylindricalConv / CylindricalConvTrans (models.py:25-96); host side: conv_backward.hip.
-#include "cd_common.h"
+#include "kernels_bwd.h"
 
 namespace cd {
 

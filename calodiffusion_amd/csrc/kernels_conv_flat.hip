@@ -18,7 +18,7 @@ namespace cd {
 // The 27 taps are fully unrolled: weight fragments (1-KiB wave loads, L1/L2 resident) and LDS fragments of tap t+1
 // are in flight while the 8*VT*CT MFMAs of tap t issue.
 // Sub-chunk k' of a 32-channel chunk = channels [8k', 8k'+8) (lane half 0) and [16+8k', 16+8k'+8) (lane half 1), so the
-// packed weight layout of cd_common.h is used unchanged (fragments q = 2k', 2k'+1).
+// packed weight layout of kernels_conv.h is used unchanged (fragments q = 2k', 2k'+1).
 // ------------------------------------------------------------------------------------------------------------
 template <int VT, int CT>
 __global__ void __launch_bounds__(512, (VT * CT <= 2 ? 3 : 2)) conv3_flat_kernel(ConvFlatArgs a) {

@@ -11,7 +11,7 @@
 //    through a 6-deep register ring and applies each to all (<= 4) row tiles of the sample: 3 MFMAs per tile and pair;
 //  * the four K-slices of every tile are exchanged through LDS, wave t sums tile t, adds the bias, stores and accumulates the
 //    channel statistics; the workgroup has seen the whole sample, so it emits ONE partial per (sample, channel).
-#include "cd_common.h"
+#include "kernels_conv.h"
 #include "split16.h"
 #include "gn_defer.h"
 

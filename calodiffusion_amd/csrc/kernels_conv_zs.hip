@@ -19,7 +19,7 @@
 //  * a step = 128 output voxels = 4 row tiles; every wave runs its K-slice over all 4 tiles, the partial 32x32 tiles
 //    are exchanged through LDS (48 KiB) and wave t sums, adds bias, stores and accumulates the channel statistics of
 //    tile t.  Fixed summation order => deterministic.
-#include "cd_common.h"
+#include "kernels_conv.h"
 #include "split16.h"
 #include "gn_defer.h"
 
@@ -62,7 +62,7 @@ __global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, u32x4* __
   if (idx >= total) return;
   pack_weights_f16x2_elem(idx, w, wpk, cout, cin, taps, transposed, flip);
 }
-// the f16x2 images of every tensor of a plan in one launch (PackJob, cd_common.h): blockIdx.y = job
+// the f16x2 images of every tensor of a plan in one launch (PackJob, kernels_conv.h): blockIdx.y = job
 __global__ void __launch_bounds__(256) pack_jobs_f16x2_kernel(const PackJob* __restrict__ jobs) {
   const PackJob j = jobs[blockIdx.y];
   if (!j.f16) return;

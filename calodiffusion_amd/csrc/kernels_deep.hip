@@ -22,7 +22,8 @@
 //  * linear attention = the arithmetic of kernels_attn.hip's single-launch form with x read from / written to LDS.
 //
 // The reference ops: ResnetBlock models.py:172-200, Block :147-169, LinearAttention / PreNorm / Residual :281-329, 111-117.
-#include "cd_common.h"
+#include "kernels_deep.h"
+#include "kernels_conv.h"
 #include "split16.h"
 
 #include <cstdio>

@@ -12,7 +12,8 @@
 // never wait for each other (no flags, no atomics between them): the only consumer of the side job's output is the later x-half
 // launch on the same stream.  Both roles need a whole CU (256 threads at 512 registers, > 80 KB of LDS), so the launch has the
 // resources of the larger of the two and loses no occupancy.
-#include "cd_common.h"
+#include "kernels_deep.h"
+#include "kernels_conv.h"
 #include "split16.h"
 #include "gn_defer.h"
 

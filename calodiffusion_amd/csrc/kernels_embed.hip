@@ -1,5 +1,5 @@
 // The conditioning MLPs of the U-Net (backward: kernels_embed_bwd.hip).
-#include "cd_common.h"
+#include "kernels_embed_head.h"
 
 namespace cd {
 

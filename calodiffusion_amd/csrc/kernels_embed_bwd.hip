@@ -1,7 +1,7 @@
 // Backward of the conditioning MLPs (time / energy embeddings and the ResnetBlock projections of CondUnet; forward: embed_kernel
 // in kernels_embed.hip): embed_bwd_kernel leaves every Linear's input and output delta per sample on a tape, linear_wgrad_kernel
 // forms the weight and bias gradients from it.
-#include "cd_common.h"
+#include "kernels_bwd.h"
 
 namespace cd {
 

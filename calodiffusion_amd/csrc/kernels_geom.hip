@@ -3,7 +3,8 @@
 // generate_sparse_mat's sampled decode in two gather passes, and the HGCal forward pre-processing, which applies the packed encoder
 // inside its own launch (cd_preprocess_hgcal).  Kernels and their C ABI; nothing here touches a plan.
 #include "philox.h"
-#include "plan_internal.h"
+#include "guarded.h"
+#include "kernels_geom.h"
 
 #include <climits>
 #include <type_traits>

@@ -10,7 +10,9 @@
 //           preconditioning rides in its staging (c_in) and its epilogue, written as radial_collapse_kernel writes them.
 //   wgrad   a thread per packed entry (l, i, j): dm[l, i, j] = sum_r gy[r, l, i] x[r, l, j] in plain ascending r, written into the
 //           dense slot its launcher cleared.  Entries of a row are neighbours, so gy is a broadcast and x nearly coalesced.
-#include "plan_internal.h"
+#include "guarded.h"
+#include "kernels_embed_head.h"
+#include "kernels_geom.h"
 
 namespace cd {
 namespace {

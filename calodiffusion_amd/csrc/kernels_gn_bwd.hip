@@ -1,8 +1,9 @@
 // GroupNorm(+SiLU)(+add) backward: the statistics pass, its finalize, the elementwise pass, the one-workgroup-per-sample form
 // for small tensors, and the batch reduction of the parameter gradients (alone or as queued jobs).  Reference: torch autograd
 // through the nn.GroupNorm + SiLU of Block / ResnetBlock (models.py:147-201) and the norms around LinearAttention
-// (models.py:281-333); forward: kernels_norm_attn.hip (launch_gn_finalize / launch_gn_apply).
-#include "cd_common.h"
+// (models.py:281-333); forward: kernels_gn.hip (launch_gn_finalize / launch_gn_apply).
+#include "kernels_bwd.h"
+#include "kernels_gn.h"
 #include <cstdlib>
 
 namespace cd {

@@ -1,5 +1,5 @@
 // The output head with the EDM pre-conditioning and the samplers' fused update (backward: kernels_head_bwd.hip).
-#include "cd_common.h"
+#include "kernels_embed_head.h"
 #include "gn_defer.h"
 
 namespace cd {

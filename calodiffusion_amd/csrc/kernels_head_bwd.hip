@@ -1,7 +1,8 @@
 // Backward of the output head (forward: head_kernel in kernels_head.hip): fused with the loss gradient for the training step
 // (head_loss_bwd_kernel; the loss types and objectives of models/loss.py) and from a caller's dL/dD for cd_denoise_vjp
 // (head_vjp_kernel); head_grad_reduce_kernel sums the blocks' partial weight / bias gradients in a fixed order.
-#include "cd_common.h"
+#include "kernels_bwd.h"
+#include "kernels_loss.h"
 
 namespace cd {
 

@@ -1,7 +1,8 @@
 // Backward of the init conv (cin <= 4 logical channels: c_in * x and the synthesised coordinate channels; forward:
 // kernels_init_conv.hip): the input gradient of the data channel with the EDM preconditioning in its epilogue (cd_denoise_vjp),
 // and the weight gradient -- a scalar kernel, or the general 3x3x3 weight-gradient ladder on a padded 32-channel input.
-#include "cd_common.h"
+#include "kernels_bwd.h"
+#include "kernels_wgrad.h"
 
 namespace cd {
 

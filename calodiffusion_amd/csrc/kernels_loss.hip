@@ -1,5 +1,5 @@
 // The training loss on the denoiser's output (its gradient: kernels_head_bwd.hip).
-#include "cd_common.h"
+#include "kernels_loss.h"
 
 namespace cd {
 

@@ -4,7 +4,7 @@
 // all sampler steps with the state in LDS: no per-step launches, no intermediate in HBM.  The ~0.7 M weights (2.7 MB) stream
 // from L2 every step; a wave owns 8 output rows at a time so 8 independent 1-KiB row reads are in flight per wave
 // (16 rows x 16 waves measured 3x slower: register pressure).
-#include "cd_common.h"
+#include "kernels_mlp.h"
 #include "philox.h"
 #include "../../include/calodiff.h"
 

@@ -9,7 +9,9 @@
 // 20 Linear layers go to a per-sample tape in HBM and linear_wgrad_kernel (kernels_embed_bwd.hip) forms all weight / bias gradients
 // (sums over the batch, fixed order => deterministic) in one more launch; its job table is written by the taping kernel itself,
 // so nothing here copies from the host or synchronises.  Forward and backward are device functions shared by the kernels.
-#include "cd_common.h"
+#include "kernels_mlp.h"
+#include "kernels_bwd.h"
+#include "kernels_loss.h"
 
 #include <algorithm>
 #include <cmath>

@@ -1,5 +1,5 @@
 // Dataset-2/3 showers between physical and normalised space: cd_reverse_norm, cd_reverse_norm_staged and cd_preprocess.
-#include "plan_internal.h"
+#include "guarded.h"
 
 namespace cd {
 

@@ -22,7 +22,10 @@
 // arithmetic in their staging and epilogue (Ds1Args::on): expand<ENC> scales the staged shower and ends in logit-norm, collapse<DEC>
 // stages reverse_logit and ends in the energy scaling and the read-out threshold.  Its flat form needs no matrices: two kernels of
 // their own over the ragged segments [bound[i], bound[i+1]), a shower in LDS and a wave per layer.
-#include "plan_internal.h"
+#include "guarded.h"
+#include "kernels_embed_head.h"
+#include "kernels_geom.h"
+#include "kernels_loss.h"
 
 #include <vector>
 

@@ -1,5 +1,5 @@
 // What the sampler loops launch around the network (sampler.hip): step scalars, Philox noise and the step-program ops.
-#include "cd_common.h"
+#include "kernels_sampler.h"
 #include "philox.h"
 
 namespace cd {

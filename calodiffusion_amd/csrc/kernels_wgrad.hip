@@ -583,7 +583,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce1_kernel(const float* __restr
   wgrad_reduce1_block(partial + (size_t)n * sample_stride_partial, dw + (size_t)n * sample_stride_out, A, Bc, T, nslots, b_total, b_off,
                       blockIdx.x);
 }
-// All queued slot reductions of a training step in one launch (WgradReduceQueue, cd_common.h): a block finds its job by binary
+// All queued slot reductions of a training step in one launch (WgradReduceQueue, kernels_wgrad.h): a block finds its job by binary
 // search over the jobs' first blocks.
 struct WgradReduceJobs {
   WgradReduceJob job[WgradReduceQueue::kMax];

@@ -13,7 +13,6 @@
 //    pairs in registers across ALL its units; per 16-voxel K step it reads the dy fragments once (4 transposed loads) and
 //    per tap the shifted x fragments (4 loads) for 3 MFMAs;
 //  * one partial [27][32][32] per workgroup, summed in a fixed order by wgrad_reduce_kernel (deterministic).
-#include "cd_common.h"
 #include "split16.h"
 #include "wgrad_internal.h"
 

@@ -1,6 +1,8 @@
 // Entry points of LayerDiffusion's layer-energy MLP: forward, denoise, sampler, sampler programs, training step, loss and VJP
 // (kernels: kernels_mlp.hip, kernels_mlp_train.hip).
-#include "plan_internal.h"
+#include "guarded.h"
+#include "kernels_mlp.h"
+#include "kernels_sampler.h"
 
 #include <vector>
 

@@ -1,6 +1,7 @@
 // Host side of the C ABI (include/calodiff.h): plan construction, the weight arena, coordinates, status and gradient layout.
 // The launch sequences are in forward.hip, sampler.hip and train.hip.
 #include "plan_internal.h"
+#include "kernels_attn.h"
 
 #include <array>
 #include <cstdio>

@@ -1,9 +1,17 @@
-// Internal interface of the library's host units (plan.hip, forward.hip, conv_backward.hip, sampler.hip, train.hip, ops.hip,
-// bns.hip, layer.hip and the entry points that share a file with their kernels): the plan and its weight records, the workspace allocator, the launch-sequence pieces more than one unit calls, and the wrappers
-// every C-ABI entry point runs in.  The public ABI is include/calodiff.h.
+// Internal interface of the host units that walk the network (plan.hip, forward.hip, conv_backward.hip, sampler.hip, train.hip,
+// ops.hip, bns.hip): the plan and its weight records, the launch-sequence pieces more than one unit calls, and the dry-run and
+// range-fallback wrappers around them.  The workspace allocator is arena.h, the entry points' wrapper guarded.h; the units that
+// never see a plan include those alone.  The public ABI is include/calodiff.h.
 #pragma once
-#include "../../include/calodiff.h"
-#include "cd_common.h"
+#include "arena.h"
+#include "guarded.h"
+#include "kernels_bwd.h"
+#include "kernels_conv.h"
+#include "kernels_embed_head.h"
+#include "kernels_geom.h"
+#include "kernels_gn.h"
+#include "kernels_sampler.h"
+#include "kernels_wgrad.h"
 
 #include <map>
 #include <string>
@@ -52,68 +60,6 @@ struct LevelW {
   int sw = -1, sb = -1;  // down / up sampling conv
 };
 
-// ------------------------------------------------------------------------------------------------------------
-// workspace allocator: deterministic first-fit over the caller's workspace, replayed identically by a dry run
-// (to size the workspace) and by every real call (so captured graphs see stable addresses).
-// ------------------------------------------------------------------------------------------------------------
-class Arena {
- public:
-  void reset(char* base, size_t cap, bool dry) {
-    base_ = base; cap_ = cap; dry_ = dry; high_ = 0;
-    blocks_.clear();
-    blocks_.push_back({0, (size_t)1 << 60, true});
-  }
-  void* alloc(size_t bytes) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (bytes == 0) bytes = 256;
-    for (size_t i = 0; i < blocks_.size(); ++i) {
-      if (blocks_[i].free && blocks_[i].size >= bytes) {
-        const size_t off = blocks_[i].off;
-        if (blocks_[i].size > bytes) {
-          Block rest{off + bytes, blocks_[i].size - bytes, true};
-          blocks_[i].size = bytes;
-          blocks_.insert(blocks_.begin() + i + 1, rest);
-        }
-        blocks_[i].free = false;
-        if (off + bytes > high_) high_ = off + bytes;
-        if (!dry_ && off + bytes > cap_) throw Fail{CD_EWORKSPACE, "workspace too small: call cd_plan_workspace_bytes for this batch size"};
-        return dry_ ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base_ + off);
-      }
-    }
-    throw Fail{CD_EWORKSPACE, "workspace allocator exhausted"};
-  }
-  template <typename T>
-  T* get(size_t count) { return (T*)alloc(count * sizeof(T)); }
-  void release(const void* p) {
-    if (!p) return;
-    const size_t off = dry_ ? (size_t)((uintptr_t)p - 0x1000) : (size_t)((const char*)p - base_);
-    for (size_t i = 0; i < blocks_.size(); ++i) {
-      if (blocks_[i].off == off && !blocks_[i].free) {
-        blocks_[i].free = true;
-        if (i + 1 < blocks_.size() && blocks_[i + 1].free) {
-          blocks_[i].size += blocks_[i + 1].size;
-          blocks_.erase(blocks_.begin() + i + 1);
-        }
-        if (i > 0 && blocks_[i - 1].free) {
-          blocks_[i - 1].size += blocks_[i].size;
-          blocks_.erase(blocks_.begin() + i);
-        }
-        return;
-      }
-    }
-    throw Fail{CD_EINVAL, "internal: release of unknown workspace block"};
-  }
-  size_t high() const { return high_; }
-  bool dry() const { return dry_; }
-
- private:
-  struct Block { size_t off, size; bool free; };
-  std::vector<Block> blocks_;
-  char* base_ = nullptr;
-  size_t cap_ = 0, high_ = 0;
-  bool dry_ = false;
-};
-
 // A sampler entry point's cached step graph (cd_ddim_sample, cd_sampler_run: one each), valid while the call's key matches the
 // one it was captured under
 struct StepGraph {
@@ -144,39 +90,6 @@ struct StepGraph {
 }  // namespace cd
 
 using namespace cd;
-
-// Layout of one Dataset-1 geometry (cd_radial_create, kernels_radial.hip)
-struct CdRadialMap {
-  int layers = 0, A = 0, R = 0, V = 0, wtotal = 0;
-  int4* lay = nullptr;  // device, per layer {bound, alpha, rin, float offset of its matrix}
-  int* vlay = nullptr;  // device, layer of every voxel
-  ~CdRadialMap() {
-    if (lay) (void)hipFree(lay);
-    if (vlay) (void)hipFree(vlay);
-  }
-};
-
-// One packed HGCal map (cd_geom_create*, kernels_geom.hip).  row_ptr / col_ptr / t_ptr run over all layers: row i of layer l
-// holds entries [row_ptr[l rows + i], row_ptr[l rows + i + 1])
-struct CdGeomMap {
-  int layers = 0, rows = 0, cols = 0, nnz = 0;
-  bool masked = false;     // the pattern is a mask (a trainable map), not the values != 0
-  int* row_ptr = nullptr;  // layers * rows + 1
-  int* col_idx = nullptr;  // nnz, ascending within a row
-  float* val = nullptr;
-  int* ent_row = nullptr;  // nnz: l rows + i of every entry
-  int* col_ptr = nullptr;  // layers * cols + 1, or null: no column view
-  int* row_idx = nullptr;  // entries > SPARSE_EPS, ascending within a column
-  float* cval = nullptr;
-  int* t_ptr = nullptr;    // layers * cols + 1, or null: no transposed view
-  int* t_row = nullptr;    // nnz: all entries, rows ascending within a column
-  int* t_pos = nullptr;    // nnz: the entry's place in col_idx / val
-  ~CdGeomMap() {
-    for (void* p : {(void*)row_ptr, (void*)col_idx, (void*)val, (void*)ent_row, (void*)col_ptr, (void*)row_idx, (void*)cval,
-                    (void*)t_ptr, (void*)t_row, (void*)t_pos})
-      if (p) (void)hipFree(p);
-  }
-};
 
 struct CdPlan {
   CdUnetDesc desc{};
@@ -365,22 +278,7 @@ void conv_transpose_backward(Run& r, const float* x, const float* w_raw, const f
 EmbedArgs embed_args(CdPlan* p, int B, const float* cond, const float* t, int kind, float* emb, float* scal);
 void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const float* t, float* out, bool raw, hipStream_t s,
                   const FwdOpts* opt = nullptr);
-// The launches of a plan's flat-state embedding around its U-Net, one set per kind (kernels_radial.hip, kernels_geom_embed.hip).
-// scal: (B, 4) of launch_embed
-void radial_embed_in(const CdRadialMap* m, const float* enc_w, const float* x, const float* scal, float* g, int batch, hipStream_t s);
-void radial_embed_out(const CdRadialMap* m, const float* dec_w, const float* F, const float* x, const float* scal, int objective,
-                      float* out, const HeadArgs* upd, int batch, hipStream_t s);
-void radial_embed_dec_vjp(const CdRadialMap* m, const float* dec_w, const float* F, const float* gf, float* dF, float* dd, int batch,
-                          hipStream_t s);
-void radial_embed_enc_vjp(const CdRadialMap* m, const float* enc_w, const float* x, const float* dg, const float* gy,
-                          const float* scal, int objective, float* dx, float* dw, int batch, hipStream_t s);
-void geom_embed_in(const CdGeomMap* enc, const float* x, const float* scal, float* g, int batch, hipStream_t s);
-void geom_embed_out(const CdGeomMap* dec, const float* F, const float* x, const float* scal, int objective, float* out,
-                    const HeadArgs* upd, int batch, hipStream_t s);
-void geom_embed_dec_vjp(const CdGeomMap* dec, const float* F, const float* gf, float* dF, float* dd, int batch, hipStream_t s);
-void geom_embed_enc_vjp(const CdGeomMap* enc, const float* x, const float* dg, const float* gy, const float* scal, int objective,
-                        float* dx, float* dw, int batch, hipStream_t s);
-// ... and the one interface forward.hip and train.hip call.
+// The one interface to a plan's flat-state embedding that forward.hip and train.hip call (the launches per kind: kernels_geom.h).
 // g (B, grid) = enc(c_in x)
 inline void launch_embed_in(const CdPlan::FlatEmbed& e, const float* x, const float* scal, float* g, int batch, hipStream_t s) {
   if (e.map) radial_embed_in(e.map, e.enc_w, x, scal, g, batch, s);
@@ -392,9 +290,6 @@ inline void launch_embed_out(const CdPlan::FlatEmbed& e, const float* F, const f
   if (e.map) radial_embed_out(e.map, e.dec_w, F, x, scal, objective, out, upd, batch, s);
   else geom_embed_out(e.gdec, F, x, scal, objective, out, upd, batch, s);
 }
-// gf (B, V), the cotangent of dec(F): from the loss (gy null; x0, data, noise) or from a caller's cotangent gy of the output
-void launch_embed_cotangent(const float* x0, const float* data, const float* noise, const float* gy, const float* scal, float* gf,
-                            int batch, int64_t per, int loss_type, int objective, hipStream_t s);
 // dF = dec's VJP of gf, and dd (nullable) = the gradient of dec's map
 inline void launch_embed_dec_vjp(const CdPlan::FlatEmbed& e, const float* F, const float* gf, float* dF, float* dd, int batch,
                                  hipStream_t s) {
@@ -410,39 +305,10 @@ inline void launch_embed_enc_vjp(const CdPlan::FlatEmbed& e, const float* x, con
 }
 // plan.hip
 void check_ready(CdPlan* p, bool need_coords);
-// sampler.hip: the one check of a step program (host arrays; op_begin null = uniform), for cd_sampler_run and cd_layer_sampler_run
-struct SamplerProgramCounts {
-  int randn_per_step = 0;  // RANDN ops in the op list
-  int64_t n_denoise = 0;   // DENOISE ops the program executes
-};
-SamplerProgramCounts validate_sampler_program(const CdSamplerOp* ops, const int32_t* op_begin, int n_steps, int n_ops, int n_bufs,
-                                              int n_coef, int batch);
 // train.hip
 void dgrad_images(CdPlan* p);  // lays out the input-gradient weight images once per plan (before any backward pass)
 void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, const float* cond, const float* gy, float* dx, float* grads,
                       bool param_grads, hipStream_t s);
-
-// Every C-ABI entry point runs inside guarded().  The launchers check `hipGetLastError()` after each launch, and that call
-// reports the thread's LAST error whoever set it -- a HIP call that failed earlier in the process (another library's, the
-// caller's own, or a previous entry point of this one) would otherwise fail the first unrelated launch here (round 3:
-// a refused hipEventElapsedTime surfaced as "cd_randn: invalid resource handle").  So the error state is cleared on the way
-// in, and again on the way out of a failed call.
-template <typename F>
-int guarded(F&& f) {
-  (void)hipGetLastError();
-  try {
-    f();
-    return CD_OK;
-  } catch (const Fail& e) {
-    (void)hipGetLastError();
-    set_error(e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    (void)hipGetLastError();
-    set_error(std::string("internal error: ") + e.what());
-    return CD_EINVAL;
-  }
-}
 
 // High-water mark of a dry run of the forward's allocation sequence (after `front`, the caller's own blocks).  The sequence
 // depends on the convolution precision (whole-block launches, fused / unfused attention), and a range fallback re-runs a call

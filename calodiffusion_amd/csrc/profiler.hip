@@ -1,6 +1,6 @@
 // Per-launch timing with HIP events on the launch stream (used by bench.py to price the dominant kernel live, in the
 // same process and on the same shapes as the timed run).  Disabled by default; never active during graph capture.
-#include "plan_internal.h"
+#include "guarded.h"
 
 #include <cstdio>
 #include <map>

@@ -7,6 +7,8 @@
 // Nothing is released between forward and backward (the tape owns the activations); temporaries of the backward are
 // released as soon as they are consumed, the weight gradients' partials once their queued reductions have been launched.
 #include "plan_internal.h"
+#include "kernels_attn.h"
+#include "kernels_loss.h"
 
 #include <cstdlib>
 
@@ -115,31 +117,17 @@ float* attn_block_train(Run& r, CdPlan* p, const AttnW& W, const float* x, Dims3
   if (!r.dry()) launch_gn_finalize(xpart, xunits, w.ng, w.nb, nullptr, 0, t.coefn, r.B, C, 1, vox, r.s, t.statn);
   if (own) ws->release(own);
   t.qkv = ws->get<float>((size_t)r.B * vox * 96);
-  if (!r.dry()) {
-    PointwiseArgs a;
-    a.in0 = x; a.ld0 = C; a.c0 = C; a.wpk = w.qkv; a.out = t.qkv; a.batch = r.B; a.cout = 96; a.vox = vox;
-    a.prologue = A_AFFINE; a.coef = t.coefn;
-    launch_pointwise(a, r.s);
-  }
   const int nsp = attn_nsplit_for(vox, r.B);
   float* part = ws->get<float>(attn_partial_floats(r.B, nsp));
   const int CT = (C + 31) / 32;
   float* wpb = ws->get<float>((size_t)r.B * CT * 1024);
   t.ctx = ws->get<float>((size_t)r.B * 1024);
   t.kstat = ws->get<float>((size_t)r.B * 64);
-  if (!r.dry()) {
-    launch_attn_context(t.qkv, part, r.B, vox, nsp, r.s);
-    launch_attn_combine(part, nsp, w.ow, C, wpb, r.B, 0.17677669529663689f, r.s, t.ctx, t.kstat);
-  }
   t.y0 = ws->get<float>((size_t)r.B * vox * C);
   const int yu = pointwise_units(vox);
   float* ypart = ws->get<float>((size_t)r.B * yu * C * 2);
-  if (!r.dry()) {
-    PointwiseArgs a;
-    a.in0 = t.qkv; a.ld0 = 96; a.off0 = 0; a.c0 = 32; a.wpk = wpb; a.w_batch_stride = (int64_t)CT * 1024; a.bias = w.ob;
-    a.out = t.y0; a.batch = r.B; a.cout = C; a.vox = vox; a.prologue = A_SOFTMAX32; a.ch_part = ypart;
-    launch_pointwise(a, r.s);
-  }
+  if (!r.dry())
+    launch_attn_unfused(x, C, t.coefn, w.qkv, w.ow, w.ob, t.qkv, part, nsp, wpb, t.y0, ypart, r.B, vox, r.s, t.ctx, t.kstat);
   ws->release(part);
   ws->release(wpb);
   t.coefg = ws->get<float>((size_t)r.B * C * 4);
@@ -306,7 +294,7 @@ float* attn_block_bwd(Run& r, CdPlan* p, const AttnTape& t, const float* dy, con
   const int64_t vox = t.dims.vox();
   const int64_t rows = (int64_t)r.B * vox;
   const Dims3 d1 = t.dims;
-  const float scale = 0.17677669529663689f;
+  const float scale = kAttnScale;
   float* scratch = ws->get<float>(gn_backward_scratch_floats(r.B, C > 96 ? C : 96, vox));
   // out = gn_g(y0) + x
   float* dy0 = ws->get<float>((size_t)rows * C);

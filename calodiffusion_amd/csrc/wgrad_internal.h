@@ -4,7 +4,7 @@
 //   kernels_wgrad16.hip   fp16 matrix pipe: stride-1 3x3x3 (ring / unit kernels) and the strided (KD,4,4) conv
 //   kernels_wgrad.hip     fp32: flat 3x3x3, streaming 1x1x1 (and, not a rung that can decline, the generic wgrad_kernel)
 #pragma once
-#include "cd_common.h"
+#include "kernels_wgrad.h"
 
 namespace cd {
 

@@ -79,7 +79,7 @@ def _fused_split(vox, B):
 
 
 def _unfused_split(vox, B):
-    """Voxel ranges per sample of attn_context_kernel: attn_nsplit_for (kernels_norm_attn.hip)."""
+    """Voxel ranges per sample of attn_context_kernel: attn_nsplit_for (kernels_attn_unfused.hip)."""
     return max(1, min(-(-1024 // B), -(-vox // 512), 128))
 
 

@@ -6,7 +6,7 @@ Every other gradient test runs at batch <= 6 (largest B*vox 40 500), where each 
 ("cap"); the shipped configs train at batch 128 / 64 / 256, where almost all of them take the batch-limited one ("want").
 
     where                                  split                                        batch-limited when
-    gn_nsplit_for (kernels_norm_attn.hip)  min(ceil(2048/B), ceil(vox/256))             B*vox > 524 288
+    gn_nsplit_for (kernels_gn.hip)         min(ceil(2048/B), ceil(vox/256))             B*vox > 524 288
     attn_nsplit_for                        min(ceil(1024/B), ceil(vox/512))             B*vox > 524 288
     gn_apply_blocks_per_sample             min(ceil(1024/B), ceil(vox/(8*rows))),       C = 32 (rows = 32): B*vox > 262 144
                                            rows = 256/(C/4)
