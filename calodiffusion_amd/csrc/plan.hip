@@ -15,48 +15,89 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 
 int add_weight(CdPlan* p, const std::string& name, int64_t numel, PackKind pk = PK_NONE, int cin = 0, int cout = 0, int taps = 0) {
   WeightEntry e;
-  e.name = name; e.numel = numel; e.pack = pk; e.cin = cin; e.cout = cout; e.taps = taps;
+  e.name = name; e.numel = numel; e.src_numel = numel; e.pack = pk; e.cin = cin; e.cout = cout; e.taps = taps;
   p->weights.push_back(e);
   p->index[name] = (int)p->weights.size() - 1;
   return (int)p->weights.size() - 1;
 }
 
-ResW add_res(CdPlan* p, const std::string& pre, int cin, int cout, bool mlp) {
+// One channel axis of a tensor: n channels as the config counts them, run as n k (kernels_widen.h).  An axis that is no U-Net
+// width (q/k/v rows, the attention's hidden inputs, the head's output, in_channels, the conditioning sizes) is plain(n).
+struct Ax {
+  int n = 0, k = 1, cpg = 1;
+  int w() const { return n * k; }
+};
+static Ax plain(int n) { return Ax{n, 1, n > 0 ? n : 1}; }
+
+// The width rule: the smallest k of {1, 2, 4} with C k a multiple of 32 (<= 256) and C k / groups a multiple of 4; 0 = none
+int widen_factor(int c, int groups) {
+  if (c <= 0 || c % groups != 0) return 0;
+  for (int k : {1, 2, 4})
+    if ((c * k) % 32 == 0 && ((c * k) / groups) % 4 == 0 && c * k <= 256) return k;
+  return 0;
+}
+
+// a tensor [out][in0 | in1][taps] (in_first: [in][out][taps]); records its map if any of its axes is widened
+int add_tensor(CdPlan* p, const std::string& name, Ax out, Ax in0, Ax in1, int taps, PackKind pk = PK_NONE, bool in_first = false) {
+  const int cin = in0.w() + in1.w();
+  const int i = pk == PK_NONE ? add_weight(p, name, (int64_t)out.w() * cin * taps)
+                              : add_weight(p, name, (int64_t)out.w() * cin * taps, pk, cin, out.w(), taps);
+  WeightEntry& e = p->weights[i];
+  e.src_numel = (int64_t)out.n * (in0.n + in1.n) * taps;
+  e.widened = out.k > 1 || in0.k > 1 || in1.k > 1;
+  WidenJob& j = e.widen;
+  j.out_w = out.w(); j.out_cpg = out.cpg; j.out_k = out.k;
+  j.in_w[0] = in0.w(); j.in_cpg[0] = in0.cpg; j.in_k[0] = in0.k;
+  j.in_w[1] = in1.w(); j.in_cpg[1] = in1.cpg; j.in_k[1] = in1.k;
+  j.taps = taps; j.in_first = in_first ? 1 : 0;
+  j.n_wide = (unsigned long long)e.numel; j.n_narrow = (unsigned long long)e.src_numel;
+  return i;
+}
+int add_vector(CdPlan* p, const std::string& name, Ax c) { return add_tensor(p, name, c, plain(1), plain(0), 1); }
+
+// A block keeps or drops its 1x1 shortcut by the config's widths, not the wide ones: a 16 -> 32 block keeps it although both
+// sides run 32 wide.
+ResW add_res(CdPlan* p, const std::string& pre, Ax in0, Ax in1, Ax out, bool mlp) {
   ResW r;
-  r.cin = cin; r.cout = cout; r.has_mlp = mlp; r.has_res = cin != cout;
+  const int cout = out.w();
+  r.cin = in0.w() + in1.w(); r.cout = cout; r.has_mlp = mlp; r.has_res = in0.n + in1.n != out.n;
+  // (without a shortcut conv the input is added to the output channel by channel: one map on both sides.  A single input of
+  // the output's width has the output's map; a concatenated one has two)
+  if (!r.has_res && in1.n > 0 && (in0.k > 1 || in1.k > 1 || out.k > 1))
+    throw Fail{CD_EINVAL, pre + ": a concatenated input added to the output without a shortcut conv cannot run widened"};
   if (mlp) {
-    r.mw = add_weight(p, pre + ".mlp.1.weight", (int64_t)cout * p->desc.cond_dim);
-    r.mb = add_weight(p, pre + ".mlp.1.bias", cout);
+    r.mw = add_tensor(p, pre + ".mlp.1.weight", out, plain(p->desc.cond_dim), plain(0), 1);
+    r.mb = add_vector(p, pre + ".mlp.1.bias", out);
     r.emb_off = p->emb_ld;
     p->emb_ld += cout;
     p->embed_list.push_back({r.mw, r.emb_off});
   }
-  r.c1w = add_weight(p, pre + ".block1.proj.conv.weight", (int64_t)cout * cin * 27, PK_CONV, cin, cout, 27);
-  r.c1b = add_weight(p, pre + ".block1.proj.conv.bias", cout);
-  r.n1g = add_weight(p, pre + ".block1.norm.weight", cout);
-  r.n1b = add_weight(p, pre + ".block1.norm.bias", cout);
-  r.c2w = add_weight(p, pre + ".block2.proj.conv.weight", (int64_t)cout * cout * 27, PK_CONV, cout, cout, 27);
-  r.c2b = add_weight(p, pre + ".block2.proj.conv.bias", cout);
-  r.n2g = add_weight(p, pre + ".block2.norm.weight", cout);
-  r.n2b = add_weight(p, pre + ".block2.norm.bias", cout);
+  r.c1w = add_tensor(p, pre + ".block1.proj.conv.weight", out, in0, in1, 27, PK_CONV);
+  r.c1b = add_vector(p, pre + ".block1.proj.conv.bias", out);
+  r.n1g = add_vector(p, pre + ".block1.norm.weight", out);
+  r.n1b = add_vector(p, pre + ".block1.norm.bias", out);
+  r.c2w = add_tensor(p, pre + ".block2.proj.conv.weight", out, out, plain(0), 27, PK_CONV);
+  r.c2b = add_vector(p, pre + ".block2.proj.conv.bias", out);
+  r.n2g = add_vector(p, pre + ".block2.norm.weight", out);
+  r.n2b = add_vector(p, pre + ".block2.norm.bias", out);
   if (r.has_res) {
-    r.rw = add_weight(p, pre + ".res_conv.conv.weight", (int64_t)cout * cin, PK_CONV, cin, cout, 1);
-    r.rb = add_weight(p, pre + ".res_conv.conv.bias", cout);
+    r.rw = add_tensor(p, pre + ".res_conv.conv.weight", out, in0, in1, 1, PK_CONV);
+    r.rb = add_vector(p, pre + ".res_conv.conv.bias", out);
   }
   return r;
 }
 
-AttnW add_attn(CdPlan* p, const std::string& pre, int c) {
+AttnW add_attn(CdPlan* p, const std::string& pre, Ax c) {
   AttnW a;
-  a.c = c;
-  a.qkv = add_weight(p, pre + ".fn.fn.to_qkv.conv.weight", (int64_t)96 * c, PK_CONV, c, 96, 1);
-  a.ow = add_weight(p, pre + ".fn.fn.to_out.0.conv.weight", (int64_t)c * 32);
-  p->weights[a.ow].cin = 32; p->weights[a.ow].cout = c; p->weights[a.ow].taps = 1; p->weights[a.ow].dg_1x1 = true;
-  a.ob = add_weight(p, pre + ".fn.fn.to_out.0.conv.bias", c);
-  a.gg = add_weight(p, pre + ".fn.fn.to_out.1.weight", c);
-  a.gb = add_weight(p, pre + ".fn.fn.to_out.1.bias", c);
-  a.ng = add_weight(p, pre + ".fn.norm.weight", c);
-  a.nb = add_weight(p, pre + ".fn.norm.bias", c);
+  a.c = c.w();
+  a.qkv = add_tensor(p, pre + ".fn.fn.to_qkv.conv.weight", plain(96), c, plain(0), 1, PK_CONV);
+  a.ow = add_tensor(p, pre + ".fn.fn.to_out.0.conv.weight", c, plain(32), plain(0), 1);
+  p->weights[a.ow].cin = 32; p->weights[a.ow].cout = a.c; p->weights[a.ow].taps = 1; p->weights[a.ow].dg_1x1 = true;
+  a.ob = add_vector(p, pre + ".fn.fn.to_out.0.conv.bias", c);
+  a.gg = add_vector(p, pre + ".fn.fn.to_out.1.weight", c);
+  a.gb = add_vector(p, pre + ".fn.fn.to_out.1.bias", c);
+  a.ng = add_vector(p, pre + ".fn.norm.weight", c);
+  a.nb = add_vector(p, pre + ".fn.norm.bias", c);
   return a;
 }
 
@@ -66,18 +107,29 @@ void check_channels(int c, const char* what) {
 }
 
 void build_plan(CdPlan* p) {
-  const CdUnetDesc& d = p->desc;
+  const CdUnetDesc& d = p->desc;  // (its layer_sizes become the wide widths below)
   CD_REQUIRE(d.n_sizes >= 2 && d.n_sizes <= CD_MAX_SIZES, "LAYER_SIZE_UNET must have 2..8 entries");
   CD_REQUIRE(d.in_channels >= 1 && d.in_channels <= 4, "in_channels must be 1..4");
   CD_REQUIRE(d.cond_dim == 128 || (d.cond_dim % 4 == 0 && d.cond_dim <= 256), "COND_SIZE_UNET must be <= 256");
   CD_REQUIRE(d.cond_size >= 1 && d.cond_size <= 256, "cond_size must be 1..256");
   CD_REQUIRE(d.groups >= 1 && d.groups <= 64, "BLOCK_GROUPS must be 1..64");
+  // the width rule: every config width C runs as C k; all further checks are on the wide widths
+  std::vector<Ax> ax(d.n_sizes);
+  for (int i = 0; i < d.n_sizes; ++i) {
+    const int c = d.layer_sizes[i], k = widen_factor(c, d.groups);
+    if (!k)
+      throw Fail{CD_EINVAL, "LAYER_SIZE_UNET entry " + std::to_string(c) + " with BLOCK_GROUPS " + std::to_string(d.groups) +
+                                ": a width C must be a multiple of the group count and have a k in {1, 2, 4} for which C k is a "
+                                "multiple of 32, at most 256, and C k / BLOCK_GROUPS a multiple of 4 (a narrow width runs widened "
+                                "to C k)"};
+    p->cfg_sizes[i] = c;
+    ax[i] = Ax{c, k, c / d.groups};
+    p->desc.layer_sizes[i] = c * k;
+    p->widened = p->widened || k > 1;
+  }
   for (int i = 0; i < d.n_sizes; ++i) check_channels(d.layer_sizes[i], "LAYER_SIZE_UNET");
-  CD_REQUIRE(d.layer_sizes[0] == 32, "the fused output head needs LAYER_SIZE_UNET[0] == 32");
-  CD_REQUIRE(d.layer_sizes[0] == d.layer_sizes[1], "final_conv expects LAYER_SIZE_UNET[1] input channels (models.py:698): sizes 0 and 1 must agree");
-  for (int i = 0; i < d.n_sizes; ++i)
-    CD_REQUIRE(d.layer_sizes[i] % d.groups == 0 && (d.layer_sizes[i] / d.groups) % 4 == 0,
-               "channels per GroupNorm group must be a multiple of 4");
+  CD_REQUIRE(d.layer_sizes[0] == 32, "the fused output head needs LAYER_SIZE_UNET[0] to be 32, or 8 or 16 (which run 32 wide)");
+  CD_REQUIRE(p->cfg_sizes[0] == p->cfg_sizes[1], "final_conv expects LAYER_SIZE_UNET[1] input channels (models.py:698): sizes 0 and 1 must agree");
   p->nres = d.n_sizes - 1;
   const int nres = p->nres;
   const int zs = d.compress_z ? 2 : 1;
@@ -111,8 +163,8 @@ void build_plan(CdPlan* p) {
 
   // weights, in CondUnet.state_dict() order
   const int half = d.cond_dim / 2, hidden = d.cond_size > half / 2 ? d.cond_size : half / 2;
-  p->init_w = add_weight(p, "init_conv.conv.weight", (int64_t)d.layer_sizes[0] * d.in_channels * 27, PK_INIT, d.in_channels, d.layer_sizes[0], 27);
-  p->init_b = add_weight(p, "init_conv.conv.bias", d.layer_sizes[0]);
+  p->init_w = add_tensor(p, "init_conv.conv.weight", ax[0], plain(d.in_channels), plain(0), 27, PK_INIT);
+  p->init_b = add_vector(p, "init_conv.conv.bias", ax[0]);
   // Linear branch: time_mlp = [Unflatten, Linear(1, q), GELU, Linear(q, half), GELU, Linear(half, half)] (keys 1, 3, 5);
   // sinusoidal branch: [SinusoidalPositionEmbeddings(q), Linear(q, half), GELU, Linear(half, half)] (keys 1, 3).  The cond
   // MLP likewise (keys 0, 2, 4 resp. 1, 3; its sinusoidal form embeds a scalar condition, so hidden must equal q).
@@ -134,38 +186,38 @@ void build_plan(CdPlan* p) {
   p->downs.resize(nres);
   p->ups.resize(nres);
   for (int i = 0; i < nres; ++i) {
-    const int ci = d.layer_sizes[i], co = d.layer_sizes[i + 1];
+    const Ax ci = ax[i], co = ax[i + 1];
     const std::string pre = "downs." + std::to_string(i);
-    p->downs[i].r1 = add_res(p, pre + ".0", ci, co, true);
-    p->downs[i].r2 = add_res(p, pre + ".1", co, co, true);
+    p->downs[i].r1 = add_res(p, pre + ".0", ci, plain(0), co, true);
+    p->downs[i].r2 = add_res(p, pre + ".1", co, plain(0), co, true);
     if (i + 1 < nres) {
-      p->downs[i].sw = add_weight(p, pre + ".2.conv.weight", (int64_t)co * co * 48, PK_CONV, co, co, 48);
-      p->downs[i].sb = add_weight(p, pre + ".2.conv.bias", co);
+      p->downs[i].sw = add_tensor(p, pre + ".2.conv.weight", co, co, plain(0), 48, PK_CONV);
+      p->downs[i].sb = add_vector(p, pre + ".2.conv.bias", co);
     }
   }
   for (int i = 0; i < nres; ++i) {
     const int lv = nres - 1 - i;
-    const int ci = d.layer_sizes[lv], co = d.layer_sizes[lv + 1];
+    const Ax ci = ax[lv], co = ax[lv + 1];
     const std::string pre = "ups." + std::to_string(i);
-    p->ups[i].r1 = add_res(p, pre + ".0", co * 2, ci, true);
-    p->ups[i].r2 = add_res(p, pre + ".1", ci, ci, true);
+    p->ups[i].r1 = add_res(p, pre + ".0", co, co, ci, true);  // cat(x, skip): two segments, each with its own map
+    p->ups[i].r2 = add_res(p, pre + ".1", ci, plain(0), ci, true);
     if (i + 1 < nres) {
       const int kz = p->up_kz[i];
-      p->ups[i].sw = add_weight(p, pre + ".2.convTrans.weight", (int64_t)ci * ci * kz * 16, PK_CONVT, ci, ci, kz * 16);
-      p->ups[i].sb = add_weight(p, pre + ".2.convTrans.bias", ci);
+      p->ups[i].sw = add_tensor(p, pre + ".2.convTrans.weight", ci, ci, plain(0), kz * 16, PK_CONVT, true);
+      p->ups[i].sb = add_vector(p, pre + ".2.convTrans.bias", ci);
     }
-    check_channels(co * 2, "skip concat");
+    check_channels(co.w() * 2, "skip concat");
   }
   if (d.block_attn) {
-    for (int i = 0; i < nres; ++i) p->downs[i].attn = add_attn(p, "downs_attn." + std::to_string(i), d.layer_sizes[i + 1]);
-    for (int i = 0; i < nres; ++i) p->ups[i].attn = add_attn(p, "ups_attn." + std::to_string(i), d.layer_sizes[nres - 1 - i]);
+    for (int i = 0; i < nres; ++i) p->downs[i].attn = add_attn(p, "downs_attn." + std::to_string(i), ax[i + 1]);
+    for (int i = 0; i < nres; ++i) p->ups[i].attn = add_attn(p, "ups_attn." + std::to_string(i), ax[nres - 1 - i]);
   }
-  const int mid = d.layer_sizes[nres];
-  p->mid1 = add_res(p, "mid_block1", mid, mid, true);
+  const Ax mid = ax[nres];
+  p->mid1 = add_res(p, "mid_block1", mid, plain(0), mid, true);
   if (d.mid_attn) p->mid_attn = add_attn(p, "mid_attn", mid);
-  p->mid2 = add_res(p, "mid_block2", mid, mid, true);
-  p->fin = add_res(p, "final_conv.0", d.layer_sizes[1], d.layer_sizes[0], false);
-  p->head_w = add_weight(p, "final_conv.1.conv.weight", d.layer_sizes[0]);
+  p->mid2 = add_res(p, "mid_block2", mid, plain(0), mid, true);
+  p->fin = add_res(p, "final_conv.0", ax[1], plain(0), ax[0], false);
+  p->head_w = add_tensor(p, "final_conv.1.conv.weight", plain(1), ax[0], plain(0), 1);
   p->head_b = add_weight(p, "final_conv.1.conv.bias", 1);
 
   // arena layout
@@ -182,12 +234,17 @@ void build_plan(CdPlan* p) {
     else if (w.pack == PK_INIT) w.pk_off = bump((size_t)w.numel);
   }
   p->arena_floats = off;
-  size_t goff = 0;
+  // the caller's flat gradient buffer is laid out by the config's own shapes; widened tensors get a slot in the step's wide block
+  size_t goff = 0, wgoff = 0;
   for (auto& w : p->weights) {
     w.grad_off = goff;
-    goff += ((size_t)w.numel + 63) & ~(size_t)63;
+    goff += ((size_t)w.src_numel + 63) & ~(size_t)63;
+    if (!w.widened) continue;
+    w.wide_grad_off = wgoff;
+    wgoff += ((size_t)w.numel + 63) & ~(size_t)63;
   }
   p->grad_floats = goff;
+  p->wide_grad_floats = wgoff;
   CD_HIP(hipMalloc((void**)&p->d_lin_jobs, sizeof(LinearWgradJob) * 64));
   CD_HIP(hipMalloc((void**)&p->arena, off * sizeof(float)));
   CD_HIP(hipMemset(p->arena, 0, off * sizeof(float)));
@@ -309,6 +366,8 @@ int cd_plan_destroy(CdPlan* plan) {
     if (plan->cap_stream) hipStreamDestroy(plan->cap_stream);
     if (plan->d_pack_jobs) hipFree(plan->d_pack_jobs);
     if (plan->d_dg_jobs) hipFree(plan->d_dg_jobs);
+    if (plan->d_expand_jobs) hipFree(plan->d_expand_jobs);
+    if (plan->d_fold_jobs) hipFree(plan->d_fold_jobs);
     if (plan->d_attn_sync) hipFree(plan->d_attn_sync);
     if (plan->arena) hipFree(plan->arena);
     if (plan->d_embed_layers) hipFree(plan->d_embed_layers);
@@ -333,7 +392,7 @@ int cd_plan_weight_name(const CdPlan* plan, int idx, char* name, int cap, int64_
   return guarded([&] {
     CD_REQUIRE(plan && idx >= 0 && idx < (int)plan->weights.size(), "weight index out of range");
     if (name && cap > 0) std::snprintf(name, cap, "%s", plan->weights[idx].name.c_str());
-    if (numel) *numel = plan->weights[idx].numel;
+    if (numel) *numel = plan->weights[idx].src_numel;
   });
 }
 
@@ -343,10 +402,16 @@ int cd_plan_set_weight(CdPlan* plan, const char* name, const float* dev_ptr, int
     auto it = plan->index.find(name);
     if (it == plan->index.end()) throw Fail{CD_EWEIGHTS, std::string("unknown weight name '") + name + "'"};
     WeightEntry& w = plan->weights[it->second];
-    if (w.numel != numel)
-      throw Fail{CD_EWEIGHTS, std::string("weight '") + name + "' has " + std::to_string(numel) + " elements, expected " + std::to_string(w.numel)};
+    if (w.src_numel != numel)
+      throw Fail{CD_EWEIGHTS, std::string("weight '") + name + "' has " + std::to_string(numel) + " elements, expected " + std::to_string(w.src_numel)};
     hipStream_t s = (hipStream_t)stream;
-    CD_HIP(hipMemcpyAsync(plan->arena + w.raw_off, dev_ptr, sizeof(float) * (size_t)numel, hipMemcpyDeviceToDevice, s));
+    if (w.widened) {
+      WidenJob j = w.widen;
+      j.narrow = const_cast<float*>(dev_ptr); j.wide = plan->arena + w.raw_off;
+      launch_widen_expand_one(j, s);
+    } else {
+      CD_HIP(hipMemcpyAsync(plan->arena + w.raw_off, dev_ptr, sizeof(float) * (size_t)numel, hipMemcpyDeviceToDevice, s));
+    }
     if (w.pack == PK_CONV) launch_pack_weights(plan->arena + w.raw_off, plan->arena + w.pk_off, w.cout, w.cin, w.taps, false, s);
     if (w.pack == PK_CONVT) {
       launch_pack_weights(plan->arena + w.raw_off, plan->arena + w.pk_off, w.cout, w.cin, w.taps, true, s);
@@ -369,15 +434,32 @@ int cd_plan_set_weights(CdPlan* plan, int n, const float* const* dev_ptrs, void*
     hipStream_t s = (hipStream_t)stream;
     bool changed = plan->pack_jobs.size() != plan->weights.size();
     if (changed) plan->pack_jobs.assign(plan->weights.size(), PackJob{});
+    // a widened tensor goes caller -> wide raw copy in the expand launch, and the packers read that copy
+    std::vector<WidenJob>& ex = plan->expand_jobs;
+    bool ex_changed = false;
+    if (plan->widened && ex.empty()) {
+      for (const auto& w : plan->weights)
+        if (w.widened) ex.push_back(w.widen);
+      CD_HIP(hipMalloc((void**)&plan->d_expand_jobs, sizeof(WidenJob) * ex.size()));
+      ex_changed = true;
+    }
+    size_t ke = 0;
     for (int i = 0; i < n; ++i) {
       CD_REQUIRE(dev_ptrs[i], "cd_plan_set_weights: null tensor pointer");
       const WeightEntry& w = plan->weights[i];
       PackJob& j = plan->pack_jobs[i];
-      if (j.src != dev_ptrs[i]) changed = true;
-      j.src = dev_ptrs[i];
+      const float* src = dev_ptrs[i];
+      if (w.widened) {
+        WidenJob& e = ex[ke++];
+        if (e.narrow != dev_ptrs[i]) ex_changed = true;
+        e.narrow = const_cast<float*>(dev_ptrs[i]); e.wide = plan->arena + w.raw_off;
+        src = plan->arena + w.raw_off;
+      }
+      if (j.src != src) changed = true;
+      j.src = src;
       j.raw = plan->arena + w.raw_off;
       j.cout = w.cout; j.cin = w.cin; j.taps = w.taps; j.kind = (int)w.pack;
-      j.numel = (unsigned long long)w.numel;
+      j.numel = w.widened ? 0ull : (unsigned long long)w.numel;
       j.pk = nullptr; j.bf3 = nullptr; j.f16 = nullptr; j.n_pk = j.n_bf3 = j.n_f16 = 0;
       const unsigned long long n16 = w.pack == PK_CONV || w.pack == PK_CONVT
                                          ? (unsigned long long)(w.cin / 16) * w.taps * ((w.cout + 31) / 32) * 64 : 0ull;
@@ -398,11 +480,13 @@ int cd_plan_set_weights(CdPlan* plan, int n, const float* const* dev_ptrs, void*
       }
     }
     if (!plan->d_pack_jobs) CD_HIP(hipMalloc((void**)&plan->d_pack_jobs, sizeof(PackJob) * plan->weights.size()));
-    if (changed) {
-      // (rare: torch keeps a parameter's storage across optimizer steps) the kernels of the previous call may still read the list
+    if (changed || ex_changed) {
+      // (rare: torch keeps a parameter's storage across optimizer steps) the kernels of the previous call may still read the lists
       CD_HIP(hipStreamSynchronize(s));
       CD_HIP(hipMemcpy(plan->d_pack_jobs, plan->pack_jobs.data(), sizeof(PackJob) * plan->pack_jobs.size(), hipMemcpyHostToDevice));
+      if (!ex.empty()) CD_HIP(hipMemcpy(plan->d_expand_jobs, ex.data(), sizeof(WidenJob) * ex.size(), hipMemcpyHostToDevice));
     }
+    launch_widen_expand(plan->d_expand_jobs, (int)ex.size(), s);
     launch_pack_jobs(plan->d_pack_jobs, n, s);
     launch_pack_jobs_f16x2(plan->d_pack_jobs, n, s);
     for (auto& w : plan->weights) w.set = true;

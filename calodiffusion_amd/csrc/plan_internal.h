@@ -12,6 +12,7 @@
 #include "kernels_gn.h"
 #include "kernels_sampler.h"
 #include "kernels_wgrad.h"
+#include "kernels_widen.h"
 
 #include <map>
 #include <string>
@@ -25,13 +26,18 @@ namespace cd {
 enum PackKind { PK_NONE = 0, PK_CONV = 1, PK_CONVT = 2, PK_INIT = 3 };
 struct WeightEntry {
   std::string name;
-  int64_t numel = 0;
+  int64_t numel = 0;    // as the kernels see it (wide, in a plan with narrow levels)
+  int64_t src_numel = 0;  // as the caller gives it and receives its gradient (the config's own shape)
   size_t raw_off = 0;   // floats into the arena
   PackKind pack = PK_NONE;
   int cin = 0, cout = 0, taps = 0;
   size_t pk_off = 0;
   size_t pk3_off = 0;  // split-bf16 image of 3x3x3 convs (floats into the arena; 0 = none)
   size_t grad_off = 0; // floats into the flat gradient buffer of cd_train_step
+  // narrow widths (kernels_widen.h): the tensor's map (pointers unset) and its slot in the step's wide gradient block
+  bool widened = false;
+  WidenJob widen{};
+  size_t wide_grad_off = 0;
   bool set = false;
   // input-gradient images of the training step (dgrad_images below), floats into the step's image block; dg_mode 0 = none
   int dg_mode = 0;
@@ -92,7 +98,8 @@ struct StepGraph {
 using namespace cd;
 
 struct CdPlan {
-  CdUnetDesc desc{};
+  CdUnetDesc desc{};  // layer_sizes: the widths the kernels run (cfg_sizes widened by the width rule)
+  int cfg_sizes[CD_MAX_SIZES] = {};  // LAYER_SIZE_UNET as the config states it
   int nres = 0;
   std::vector<Dims3> shapes;           // per level
   std::vector<int> up_kz;              // per up step (i = 0 .. nres-2)
@@ -183,6 +190,14 @@ struct CdPlan {
   size_t embed_grad_floats() const { return flat() ? fe.grad_floats() : 0; }
   size_t enc_grad_off() const { return grad_floats; }
   size_t dec_grad_off() const { return grad_floats + embed_grad_floats(); }
+
+  // narrow widths: any level runs widened; the job lists of the widening stage (cd_plan_set_weights; host copy with the callers'
+  // pointers of the last call) and of the gradient fold (pointed at the step's wide block and the caller's buffer), and the
+  // floats of that wide block
+  bool widened = false;
+  std::vector<WidenJob> expand_jobs, fold_jobs;
+  WidenJob *d_expand_jobs = nullptr, *d_fold_jobs = nullptr;
+  size_t wide_grad_floats = 0;
 
   Arena ws;
 

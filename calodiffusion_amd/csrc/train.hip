@@ -39,11 +39,43 @@ struct TrainTape {
   float *h0 = nullptr, *emb = nullptr, *scal = nullptr, *x0 = nullptr;
 };
 
+// Where a step's gradients land: the caller's flat buffer (base), or for a widened tensor its slot in the step's wide block,
+// which fold_wide_grads maps back into the caller's buffer at the end of the step
 struct Grads {
   CdPlan* p;
   float* base;
-  float* at(int widx) const { return base + p->weights[widx].grad_off; }
+  float* wide = nullptr;
+  float* at(int widx) const {
+    const WeightEntry& w = p->weights[widx];
+    return w.widened ? wide + w.wide_grad_off : base + w.grad_off;
+  }
 };
+
+// narrow widths: the step's wide gradient block (widened plans with parameter gradients only; first in the workspace) ...
+static void take_wide_grads(CdPlan* p, Run& r, Grads& G) {
+  if (p->widened && r.param_grads) G.wide = r.ws->get<float>(p->wide_grad_floats);
+}
+// ... and the fold of every widened tensor's gradient into the caller's buffer, one launch after the last gradient is written
+static void fold_wide_grads(CdPlan* p, Run& r, const Grads& G) {
+  if (!G.wide || r.dry()) return;
+  std::vector<WidenJob>& jobs = p->fold_jobs;
+  if (jobs.empty()) {
+    for (const auto& w : p->weights)
+      if (w.widened) jobs.push_back(w.widen);
+    CD_HIP(hipMalloc((void**)&p->d_fold_jobs, sizeof(WidenJob) * jobs.size()));
+  }
+  size_t k = 0;
+  bool moved = false;
+  for (const auto& w : p->weights) {
+    if (!w.widened) continue;
+    WidenJob& j = jobs[k++];
+    moved = moved || j.narrow != G.base + w.grad_off || j.wide != G.wide + w.wide_grad_off;
+    j.narrow = G.base + w.grad_off; j.wide = G.wide + w.wide_grad_off;
+  }
+  // (the caller's buffer is a fresh tensor each step: the list is re-sent; in stream order, so the previous fold has read its own)
+  if (moved) CD_HIP(hipMemcpyAsync(p->d_fold_jobs, jobs.data(), sizeof(WidenJob) * jobs.size(), hipMemcpyHostToDevice, r.s));
+  launch_widen_fold(p->d_fold_jobs, (int)jobs.size(), r.s);
+}
 
 // ---- forward pieces (training flavour: keep everything, separate output buffers) ------------------------------------
 float* res_block_train(Run& r, CdPlan* p, const ResW& W, const float* emb, const float* x0, int c0, const float* x1, int c1,
@@ -662,6 +694,7 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   Run r{&p->ws, s, B, d.groups};
   r.status = p->status_word;
   Grads G{p, grads};
+  take_wide_grads(p, r, G);
   TapedForward f;
   taped_forward(p, r, true, data, noise, nullptr, sigma, cond, f);
   const TrainTape& T = f.T;
@@ -689,6 +722,7 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
   if (fe) embed_input_backward(p, r, f, g, nullptr, f.gf, G);
   // init conv: weight and bias gradients only (its input is data)
   finish_param_grads(p, r, f, g, G, bs);
+  fold_wide_grads(p, r, G);
 }
 
 void embed_head_backward(CdPlan* p, Run& r, const TapedForward& f, const Grads& G, BackwardState& bs, float* hpart) {
@@ -731,6 +765,7 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
   r.status = p->status_word;
   r.param_grads = param_grads;
   Grads G{p, grads};
+  take_wide_grads(p, r, G);
   TapedForward f;
   taped_forward(p, r, false, nullptr, nullptr, x, sigma, cond, f);
   const TrainTape& T = f.T;
@@ -757,6 +792,7 @@ void denoise_vjp_impl(CdPlan* p, int B, const float* x, const float* sigma, cons
     launch_init_dgrad(g, p->raw(p->init_w), d.in_channels, d.layer_sizes[0], gy, T.scal, d.objective, dx, B, dims, s);
   if (param_grads) {
     finish_param_grads(p, r, f, g, G, bs);
+    fold_wide_grads(p, r, G);
   } else {
     r.ws->release(g);
     r.gq = nullptr;

@@ -62,6 +62,11 @@ typedef struct CdUnetDesc {
   int32_t grid[3];                 /* D, H, W of SHAPE_FINAL */
   int32_t in_channels;             /* `channels`: 1 (+2 if R_Z_INPUT) (+1 if PHI_INPUT) */
   int32_t n_sizes;                 /* len(LAYER_SIZE_UNET) */
+  /* LAYER_SIZE_UNET as the config states it.  A width C runs as C k for the smallest k of {1, 2, 4} with C % groups == 0,
+   * C k % 32 == 0, (C k / groups) % 4 == 0 and C k <= 256 (channels duplicated inside each GroupNorm group); a width without
+   * such a k is refused with CD_EINVAL.  Tensor sizes (cd_plan_weight_name) and the gradient layout (cd_plan_grad_layout)
+   * are always the config's own; a plan with k > 1 somewhere takes one launch more per weight sync and per training step
+   * and a larger training / VJP workspace. */
   int32_t layer_sizes[CD_MAX_SIZES];
   int32_t groups;                  /* BLOCK_GROUPS (8) */
   int32_t block_attn, mid_attn, compress_z;
