@@ -3,7 +3,7 @@
     python -m calodiffusion_amd.build        # -> calodiffusion_amd/lib/libcalodiff_hip.so
 
 hipcc cross-compiles for gfx950 without a GPU present.  The shared object is git-ignored but travels with the
-working tree to the GPU box.
+working tree to the GPU box; so does lib/cd_generate_example, the C example of INTEGRATION.md section B2 (gcc, linked against it).
 """
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ LIBDIR = os.path.join(HERE, "lib")
 TAG = os.environ.get("CD_BUILD_TAG", "")
 LIB = os.path.join(LIBDIR, f"libcalodiff_hip{'_' + TAG if TAG else ''}.so")
 SOURCES = ["kernels_conv_flat16.hip", "kernels_conv_flat.hip", "kernels_conv_tiled.hip", "kernels_conv_transpose.hip", "kernels_pointwise.hip", "kernels_init_conv.hip", "kernels_conv.hip", "kernels_conv_zs.hip", "kernels_attn.hip", "kernels_conv_small.hip", "kernels_deep.hip", "kernels_deep_side.hip", "kernels_wgrad16.hip", "kernels_gn.hip", "kernels_attn_unfused.hip", "kernels_embed.hip", "kernels_head.hip", "kernels_sampler.hip", "kernels_loss.hip", "kernels_preprocess.hip", "kernels_mlp.hip", "kernels_mlp_train.hip", "kernels_wgrad.hip", "kernels_gn_bwd.hip", "kernels_conv_bwd.hip", "kernels_attn_bwd.hip", "kernels_head_bwd.hip", "kernels_init_bwd.hip", "kernels_embed_bwd.hip", "profiler.hip", "plan.hip",
-           "forward.hip", "conv_backward.hip", "sampler.hip", "train.hip", "bns.hip", "ops.hip", "layer.hip", "adam.hip", "kernels_geom.hip", "kernels_geom_embed.hip", "kernels_radial.hip", "kernels_widen.hip"]
+           "forward.hip", "conv_backward.hip", "sampler.hip", "train.hip", "bns.hip", "ops.hip", "layer.hip", "adam.hip", "kernels_geom.hip", "kernels_geom_embed.hip", "kernels_radial.hip", "kernels_widen.hip", "generator.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 FLAGS += os.environ.get("CD_EXTRA_HIPCC_FLAGS", "").split()  # e.g. -DCD_ZS_EXPERIMENTS (tools/zs_stamps.sh, tools/zs_power.sh)
@@ -75,7 +75,7 @@ def build_all(force: bool = False, verbose: bool = True) -> str:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{r.stdout}\n{r.stderr}")
+            raise RuntimeError(f"{os.path.basename(cmd[0])} failed:\n{r.stdout}\n{r.stderr}")
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
 
@@ -96,7 +96,31 @@ def build_all(force: bool = False, verbose: bool = True) -> str:
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
         with open(LIB + ".srchash", "w") as fh:  # which sources the library next to it was built from
             fh.write(want + "\n")
+    build_example(run, want)
     return LIB
+
+
+EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "tools", "cd_generate_example.c")
+EXAMPLE = os.path.join(LIBDIR, "cd_generate_example")
+
+
+def build_example(run, lib_hash: str) -> None:
+    """tools/cd_generate_example.c (plain C: calodiff.h and the HIP runtime's C API) next to the library it links; rebuilt when
+    its source or the library's sources changed.  Not for tagged experiment builds."""
+    if TAG or not os.path.exists(EXAMPLE_SRC):
+        return
+    import shutil
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(HIPCC) or HIPCC)))
+    key = _file_digest([EXAMPLE_SRC], lib_hash + rocm)
+    if os.path.exists(EXAMPLE) and _read(EXAMPLE + ".srchash") == key:
+        return
+    if os.path.exists(EXAMPLE + ".srchash"):
+        os.remove(EXAMPLE + ".srchash")
+    run([os.environ.get("CC", "gcc"), "-std=c11", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(os.path.dirname(HERE), "include"),
+         "-I", os.path.join(rocm, "include"), EXAMPLE_SRC, "-o", EXAMPLE, "-L", LIBDIR, "-lcalodiff_hip", "-L", os.path.join(rocm, "lib"),
+         "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    with open(EXAMPLE + ".srchash", "w") as fh:
+        fh.write(key + "\n")
 
 
 def source_hash() -> str:

@@ -1,4 +1,5 @@
 // Dataset-2/3 showers between physical and normalised space: cd_reverse_norm, cd_reverse_norm_staged and cd_preprocess.
+#include "energy_map.h"
 #include "guarded.h"
 
 namespace cd {
@@ -141,9 +142,7 @@ __global__ void __launch_bounds__(kPreThreads) preprocess_kernel(PreprocessArgs 
     return;
   }
   if (tid == 0) {
-    // utils.py:307-310: float32 quotient and float32 log10, divided by the python float log10(emax / emin)
-    if (a.logE) a.e_out[b] = (float)((double)(float)log10((double)(e / a.emin)) / log10((double)a.emax / (double)a.emin));
-    else a.e_out[b] = (e - a.emin) / (a.emax - a.emin);
+    a.e_out[b] = energy_to_cond(e, a.emin, a.emax, a.logE);  // utils.py:307-310
   }
   float* q_lds = (float*)(pre_smem + ((a.D + 1) & ~1));
   if (a.layer_mode) {

@@ -134,6 +134,13 @@ _SIGNATURES = {
     "cd_denoise_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_plan_bns_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_bns_theta_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cd_generator_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), _P]),
+    "cd_generator_destroy": (C.c_int, [_P]),
+    "cd_generator_checksum": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "cd_generator_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "cd_generator_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
+    "cd_generator_run": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64),
+                                   _P, C.c_size_t, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),
@@ -274,6 +281,38 @@ def _program_io(start, program, n_steps: int, step_noise, debug: bool, what: str
     return xs, x0s, step_noise
 
 
+def unet_desc(unet, rz_input=False, phi_input=False, time_kind="raw", objective="hybrid", sigma_data=1.0, coords=None) -> CdUnetDesc:
+    """The CdUnetDesc of a CondUnet under its ``_engine_opts`` (``coords`` is not part of it).  Needs no GPU."""
+    d = CdUnetDesc()
+    d.struct_size = C.sizeof(CdUnetDesc)
+    d.grid = _i32x3(unet.grid)
+    d.in_channels = unet.channels
+    d.n_sizes = len(unet.layer_sizes)
+    for i, v in enumerate(unet.layer_sizes):
+        d.layer_sizes[i] = int(v)
+    d.groups = unet.groups
+    d.block_attn = int(bool(unet.block_attn))
+    d.mid_attn = int(unet.mid_attn is not False)
+    d.compress_z = int(bool(unet.compress_Z))
+    d.cond_size, d.cond_dim = unet.cond_size, unet.cond_dim
+    d.rz_input, d.phi_input = int(bool(rz_input)), int(bool(phi_input))
+    d.time_embed_kind = TIME_KINDS[time_kind]
+    d.objective = OBJECTIVES[objective]
+    d.sigma_data = float(sigma_data)
+    d.time_sin, d.cond_sin = int(bool(getattr(unet, "time_embed", False))), int(bool(getattr(unet, "cond_embed", False)))
+    return d
+
+
+def layer_mlp_desc(resnet, time_kind="raw", objective="hybrid", sigma_data=1.0) -> CdLayerMlpDesc:
+    """The CdLayerMlpDesc of a ResNet layer model under its ``_engine_opts``.  Needs no GPU."""
+    d = CdLayerMlpDesc()
+    d.struct_size = C.sizeof(CdLayerMlpDesc)
+    d.dim_in, d.hidden, d.cond_emb, d.cond_size = resnet.dim_in, resnet.hidden_dim, resnet.cond_emb_dim, resnet.cond_size
+    d.n_res = len(resnet.hidden_layers)
+    d.time_embed_kind, d.objective, d.sigma_data = TIME_KINDS[time_kind], OBJECTIVES[objective], float(sigma_data)
+    return d
+
+
 class UnetEngine:
     """One HIP plan bound to one CondUnet parameter set on one device."""
 
@@ -282,24 +321,7 @@ class UnetEngine:
         self.lib = load_library()
         self.device_name = require_gpu()
         self.unet = unet
-        d = CdUnetDesc()
-        d.struct_size = C.sizeof(CdUnetDesc)
-        d.grid = _i32x3(unet.grid)
-        d.in_channels = unet.channels
-        d.n_sizes = len(unet.layer_sizes)
-        for i, v in enumerate(unet.layer_sizes):
-            d.layer_sizes[i] = int(v)
-        d.groups = unet.groups
-        d.block_attn = int(bool(unet.block_attn))
-        d.mid_attn = int(unet.mid_attn is not False)
-        d.compress_z = int(bool(unet.compress_Z))
-        d.cond_size, d.cond_dim = unet.cond_size, unet.cond_dim
-        d.rz_input, d.phi_input = int(bool(rz_input)), int(bool(phi_input))
-        d.time_embed_kind = TIME_KINDS[time_kind]
-        d.objective = OBJECTIVES[objective]
-        d.sigma_data = float(sigma_data)
-        d.time_sin, d.cond_sin = int(bool(getattr(unet, "time_embed", False))), int(bool(getattr(unet, "cond_embed", False)))
-        self.desc = d
+        d = self.desc = unet_desc(unet, rz_input, phi_input, time_kind, objective, sigma_data)
         self.grid = tuple(unet.grid)
         self.voxels = int(np.prod(self.grid))
         handle = _P()
@@ -753,12 +775,7 @@ class LayerMlpEngine:
         self.lib = load_library()
         self.device_name = require_gpu()
         self.net = resnet
-        d = CdLayerMlpDesc()
-        d.struct_size = C.sizeof(CdLayerMlpDesc)
-        d.dim_in, d.hidden, d.cond_emb, d.cond_size = resnet.dim_in, resnet.hidden_dim, resnet.cond_emb_dim, resnet.cond_size
-        d.n_res = len(resnet.hidden_layers)
-        d.time_embed_kind, d.objective, d.sigma_data = TIME_KINDS[time_kind], OBJECTIVES[objective], float(sigma_data)
-        self.desc = d
+        self.desc = layer_mlp_desc(resnet, time_kind, objective, sigma_data)
         self.dim = resnet.dim_in
 
     def _weights(self):

@@ -1,0 +1,285 @@
+"""Generator files: one self-contained blob per model, from which the C ABI generates showers without Python.
+
+``export_generator(model, sample_steps)`` writes everything ``Diffusion.generate`` / ``LayerDiffusion.generate`` need for one
+regular-grid model -- the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's layer model, each stage's compiled
+sampler exactly as the Python path hands it to the library, and the inverse pre-processing record -- in the format DESIGN.md
+("Generator file") documents.  It runs on the CPU.  ``cd_generator_create`` / ``cd_generator_run`` (include/calodiff.h) turn the
+file into "incident energies in, physical showers out"; ``Generator`` is the thin ctypes wrapper over them, and
+tools/cd_generate_example.c the same from C.
+
+First-version scope: DATASET_NUM 2 / 3 with a ``[layer-]logit-norm`` map, any width the plan takes, any sampler that compiles to a
+CdStep table or to a step program that does not depend on the batch.  Everything else is refused at export, by name.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import struct
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import engine
+
+MAGIC = b"CDGENBLB"
+FORMAT_VERSION = 1
+HEADER_BYTES, SECTION_ENTRY_BYTES, ALIGN = 64, 24, 64
+WEIGHT_RECORD_BYTES, WEIGHT_NAME_BYTES = 112, 96
+TAG_META, TAG_UNET, TAG_LAYER, TAG_UNET_SAMPLER, TAG_LAYER_SAMPLER, TAG_REVNORM = b"META", b"UNET", b"LAYR", b"USMP", b"LSMP", b"RNRM"
+
+
+def fnv1a64(data: bytes) -> int:
+    """64-bit FNV-1a, the file's checksum: the library's loop (cd_generator_checksum, host code) when it is built, else the same
+    loop in Python (a few seconds for a 10 MB file)."""
+    data = bytes(data)
+    if os.path.exists(engine.LIB_PATH):
+        out = C.c_uint64()
+        engine._check(engine.load_library().cd_generator_checksum(data, len(data), C.byref(out)))
+        return int(out.value)
+    return fnv1a64_py(data)
+
+
+def fnv1a64_py(data: bytes) -> int:
+    h = 0xCBF29CE484222325
+    for b in bytes(data):
+        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def _pad(b: bytes, align: int) -> bytes:
+    return b + b"\0" * (-len(b) % align)
+
+
+class _Capture:
+    """Stands where the model stands in a sampler call and records what the sampler hands to the engine: the CdStep table
+    (``ddim_sample``) or the step program (``sampler_run``), with ``use_graph``.  Everything else is the model's own (schedule
+    tables, loss function, config), so the compiled sampler is the one the Python path would run."""
+
+    def __init__(self, model):
+        self._model = model
+        self.table = self.program = None
+        self.use_graph = True
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def engine(self):
+        return self
+
+    def cond_tensor(self, E, layers):
+        return None
+
+    def step_noise_stream(self, start):
+        return 0, 0
+
+    def denoise(self, *a, **k):
+        raise NotImplementedError("export_generator: this sampler calls the model back from the host: it has no table or program")
+
+    def ddim_sample(self, start, cond, steps, use_graph=True, **kw):
+        self.table = np.ascontiguousarray(steps, dtype=np.float32)
+        self.use_graph = bool(use_graph)
+        return start, None, None
+
+    def sampler_run(self, start, cond, program, use_graph=True, **kw):
+        self.program = program
+        self.use_graph = bool(use_graph)
+        return start, None, None
+
+
+def compile_sampler(model, sampler, num_steps: int, sample_offset: int, state_shape) -> dict:
+    """What ``sampler(model, start, ...)`` passes to the library for these steps: {'table': (n, 4) fp32} or {'program': Program},
+    with 'use_graph' and 'noise_tensors_drawn'."""
+    from . import sample
+    name = type(sampler).__name__
+    if isinstance(sampler, sample.DPMAdaptive):
+        raise NotImplementedError(f"export_generator: {name} decides every step on the host (a loop around denoise): it has no device "
+                                  "table or program to export")
+    if isinstance(sampler, sample.BespokeNonStationary):
+        raise NotImplementedError(f"export_generator: {name}'s step program carries a sigma column per sample: it depends on the "
+                                  "batch and cannot be compiled once")
+    cap = _Capture(model)
+    sampler(cap, torch.zeros((1,) + tuple(state_shape)), None, None, num_steps, sample_offset, False)
+    out = dict(use_graph=cap.use_graph, noise_tensors_drawn=int(sampler.noise_tensors_drawn))
+    if cap.program is not None:
+        out["program"] = cap.program
+    elif cap.table is not None:
+        out["table"] = cap.table
+    else:
+        raise NotImplementedError(f"export_generator: {name} handed the library neither a step table nor a program")
+    return out
+
+
+def _sampler_section(c: dict) -> bytes:
+    if "table" in c:
+        t = c["table"]
+        head = struct.pack("<8if", 0, t.shape[0], 0, 0, 0, 0, c["noise_tensors_drawn"], int(c["use_graph"]), 1.0)
+        return _pad(head, 64) + t.astype("<f4").tobytes()
+    p = c["program"]
+    coefs = np.ascontiguousarray(p.coefs, dtype="<f4")
+    n_steps, n_coef = coefs.shape
+    ops = engine._pack_ops(p).astype("<i4")
+    head = struct.pack("<8if", 1, n_steps, len(p.ops), n_coef, p.n_bufs, int(p.op_begin is not None), c["noise_tensors_drawn"],
+                       int(c["use_graph"]), float(p.start_scale))
+    body = ops.tobytes()
+    if p.op_begin is not None:
+        assert len(p.op_begin) == n_steps + 1
+        body += np.asarray(p.op_begin, dtype="<i4").tobytes()
+    return _pad(head, 64) + body + coefs.tobytes()
+
+
+def _net_section(desc, state_dict, coords=()) -> bytes:
+    """UNET / LAYR: header, descriptor, coordinate profiles, the weight records, then the fp32 tensors (64-byte aligned)."""
+    desc = bytes(desc)
+    coords = [np.ascontiguousarray(a, dtype="<f4") for a in coords]
+    n_coord = [len(a) for a in coords] + [0] * (3 - len(coords))
+    items = [(k, v.detach().to("cpu", torch.float32).contiguous().numpy()) for k, v in state_dict.items()]
+    front = struct.pack("<8I", len(desc), len(items), *n_coord, 0, 0, 0) + _pad(desc, 8) + b"".join(a.tobytes() for a in coords)
+    off = len(front) + WEIGHT_RECORD_BYTES * len(items)
+    off += -off % 64
+    records, data = b"", b""
+    for name, arr in items:
+        raw = name.encode()
+        if len(raw) >= WEIGHT_NAME_BYTES:
+            raise ValueError(f"export_generator: tensor name {name!r} is longer than {WEIGHT_NAME_BYTES - 1} bytes")
+        records += raw.ljust(WEIGHT_NAME_BYTES, b"\0") + struct.pack("<QQ", arr.size, off + len(data))
+        data += _pad(arr.astype("<f4").tobytes(), 64)
+    return _pad(front + records, 64) + data
+
+
+def _refuse_out_of_scope(model, debug):
+    cfg = model.config
+    if debug:
+        raise NotImplementedError("export_generator: a debug trajectory request is not part of a generator file (cd_generator_run "
+                                  "returns showers only)")
+    if cfg.get("HGCAL", False) or getattr(model, "hgcal", False):
+        raise NotImplementedError("export_generator: HGCal configs are not provided: their geometry maps would have to be in the file")
+    if cfg.get("DATASET_NUM", 2) not in (2, 3):
+        raise NotImplementedError(f"export_generator: Dataset {cfg.get('DATASET_NUM')} is not provided (DATASET_NUM 2 / 3 only): the "
+                                  "irregular geometry would have to be in the file")
+    if getattr(model, "do_embed", False) or getattr(model, "NN_embed", None) is not None:
+        raise NotImplementedError("export_generator: a model with an in-model geometry embedding (do_embed) is not provided: its "
+                                  "maps would have to be in the file")
+    if cfg.get("SHOWERMAP") not in ("layer-logit-norm", "logit-norm"):
+        raise NotImplementedError(f"export_generator: SHOWERMAP {cfg.get('SHOWERMAP')!r} is not provided ([layer-]logit-norm only)")
+    missing = [k for k in ("EMAX", "EMIN", "logE", "MAXDEP", "ECUT") if k not in cfg]
+    if missing:
+        raise ValueError(f"export_generator: the config lacks {missing}: the inverse pre-processing record needs them")
+
+
+def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Optional[str] = None, debug: bool = False) -> bytes:
+    """The generator file of ``model`` (a ``CaloDiffusion`` or ``LayerDiffusion`` as constructed from its config) for
+    ``model.generate(loader, sample_steps, sample_offset=sample_offset)``; also written to ``path`` when given."""
+    from .layerdiffusion import LayerDiffusion
+    from .postprocess import DATASET_PARAMS
+    _refuse_out_of_scope(model, debug)
+    cfg = model.config
+    sample_steps, sample_offset = int(sample_steps), int(sample_offset or 0)
+    two_stage = isinstance(model, LayerDiffusion)
+    unet = model.base_model if two_stage else model.model
+    opts = dict(unet._engine_opts)
+    coords = opts.pop("coords")
+    data_shape = [int(v) for v in model._data_shape]
+    D, H, W = (int(v) for v in cfg["SHAPE_FINAL"][2:])
+    if data_shape != [1, D, H, W]:
+        raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (1, D, H, W) grid")
+    layer_map = "layer" in cfg["SHOWERMAP"]
+
+    sections = []
+    if two_stage:
+        # the Python path compiles the layer sampler first (LayerDiffusion.sample)
+        lay = compile_sampler(model, model.layer_sampler, int(model.layer_steps), sample_offset, (D + 1,))
+        sections += [(TAG_LAYER, _net_section(engine.layer_mlp_desc(model.layer_model, **model.layer_model._engine_opts),
+                                              model.layer_model.state_dict())),
+                     (TAG_LAYER_SAMPLER, _sampler_section(lay))]
+    net = compile_sampler(model, model.sampler_algorithm, sample_steps, sample_offset, data_shape)
+    r, z, phi = coords
+    sections += [(TAG_UNET, _net_section(engine.unet_desc(unet, **opts), unet.state_dict(), (r, z, phi))),
+                 (TAG_UNET_SAMPLER, _sampler_section(net))]
+
+    c = DATASET_PARAMS[cfg["DATASET_NUM"]]
+    rev = struct.pack("<6i8f2d", D, H, W, int(layer_map), int(bool(cfg["logE"])), int(cfg["DATASET_NUM"]),
+                      c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"],
+                      float(cfg["MAXDEP"]), float(cfg["ECUT"]), float(cfg["EMAX"]), float(cfg["EMIN"]))
+    name = str(cfg.get("CHECKPOINT_NAME", "")).encode()[:63]
+    meta = struct.pack("<12iQ2i", 4, *data_shape, unet.cond_size, 1, int(two_stage), int(layer_map), sample_steps,
+                       int(model.layer_steps) if two_stage else 0, sample_offset, int(model.noise_seed), D + 1 if layer_map else 0, 0)
+    meta += name.ljust(64, b"\0")
+    sections = [(TAG_META, meta), (TAG_REVNORM, _pad(rev, 80))] + sections
+
+    # header, section table, 64-byte aligned sections; the checksum covers everything behind the header
+    off = HEADER_BYTES + SECTION_ENTRY_BYTES * len(sections)
+    off += -off % ALIGN
+    table, payload = b"", b""
+    for tag, body in sections:
+        table += struct.pack("<4sIQQ", tag, 0, off + len(payload), len(body))
+        payload += _pad(body, ALIGN)
+    rest = _pad(table, ALIGN) + payload
+    total = HEADER_BYTES + len(rest)
+    blob = _pad(MAGIC + struct.pack("<IIQQ", FORMAT_VERSION, len(sections), total, fnv1a64(rest)), HEADER_BYTES) + rest
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(blob)
+    return blob
+
+
+class Generator:
+    """``cd_generator_*`` for Python users: ``Generator(blob)`` (bytes or a path), ``.info``, ``.run(E, ...)``.  Needs the GPU."""
+
+    INFO_KEYS = ("voxels", "layers", "energy_columns", "has_layer_stage", "takes_layers", "sample_steps", "layer_steps", "format_version")
+
+    def __init__(self, blob):
+        if not isinstance(blob, (bytes, bytearray, memoryview)):
+            with open(blob, "rb") as fh:
+                blob = fh.read()
+        blob = bytes(blob)
+        self.lib = engine.load_library()
+        engine.require_gpu()
+        handle = C.c_void_p()
+        engine._check(self.lib.cd_generator_create(blob, len(blob), C.byref(handle), engine._stream()))
+        self.handle = handle
+        info = (C.c_int32 * 8)()
+        engine._check(self.lib.cd_generator_info(self.handle, info))
+        self.info = dict(zip(self.INFO_KEYS, (int(v) for v in info)))
+        self._ws = {}
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.cd_generator_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def workspace_bytes(self, batch: int) -> int:
+        n = C.c_size_t()
+        engine._check(self.lib.cd_generator_workspace_bytes(self.handle, int(batch), C.byref(n)))
+        return n.value
+
+    def workspace(self, batch: int) -> torch.Tensor:
+        """One workspace kept: the last batch size asked for."""
+        ws = self._ws.get(int(batch))
+        if ws is None:
+            self._ws = {}
+            ws = torch.empty(self.workspace_bytes(batch), dtype=torch.uint8, device="cuda")
+            self._ws = {int(batch): ws}
+        return ws
+
+    def run(self, E, layers=None, seed: int = 1234, offset: int = 0, shard=None, normalised: bool = True, workspace=None):
+        """(showers (B, voxels), layers_out (B, 1 + D) or None, next_offset): one cd_generator_run call.  ``E`` (B,) or (B, 1)
+        device tensor of conditioning values (``normalised``) or physical energies; ``shard`` = (first_row, global_batch)."""
+        E = engine._dev32(E, "E").reshape(-1)
+        B = E.shape[0]
+        if layers is not None:
+            layers = engine._dev32(layers, "layers")
+            if tuple(layers.shape) != (B, self.info["layers"] + 1):
+                raise ValueError(f"layers must have shape ({B}, {self.info['layers'] + 1}), not {tuple(layers.shape)}")
+        first, gb = (0, B) if shard is None else (int(shard[0]), int(shard[1]))
+        ws = self.workspace(B) if workspace is None else workspace
+        showers = torch.empty((B, self.info["voxels"]), dtype=torch.float32, device=E.device)
+        lout = torch.empty((B, self.info["layers"] + 1), dtype=torch.float32, device=E.device) if self.info["takes_layers"] else None
+        nxt = C.c_uint64(0)
+        engine._check(self.lib.cd_generator_run(self.handle, B, E.data_ptr(), int(bool(normalised)), engine._ptr(layers), int(seed),
+                                                int(offset), first, gb, showers.data_ptr(), engine._ptr(lout), C.byref(nxt),
+                                                ws.data_ptr(), ws.numel(), engine._stream()))
+        return showers, lout, int(nxt.value)

@@ -603,6 +603,52 @@ int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights
                          const float* sigma, const float* cond, const float* gy, float* dx, float* grads /* nullable */,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- generator: incident energies in, physical showers out, without Python -------------------------------------------
+ * A generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file") holds everything
+ * Diffusion.generate / LayerDiffusion.generate (calodiffusion/models/diffusion.py:118-197, layerdiffusion.py:171-235) need for one
+ * regular-grid model (Dataset 2 / 3, '[layer-]logit-norm'): the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's
+ * layer model, each stage's compiled sampler (CdStep table or step program) and the inverse pre-processing record.
+ * cd_generator_run is the launch sequence of that Python path -- start tensor from the Philox stream, (layer stage,) conditioning
+ * row, U-Net sampler, cd_reverse_norm -- with the same stream offsets, so its showers are the ones generate() returns for the same
+ * seed and offset (to the bit within a process; the convolutions' tilings are picked by a timer once per process and differ in the
+ * last bits, so two processes agree to the bit only with CD_NO_AUTOTUNE set in both).  tools/cd_generate_example.c is a complete
+ * caller.
+ *
+ * cd_generator_create: blob is HOST memory (the file's bytes; not needed after the call); a malformed one is CD_EINVAL with a
+ * message, whatever its bytes.  It allocates the plan (cd_plan_create's device memory) and ONE device block that lives as long as
+ * the handle: the layer model's weights (about 3 MB for 45 layers) and its step table or program, each rounded up to 256 bytes;
+ * a model without a layer stage has no block.  A staging block of the U-Net's fp32 tensors (the sum of their sizes, each rounded
+ * up to 256 bytes) is freed before create returns.  The call synchronises `stream`. */
+typedef struct CdGenerator CdGenerator;
+int cd_generator_create(const void* blob, size_t bytes, CdGenerator** out, void* stream);
+int cd_generator_destroy(CdGenerator* gen);
+/* The file's checksum for code that writes or verifies one: 64-bit FNV-1a of `bytes` bytes of HOST memory (everything behind the
+ * 64-byte header).  Host code; touches no device. */
+int cd_generator_checksum(const void* data, size_t bytes, uint64_t* out);
+/* info[8] (host) = {voxels per shower, layers D, energy columns, has layer stage, takes layer energies, sample steps, layer steps
+ * (0 without a layer stage), format version}. */
+int cd_generator_info(const CdGenerator* gen, int32_t* info);
+int cd_generator_workspace_bytes(CdGenerator* gen, int batch, size_t* bytes);
+/* energy (batch): the conditioning values e (energy_is_normalised != 0, what a loader of the Python path yields) or physical
+ * incident energies in the unit of the config's EMIN / EMAX, mapped in the call as cd_preprocess maps them.  Either way the
+ * energies cd_reverse_norm scales by are emin * (emax / emin)^e (logE; emin + (emax - emin) e otherwise) formed from e on the
+ * device, the power correctly rounded to fp32 (numpy's float32 power, which the Python path takes on the host, may differ from it
+ * in the last bit depending on the host's vector math library).
+ * layers (batch, 1 + D), normalised: required for a model that conditions on layer energies and has no layer stage
+ * (CaloDiffusion on a 'layer-' map), refused otherwise.  layers_out (batch, 1 + D), nullable: the layer energies the showers were
+ * conditioned on (generated, or a copy of `layers`); not written for a model that takes none.
+ * showers (batch, voxels): physical showers, the rows of generate()'s first return value.
+ * seed / offset: the Philox stream position (model.noise_seed / model.noise_offset); *next_offset (HOST, nullable): the value
+ * model.noise_offset holds after the same batch -- pass it as the next call's offset.  first_row / global_batch:
+ * Diffusion.set_noise_shard's arguments, this call generates rows [first_row, first_row + batch) of a global batch; 0, batch (or
+ * 0, 0) = unsharded.
+ * Nothing is allocated; all scratch is in `workspace` (cd_generator_workspace_bytes at this batch).  The argument checks (a NULL
+ * or unexpected `layers`, a short workspace) come before the first launch.  The call synchronises `stream` where the sampler
+ * entry points do: their range fallback, and cd_layer_sampler_run's program check. */
+int cd_generator_run(CdGenerator* gen, int batch, const float* energy, int energy_is_normalised, const float* layers /* nullable */,
+                     uint64_t seed, uint64_t offset, int first_row, int global_batch, float* showers, float* layers_out /* nullable */,
+                     uint64_t* next_offset /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
  * "bf16x3" (convolutions on an exact three-term bf16 split, 6 MFMAs; attention unfused on the f32-input MFMA: full fp32 range)

@@ -1,0 +1,40 @@
+// Host-only check of a generator file: runs the reader cd_generator_create uses (csrc/generator_blob.h) and prints the section
+// table, or the reader's error.  Exit status 0 (good file) or 1.
+//
+//   g++ -std=c++17 -O1 -I calodiffusion_amd/csrc tools/generator_blob_check.cpp -o generator_blob_check
+//   ./generator_blob_check model.cdgen
+#include "generator_blob.h"
+
+#include <cstdio>
+#include <fstream>
+#include <iterator>
+
+int main(int argc, char** argv) {
+  if (argc != 2) {
+    std::fprintf(stderr, "usage: %s <generator file>\n", argv[0]);
+    return 1;
+  }
+  std::ifstream in(argv[1], std::ios::binary);
+  if (!in) {
+    std::fprintf(stderr, "%s: cannot open\n", argv[1]);
+    return 1;
+  }
+  const std::vector<char> bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  cdgen::Blob blob;
+  std::string err;
+  if (!cdgen::parse(bytes.data(), bytes.size(), &blob, &err)) {
+    std::fprintf(stderr, "%s: %s\n", argv[1], err.c_str());
+    return 1;
+  }
+  std::printf("%s: format version %u, %llu bytes, config '%s'\n", argv[1], blob.version, (unsigned long long)blob.total_bytes,
+              blob.meta.config_name);
+  for (const cdgen::Section& s : blob.sections)
+    std::printf("  %s  offset %10llu  bytes %10llu\n", cdgen::detail::tag_name(s.tag).c_str(), (unsigned long long)s.off,
+                (unsigned long long)s.bytes);
+  std::printf("  U-Net: %zu tensors, sampler %s, %d steps\n", blob.unet.weights.size(), blob.unet_sampler.kind ? "program" : "table",
+              blob.unet_sampler.n_steps);
+  if (blob.meta.has_layer_stage)
+    std::printf("  layer model: %zu tensors, sampler %s, %d steps\n", blob.layer.weights.size(),
+                blob.layer_sampler.kind ? "program" : "table", blob.layer_sampler.n_steps);
+  return 0;
+}
