@@ -112,20 +112,24 @@ struct LazyClose {
   float* part = nullptr;
   bool on = false;
 };
+// `h1_done` (optional): the first conv's output AND its channel partials, computed whole by an earlier launch (the composed init
+// pair, kernels_init_pair.hip): the conv is skipped, both blocks are taken over.
 float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
-                 float** part_out, int* units_out, LazyClose* lazy, float* h1_side) {
+                 float** part_out, int* units_out, LazyClose* lazy, float* h1_side, const ConvDone* h1_done) {
   Arena* ws = r.ws;
   CD_REQUIRE(c0 + c1 == w.cin, "internal: resnet block input width mismatch");
   const int64_t vox = dims.vox();
   const int G = r.groups;
   int u1 = 0, u2 = 0;
   static const bool defer_gn = getenv("CD_NO_GNDEFER") == nullptr;  // consumers fold the GroupNorm coefficients (gn_defer.h)
-  float* h1 = h1_side ? h1_side : ws->get<float>((size_t)r.B * vox * w.cout);
+  float* h1 = h1_done ? h1_done->h1 : (h1_side ? h1_side : ws->get<float>((size_t)r.B * vox * w.cout));
   // a 32-channel block on a grid of <= 128 voxels is ONE launch (kernels_conv_small.hip): decided below, once the shortcut exists
   const bool whole = vox <= 128 && w.cout == 32 && defer_gn && conv_precision() == PREC_F16X2 && w.c1w3 && w.c2w3;
   float* p1 = nullptr;
   CD_REQUIRE(!h1_side || (!whole && c1 > 0), "internal: a side conv belongs to a concat conv on a full-resolution grid");
-  if (h1_side) p1 = conv3_x_half_with_stats(r, x0, c0, c1, w.c1w3, h1, w.cout, dims, &u1);
+  CD_REQUIRE(!h1_done || (!whole && !h1_side && c1 == 0), "internal: a finished first conv belongs to a single-input block on a full-resolution grid");
+  if (h1_done) { p1 = h1_done->part; u1 = h1_done->units; }
+  else if (h1_side) p1 = conv3_x_half_with_stats(r, x0, c0, c1, w.c1w3, h1, w.cout, dims, &u1);
   else if (!whole) p1 = conv3_with_stats(r, x0, c0, x1, c1, w.c1w, w.c1w3, w.c1b, h1, w.cout, dims, nullptr, &u1);
   else p1 = ws->get<float>((size_t)r.B * ((vox + 31) / 32) * w.cout * 2);  // (same block as conv3_with_stats would take)
   float* coef1 = ws->get<float>((size_t)r.B * w.cout * 4);
@@ -354,7 +358,9 @@ bool deep_level_desc(const CdPlan* p, const float* emb, DeepLevelDesc* out) {
 
 // CondUnet.forward after init_conv / embeddings (models.py:713-748). Takes ownership of h (a workspace block).
 // `lazy`: see res_block -- when set on return, the result is the final block's raw conv output, *xin its (still allocated) input.
-float* unet_body(CdPlan* p, Run& r, const float* emb, float* h, LazyClose* lazy = nullptr, float** xin = nullptr) {
+// `first` (optional): downs[0]'s first block's first conv, already computed (res_block's h1_done).
+float* unet_body(CdPlan* p, Run& r, const float* emb, float* h, LazyClose* lazy = nullptr, float** xin = nullptr,
+                 const ConvDone* first = nullptr) {
   const CdUnetDesc& d = p->desc;
   const int nres = p->nres;
   const int zs = d.compress_z ? 2 : 1;
@@ -395,7 +401,8 @@ float* unet_body(CdPlan* p, Run& r, const float* emb, float* h, LazyClose* lazy 
       x = y;
       break;
     }
-    float* t = res_block(r, resolve(p, p->downs[i].r1, emb), x, cx, nullptr, 0, dims);
+    float* t = res_block(r, resolve(p, p->downs[i].r1, emb), x, cx, nullptr, 0, dims, nullptr, nullptr, nullptr, nullptr,
+                         i == 0 ? first : nullptr);
     r.ws->release(x);
     x = t; cx = p->downs[i].r1.cout;
     float* xp = nullptr;
@@ -532,10 +539,29 @@ void forward_impl(CdPlan* p, int B, const float* x, const float* cond, const flo
     }
     launch_init_conv(a, s);
   }
+  // The first block's first conv reads h with nothing non-linear in between: in the denoise form (one data channel, the coordinate
+  // table) it runs composed with the init conv as a one-channel 5x5x5 conv of c_in x (kernels_init_pair.hip).  h itself is still
+  // needed, as the block's shortcut.  Geometry and widths decide (build_plan: d_pair_w), never the batch; the full-range precisions
+  // (and with them a range fallback's re-run), cd_unet_forward, the training tape and the VJP keep the chained convs.  The two
+  // blocks are the ones res_block would take next, in its order: the workspace sequence is the same in both forms.
+  // (CD_NO_INIT_PAIR read per call: the parity test switches it in one process)
+  ConvDone pair;
+  const bool pair_on = !raw && p->d_pair_w && p->init_pair_ready && conv_precision() == PREC_F16X2 && getenv("CD_NO_INIT_PAIR") == nullptr;
+  if (pair_on) {
+    pair.h1 = p->ws.get<float>((size_t)B * dims.vox() * 32);
+    pair.part = p->ws.get<float>((size_t)B * ((dims.vox() + 31) / 32) * 32 * 2);  // (units <= D <= ceil(vox / 32): build_plan)
+    if (!r.dry()) {
+      InitPairArgs ia;
+      ia.x = fe ? g_in : x; ia.sigma_b = fe ? nullptr : t; ia.sigma_data = d.sigma_data;  // (g_in carries c_in)
+      ia.wc = p->d_pair_w; ia.table = p->d_pair_table; ia.out = pair.h1; ia.ch_part = pair.part; ia.batch = B; ia.dims = dims;
+      ia.status = r.status;
+      launch_init_pair_conv(ia, &pair.units, s);
+    }
+  }
   LazyClose lazy;
   float* xin = nullptr;
   static const bool head_fused = getenv("CD_NO_HEAD_GN") == nullptr;
-  float* hf = unet_body(p, r, emb, h, head_fused ? &lazy : nullptr, &xin);
+  float* hf = unet_body(p, r, emb, h, head_fused ? &lazy : nullptr, &xin, pair_on ? &pair : nullptr);
   if (!r.dry()) {
     HeadArgs ha;
     ha.h = hf; ha.w = p->raw(p->head_w); ha.bias = p->raw(p->head_b); ha.out = fe ? f_grid : out; ha.batch = B; ha.vox = dims.vox();

@@ -217,4 +217,39 @@ void launch_init_conv(const InitConvArgs& a, hipStream_t s);  // kernels_init_co
 // coordinate channels + bias of the init conv into a.coord_table (vox, cout): changes only with the weights / profiles
 void launch_init_coord_table(const InitConvArgs& a, hipStream_t s);
 
+// ---- init conv + the first block's first conv as ONE one-channel 5x5x5 conv of c_in x (kernels_init_pair.hip) ----
+// Nothing non-linear lies between the init conv and the 32 -> 32 3x3x3 conv that reads it, and x has one data channel:
+//   conv1(init_conv(x)) + b1 = T1 + sum_d Wc[class][d] c_in x(p + d - 2),
+// T1 = conv1(coordinate table) + b1 (vox, 32) and Wc the two kernels composed over the 5x5x5 offsets d.  conv1 zero-pads the init
+// conv's OUTPUT in z and r, so the composed weights depend on the output voxel's boundary class: class = 3 zc + rc,
+// zc / rc = 0 first plane / column, 1 interior, 2 last (the taps that would read the padding are left out of the sum).
+constexpr int kInitPairClasses = 9;
+constexpr int kInitPairKSteps = 8;  // K = 125 offsets padded to 128
+// f16x2 image of the composed weights: [class][k-step][term][lane = half * 32 + co][8 fp16], k = 16 ks + 8 half + e = offset index
+constexpr size_t kInitPairWeightBytes = (size_t)kInitPairClasses * kInitPairKSteps * 2 * 64 * 16;
+struct InitPairArgs {
+  const float* x = nullptr;        // (B, D, H, W): the data channel
+  const float* scale_b = nullptr;  // per-sample multiplier c_in (scale_b[b * scale_stride]), or null
+  int scale_stride = 1;
+  const float* sigma_b = nullptr;  // alternative: c_in = 1 / sqrt(sigma_b[b]^2 + sigma_data^2), as the init conv forms it
+  float sigma_data = 1.f;
+  const void* wc = nullptr;        // composed weights (kInitPairWeightBytes)
+  const float* table = nullptr;    // T1 (vox, 32)
+  float* out = nullptr;            // (B, vox, 32) channels-last
+  float* ch_part = nullptr;        // [B][units][32][2] channel partials {sum, sum of squares} of `out`, one unit per workgroup
+  int batch = 0;
+  Dims3 dims{};
+  int* status = nullptr;           // bit 0: |c_in x| exceeded the fp16 range
+  int slabs = 0;                   // workgroups per sample (0: the launcher's own count)
+};
+// geometry only: both boundary classes of an axis must be distinct voxels, and one plane with its halo must fit the LDS image
+bool init_pair_eligible(Dims3 dims);
+// workgroups per sample = units of the channel partials (depends on the batch as the chunk counts of the other convs do)
+int init_pair_units(Dims3 dims, int batch, int slabs = 0);
+// composed weights and table from the two convs' torch-layout weights (w0: (32, cin, 27), data channel 0; w1: (32, 32, 27)) and the
+// init conv's coordinate table (vox, 32): fp64 sums in a fixed order
+void launch_init_pair_build(const float* w0, int cin, const float* w1, const float* b1, const float* init_table, void* wc, float* table,
+                            Dims3 dims, hipStream_t s);
+void launch_init_pair_conv(const InitPairArgs& a, int* units, hipStream_t s);
+
 }  // namespace cd

@@ -142,6 +142,35 @@ int cd_op_init_conv(const float* x_ncdhw, const float* w, const float* bias, flo
   });
 }
 
+int cd_op_init_pair_conv(const float* x, const float* w0, const float* b0, const float* w1, const float* b1, int cin, const float* r_w,
+                         const float* z_d, const float* phi_h, int use_rz, int use_phi, const float* scale_b, float* y, float* ch_part,
+                         int* units, int batch, const int32_t dims[3], int slabs, void* scratch, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(x && w0 && w1 && y && ch_part && units && scratch && batch > 0 && slabs >= 0, "bad argument");
+    CD_REQUIRE(cin == 1 + 2 * (use_rz ? 1 : 0) + (use_phi ? 1 : 0), "cin must be 1 + the coordinate channels in use");
+    CD_REQUIRE(cin == 1 || (r_w && z_d && phi_h), "coordinate channels need their profiles");
+    hipStream_t s = (hipStream_t)stream;
+    const Dims3 d{dims[0], dims[1], dims[2]};
+    CD_REQUIRE(init_pair_eligible(d), "this grid is not eligible for the composed init pair");
+    // scratch: the init conv's [tap][ci][32] image | its coordinate table | the composed weights | the composed table
+    auto up = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    float* wpk0 = (float*)scratch;
+    float* tab0 = wpk0 + up((size_t)27 * cin * 32);
+    float* wc = tab0 + up((size_t)d.vox() * 32);
+    float* tab1 = wc + up(kInitPairWeightBytes / 4);
+    launch_pack_init_weights(w0, wpk0, 32, cin, s);
+    InitConvArgs a;
+    a.cin = cin; a.cx = 1; a.wpk = wpk0; a.bias = b0; a.cout = 32; a.dims = d; a.use_rz = use_rz; a.use_phi = use_phi;
+    a.r_w = r_w; a.z_d = z_d; a.phi_h = phi_h; a.coord_table = tab0;
+    launch_init_coord_table(a, s);
+    launch_init_pair_build(w0, cin, w1, b1, tab0, wc, tab1, d, s);
+    InitPairArgs ia;
+    ia.x = x; ia.scale_b = scale_b; ia.wc = wc; ia.table = tab1; ia.out = y; ia.ch_part = ch_part; ia.batch = batch; ia.dims = d;
+    ia.slabs = slabs;
+    launch_init_pair_conv(ia, units, s);
+  });
+}
+
 int cd_op_group_norm(const float* x, float* y, const float* gamma, const float* beta, int batch, int channels,
                      int64_t voxels, int groups, int silu, const float* add_bc, const float* residual,
                      void* scratch, void* stream) {

@@ -268,6 +268,15 @@ void build_plan(CdPlan* p) {
   CD_HIP(hipMalloc((void**)&p->d_coords, sizeof(float) * (size_t)(d.grid[0] + d.grid[1] + d.grid[2] + 4)));
   CD_HIP(hipMemset(p->d_coords, 0, sizeof(float) * (size_t)(d.grid[0] + d.grid[1] + d.grid[2] + 4)));
   CD_HIP(hipMalloc((void**)&p->d_init_table, sizeof(float) * (size_t)p->shapes[0].vox() * d.layer_sizes[0]));
+  // the composed form of init conv + downs[0].r1's first conv: geometry and widths only (forward_impl adds the precision and the
+  // entry point); the deepest level's launch must not be the one that runs that block, a grid of <= 128 voxels runs the block as
+  // one launch, and one unit of channel partials per plane must fit the block res_block sets aside (ceil(vox / 32) units)
+  if (nres >= 2 && init_pair_eligible(p->shapes[0]) && p->shapes[0].vox() > 128 && p->shapes[0].d <= (p->shapes[0].vox() + 31) / 32 &&
+      p->downs[0].r1.cin == 32 && p->downs[0].r1.cout == 32 &&
+      !p->downs[0].r1.has_res && d.layer_sizes[0] == 32) {
+    CD_HIP(hipMalloc(&p->d_pair_w, kInitPairWeightBytes));
+    CD_HIP(hipMalloc((void**)&p->d_pair_table, sizeof(float) * (size_t)p->shapes[0].vox() * 32));
+  }
   CD_HIP(hipMalloc((void**)&p->d_table, sizeof(float) * 4 * CdPlan::kMaxSteps));
   CD_HIP(hipMalloc((void**)&p->d_counter, sizeof(int) * 4));  // [0] sampler step counter, [2] range flags
   CD_HIP(hipMemset(p->d_counter, 0, sizeof(int) * 4));
@@ -297,11 +306,20 @@ static void init_conv_coord_args(CdPlan* p, InitConvArgs& a) {
   a.r_w = p->d_coords; a.z_d = p->d_coords + d.grid[2]; a.phi_h = p->d_coords + d.grid[2] + d.grid[0];
   a.coord_table = p->d_init_table;
 }
+// ... and what the composed init pair derives from it and from downs[0].r1's first conv (kernels_init_pair.hip)
+static void refresh_init_pair(CdPlan* p, hipStream_t s) {
+  const ResW& r1 = p->downs[0].r1;
+  if (!p->d_pair_w || !p->weights[p->init_w].set || !p->weights[p->init_b].set || !p->weights[r1.c1w].set || !p->weights[r1.c1b].set) return;
+  launch_init_pair_build(p->raw(p->init_w), p->desc.in_channels, p->raw(r1.c1w), p->raw(r1.c1b), p->d_init_table, p->d_pair_w,
+                         p->d_pair_table, p->shapes[0], s);
+  p->init_pair_ready = true;
+}
 static void refresh_init_table(CdPlan* p, hipStream_t s) {
   if (!p->weights[p->init_w].set || !p->weights[p->init_b].set) return;
   InitConvArgs a;
   init_conv_coord_args(p, a);
   launch_init_coord_table(a, s);
+  refresh_init_pair(p, s);
 }
 
 }  // namespace cd
@@ -373,6 +391,8 @@ int cd_plan_destroy(CdPlan* plan) {
     if (plan->d_embed_layers) hipFree(plan->d_embed_layers);
     if (plan->d_coords) hipFree(plan->d_coords);
     if (plan->d_init_table) hipFree(plan->d_init_table);
+    if (plan->d_pair_w) hipFree(plan->d_pair_w);
+    if (plan->d_pair_table) hipFree(plan->d_pair_table);
     if (plan->d_table) hipFree(plan->d_table);
     if (plan->d_counter) hipFree(plan->d_counter);
     if (plan->d_stepvals) hipFree(plan->d_stepvals);
@@ -422,6 +442,7 @@ int cd_plan_set_weight(CdPlan* plan, const char* name, const float* dev_ptr, int
     else if (w.pack == PK_INIT) launch_pack_init_weights(plan->arena + w.raw_off, plan->arena + w.pk_off, w.cout, w.cin, s);
     w.set = true;
     if (it->second == plan->init_w || it->second == plan->init_b) refresh_init_table(plan, s);
+    else if (it->second == plan->downs[0].r1.c1w || it->second == plan->downs[0].r1.c1b) refresh_init_pair(plan, s);
   });
 }
 

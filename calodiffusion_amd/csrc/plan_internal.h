@@ -122,6 +122,12 @@ struct CdPlan {
   float* d_coords = nullptr;  // r[W], z[D], phi[H]
   float* d_init_table = nullptr;  // (vox, C0): coordinate-channel part + bias of the init conv (refresh_init_table)
   bool coords_set = false;
+  // init conv + downs[0].r1's first conv as one launch (kernels_init_pair.hip): the composed weights and the table conv1(d_init_table)
+  // + b1, rebuilt with d_init_table and whenever that conv's weight or bias is set (refresh_init_pair).  Null where the geometry or
+  // the widths rule the form out; init_pair_ready once all four tensors have been set.
+  void* d_pair_w = nullptr;
+  float* d_pair_table = nullptr;
+  bool init_pair_ready = false;
 
   // sampler state (device): step table, counter, stepvals
   static constexpr int kMaxSteps = 4096;
@@ -279,8 +285,16 @@ float* stats_pass(Run& r, const float* x, int C, int64_t vox, int* units);
 float* conv3_with_stats(Run& r, const float* x0, int c0, const float* x1, int c1, const float* wpk, const void* wpk3,
                         const float* bias, float* out, int cout, Dims3 dims, const float* coef_in, int* units,
                         const GnDefer* defer_in = nullptr, float* coef_buf = nullptr, const ConvFusion::GnOut* gn_out = nullptr);
+// the first conv of a block already computed whole by another launch (the composed init pair): its output and channel partials,
+// both workspace blocks res_block takes over
+struct ConvDone {
+  float* h1 = nullptr;
+  float* part = nullptr;
+  int units = 0;
+};
 float* res_block(Run& r, const ResP& w, const float* x0, int c0, const float* x1, int c1, Dims3 dims,
-                 float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr, float* h1_side = nullptr);
+                 float** part_out = nullptr, int* units_out = nullptr, LazyClose* lazy = nullptr, float* h1_side = nullptr,
+                 const ConvDone* h1_done = nullptr);
 float* attn_block(Run& r, const AttnP& w, const float* x, Dims3 dims, float* xpart = nullptr, int xunits = 0);
 // conv_backward.hip
 void bias_grad(Run& r, const float* dy, int C, int64_t vox, float* db);

@@ -156,6 +156,8 @@ _SIGNATURES = {
     "cd_op_cyl_conv_transpose": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                            C.POINTER(C.c_int32), _P, _P]),
     "cd_op_init_conv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, _P]),
+    "cd_op_init_pair_conv": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.c_int,
+                                       C.POINTER(C.c_int32), C.c_int, _P, _P]),
     "cd_op_group_norm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "cd_op_resnet_block": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(_P), _P, _P, C.c_int, C.c_int,
                                      C.POINTER(C.c_int32), C.c_int, _P, C.c_size_t, _P]),
@@ -1071,6 +1073,27 @@ class Ops:
         _check(self.lib.cd_op_init_conv(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, cin, cout, _i32x3((D, H, W)),
                                         sc.data_ptr(), _stream()))
         return y
+
+    def init_pair_conv(self, x, w0, b0, w1, b1, profiles=None, scale=None, slabs=0, y=None, part=None):
+        """The init conv followed by a 32 -> 32 3x3x3 conv as the one composed 5x5x5 launch.  x: (B, D, H, W), the data channel;
+        w0 (32, cin, 3, 3, 3) with cin = 1 + coordinate channels; profiles = (r_w, z_d, phi_h, use_rz, use_phi) or None; scale:
+        (B,) per-sample multiplier of x or None.  y (B, D, H, W, 32) and part (>= B * D * 64 floats) may be the caller's own
+        (guard-band tests).  Returns (y, stats, units), stats as zslide_conv_chunked's."""
+        x, w0, w1 = _dev32(x, "x"), _dev32(w0, "w0"), _dev32(w1, "w1")
+        B, D, H, W = x.shape
+        cin = w0.shape[1]
+        if y is None:
+            y = torch.empty((B, D, H, W, 32), dtype=torch.float32, device=x.device)
+        if part is None:
+            part = torch.zeros((B * D * 64,), dtype=torch.float32, device=x.device)
+        r_w, z_d, phi_h, use_rz, use_phi = profiles if profiles is not None else (None, None, None, 0, 0)
+        units = C.c_int()
+        sc = self.scratch(B, 32, D * H * W)
+        _check(self.lib.cd_op_init_pair_conv(x.data_ptr(), w0.data_ptr(), _ptr(b0), w1.data_ptr(), _ptr(b1), cin, _ptr(r_w), _ptr(z_d),
+                                             _ptr(phi_h), int(use_rz), int(use_phi), _ptr(scale), y.data_ptr(), part.data_ptr(),
+                                             C.byref(units), B, _i32x3((D, H, W)), int(slabs), sc.data_ptr(), _stream()))
+        u = units.value
+        return y, part.view(-1)[:B * u * 64].view(B, u, 32, 2).double().sum(1), u
 
     def group_norm(self, x_cl, gamma, beta, groups, silu=False, add_bc=None, residual=None):
         x = _dev32(x_cl, "x")

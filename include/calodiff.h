@@ -687,6 +687,16 @@ int cd_op_cyl_conv_transpose(const float* x, const float* w, const float* bias, 
 /* small-Cin planar 3x3x3 conv (init_conv, models.py:562-564): x NCDHW (B,cin,D,H,W) -> y channels-last (B,D,H,W,cout). */
 int cd_op_init_conv(const float* x_ncdhw, const float* w, const float* bias, float* y, int batch, int cin, int cout,
                     const int32_t dims[3], void* scratch, void* stream);
+/* The denoiser's init conv followed by the 32 -> 32 3x3x3 conv that reads it (downs[0] block 1, conv 1), as ONE launch: a
+ * one-channel 5x5x5 conv of scale_b[b] * x with weights composed per boundary class, plus a table that carries the coordinate
+ * channels and both biases.  x: (B, D, H, W), the data channel; w0 (32, cin, 3,3,3) / b0 and w1 (32, 32, 3,3,3) / b1: the two
+ * convs; channels 1.. of w0 read the coordinate images built from r_w[W], z_d[D], phi_h[H] (use_rz: R and Z, use_phi: phi;
+ * cin = 1 + 2 use_rz + use_phi).  The composed data is built in `scratch` by the call.  y: (B, D, H, W, 32); ch_part as
+ * cd_op_zslide_conv's, one unit per workgroup, capacity batch * D * 64 floats; slabs: workgroups per sample (0: the launcher's
+ * own count).  An error where the grid is not eligible (an axis of z or r with a single voxel, or a plane too large for LDS). */
+int cd_op_init_pair_conv(const float* x, const float* w0, const float* b0, const float* w1, const float* b1, int cin, const float* r_w,
+                         const float* z_d, const float* phi_h, int use_rz, int use_phi, const float* scale_b, float* y, float* ch_part,
+                         int* units, int batch, const int32_t dims[3], int slabs, void* scratch, void* stream);
 /* GroupNorm (+SiLU) (+ per-(b,c) additive embedding) (+ residual), Block.forward / PreNorm (models.py:160-169,321-329). */
 int cd_op_group_norm(const float* x, float* y, const float* gamma, const float* beta, int batch, int channels,
                      int64_t voxels, int groups, int silu, const float* add_bc, const float* residual,
