@@ -57,6 +57,12 @@ class CdLayerMlpDesc(C.Structure):
                 ("n_res", C.c_int32), ("time_embed_kind", C.c_int32), ("objective", C.c_int32), ("sigma_data", C.c_float)]
 
 
+class CdHlfDesc(C.Structure):
+    """Host tables of one binning geometry (cd_hlf_create copies them to the device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_layers", C.c_int32), ("layer_offset", C.POINTER(C.c_int32)),
+                ("eta", C.POINTER(C.c_double)), ("phi", C.POINTER(C.c_double)), ("with_centres", C.POINTER(C.c_int32))]
+
+
 class CdStep(C.Structure):
     _fields_ = [("sigma", C.c_float), ("sigma_prev_masked", C.c_float), ("ddim_sigma", C.c_float), ("denom", C.c_float)]
 
@@ -141,6 +147,9 @@ _SIGNATURES = {
     "cd_generator_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_generator_run": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64),
                                    _P, C.c_size_t, _P]),
+    "cd_hlf_create": (C.c_int, [C.POINTER(CdHlfDesc), C.POINTER(_P), _P]),
+    "cd_hlf_destroy": (C.c_int, [_P]),
+    "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),

@@ -8,7 +8,13 @@ flat shower: ``bin_edges`` holds their offsets.
 
 This is what ``geom1.GeomConverter(bins=...)`` reads: ``r_edges``, ``alphaListPerLayer``, ``GetBinEdges()`` and
 ``GetRelevantLayers()``; ``r_bins``, ``a_bins``, ``bin_edges`` and ``GetTotalNumberOfBins()`` are kept for callers of the reference
-class.  The eta / phi positions the reference also derives (plotting only) are not."""
+class.
+
+``eta_all_layers`` / ``phi_all_layers`` / ``GetEtaPhiAllLayers()`` are the voxel positions the reference derives in
+``SetEtaAndPhiFromPolar`` (:72-108), which ``hlf.HighLevelFeatures`` weighs the energies with: per layer a float64 array in the flat
+shower's voxel order, ``eta = r_mid * cos(alpha_centre)`` and ``phi = r_mid * sin(alpha_centre)``; a layer without voxels has an empty
+array.  The reference's quirk is kept: ``GetRelevantLayers()`` holds layer INDICES and ``GetLayersWithBinningInAlpha()`` the XML
+``id`` attributes, which differ where ids skip (Dataset 1's 0, 1, 2, 3, 12)."""
 from __future__ import annotations
 
 import math
@@ -46,6 +52,13 @@ class XMLHandler:
         self.bin_edges = [0]
         for n in self.bin_number:
             self.bin_edges.append(n + self.bin_edges[-1])
+        self.eta_all_layers, self.phi_all_layers = [], []
+        for layer, (nr, na) in enumerate(zip(self.r_bins, self.a_bins)):
+            # alpha-major, r fastest (fill_r_a_lists, :72-83); a layer without voxels has no alpha bins either
+            r_list = np.array(self.r_midvalue[layer] * (na if nr > 0 else 0), dtype=np.float64)
+            a_list = [a for a in (self.alphaListPerLayer[layer][0] if nr > 0 else []) for _ in range(nr)]
+            self.eta_all_layers.append(r_list * np.cos(np.array(a_list, dtype=np.float64)))
+            self.phi_all_layers.append(r_list * np.sin(np.array(a_list, dtype=np.float64)))
 
     @staticmethod
     def _midpoints(arr):
@@ -66,6 +79,9 @@ class XMLHandler:
 
     def GetBinEdges(self):
         return self.bin_edges
+
+    def GetEtaPhiAllLayers(self):
+        return self.eta_all_layers, self.phi_all_layers
 
     def GetRelevantLayers(self):
         return self.relevantlayers

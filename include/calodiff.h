@@ -649,6 +649,42 @@ int cd_generator_run(CdGenerator* gen, int batch, const float* energy, int energ
                      uint64_t seed, uint64_t offset, int first_row, int global_batch, float* showers, float* layers_out /* nullable */,
                      uint64_t* next_offset /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- shower observables: the CaloChallenge high-level features -------------------------------------------------------
+ * HighLevelFeatures.CalculateFeatures of the reference (calodiffusion/utils/HighLevelFeatures.py:48-89) over the voxel positions
+ * XMLHandler.SetEtaAndPhiFromPolar derives (utils/XMLHandler.py:72-108): per shower and layer the deposited energy, the centre of
+ * energy in eta and phi and their widths -- and the hit count and brightest voxel the reference's plots take from the same
+ * showers (utils/plots.py:688, 916, 982) -- in one pass over the showers instead of one float64 temporary per product and layer.
+ *
+ * The descriptor holds HOST pointers, copied to the device by cd_hlf_create (the call allocates, and synchronises `stream`):
+ * layer l owns voxels [layer_offset[l], layer_offset[l + 1]) of a flat shower of V = layer_offset[n_layers] voxels (the
+ * `bin_edges`), eta / phi are the V positions, and with_centres[l] != 0 where centres and widths are defined (the reference:
+ * l in layersBinnedInAlpha, :78-79).  A layer without voxels has no record; the R layers with voxels, in ascending l, are
+ * GetRelevantLayers().  Refused with CD_EINVAL, before anything touches the device: a struct_size other than
+ * sizeof(CdHlfDesc), n_layers <= 0, a null layer_offset / eta / phi / with_centres table, layer_offset[0] != 0, a
+ * layer_offset that decreases, V == 0.
+ * (Tag and typedef are declared apart because the struct holds pointers: a binder lays it out with its own pointer type.) */
+struct CdHlfDesc {
+  uint32_t struct_size;         /* = sizeof(CdHlfDesc) */
+  int32_t n_layers;
+  const int32_t* layer_offset;  /* [n_layers + 1] */
+  const double* eta;            /* [V] */
+  const double* phi;            /* [V] */
+  const int32_t* with_centres;  /* [n_layers] */
+};
+typedef struct CdHlfDesc CdHlfDesc;
+typedef struct CdHlf CdHlf;
+int cd_hlf_create(const CdHlfDesc* desc, CdHlf** out, void* stream);
+int cd_hlf_destroy(CdHlf* hlf);
+/* showers (batch, V) fp32 on the device, in physical units.  out (batch, R, 8) fp64 = {E, EC_eta, EC_phi, var_eta, var_phi,
+ * width_eta, width_phi, max_voxel} and n_hits (batch, R) int32 = the number of voxels > threshold, with (:48-68)
+ *   E = sum e,   EC_c = sum c e / (E + 1e-16),   var_c = max(sum c c e / (E + 1e-16) - EC_c^2, 0),   width_c = sqrt(var_c);
+ * the six centre / variance / width values of a layer without centres are 0.  Every shower element is read once.  A layer of
+ * a shower is summed by 16 lanes: lane j takes the layer's voxels j, j + 16, ... in ascending order, every sum is fp64 (the
+ * voxel energies enter exactly), and the lanes are combined by a fixed tree -- no atomics, so repeated calls are bitwise equal and a record does not depend on the batch it is in or on the row's alignment.
+ * The grid is layers x shower slices in one dimension and is capped: any batch an int holds.  Nothing is allocated and the
+ * stream is not synchronised. */
+int cd_hlf_compute(const CdHlf* hlf, const float* showers, int batch, float threshold, double* out, int32_t* n_hits, void* stream);
+
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
  * "bf16x3" (convolutions on an exact three-term bf16 split, 6 MFMAs; attention unfused on the f32-input MFMA: full fp32 range)
