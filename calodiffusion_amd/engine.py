@@ -150,6 +150,8 @@ _SIGNATURES = {
     "cd_hlf_create": (C.c_int, [C.POINTER(CdHlfDesc), C.POINTER(_P), _P]),
     "cd_hlf_destroy": (C.c_int, [_P]),
     "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "cd_fpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "cd_fpd_moments": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),

@@ -1,0 +1,281 @@
+"""The reference's evaluation metric (calodiffusion/train/evaluate.py:21-79): ``FDP``, the Frechet physics distance between generated
+and Geant4 showers in the space of the CaloChallenge observables -- the objective of the reference's Optuna search and the figure
+its validation quotes.  The reference hands ``HighLevelFeatures``' arrays to ``jetnet.evaluation.fpd``; this package does not
+depend on jetnet, so ``fpd`` is defined here, after Kansal et al., Phys. Rev. D 107, 076017, with the signature and defaults
+jetnet documents:
+
+  1. ``normalise``: both arrays are divided by the per-column ``max|real_features|`` (a column whose maximum is 0 stays);
+  2. batch sizes ``(1 / linspace(1 / min_samples, 1 / max_samples, num_points)).astype(int32)``;
+  3. per batch size, ``num_batches`` times: ``rs.choice(len(X), size=b)`` then ``rs.choice(len(Y), size=b)`` of
+     ``rs = np.random.RandomState(seed)`` (the stream of ``np.random.seed(seed)`` and the global ``np.random.choice``);
+  4. per pair the Frechet distance of the two Gaussians, ``|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2)``, averaged per size;
+  5. a least-squares fit of ``a + b / N`` with ``a, b >= 0`` to those means; the result is ``(a, its standard error)``.
+
+Step 3's 400 means and covariances of up to 50 000 gathered rows are the expensive part and run on the device
+(``cd_fpd_moments``, include/calodiff.h: the Gram matrices on the fp64 matrix instruction): both arrays are uploaded once, as one
+matrix, the draws stay on the host and their index lists go up one batch size at a time, ``2 num_batches`` sets a call.  Steps 4
+and 5 are NumPy on the host (two symmetric eigen-decompositions per pair; no SciPy).  There is no host fallback for step 3.
+
+Not provided: ``ComparisonNetwork`` and ``CNNCompare`` of the same reference module (a torchvision ResNet, not a dependency of
+this package), and jetnet's kernel physics distance (KPD).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+import numpy as np
+import torch
+
+from . import engine
+from .hlf import HighLevelFeatures
+
+MAX_FEATURES = 256  # CD_FPD_MAX_D
+
+
+class FDPCalculationError(Exception):
+    def __init__(self, *args):
+        super().__init__(*args)
+
+
+# ---- step 2 and 3: the draws (host) ---------------------------------------------------------------------------------------
+
+def fpd_batch_sizes(min_samples=20_000, max_samples=50_000, num_points=10):
+    """The bootstrap sample sizes: equally spaced in 1 / N between ``min_samples`` and ``max_samples``."""
+    if not (int(num_points) >= 1 and 2 <= int(min_samples) <= int(max_samples)):
+        raise ValueError(f"fpd: needs 2 <= min_samples <= max_samples and num_points >= 1, got {min_samples}, {max_samples}, {num_points}")
+    return (1 / np.linspace(1 / min_samples, 1 / max_samples, num_points)).astype("int32")
+
+
+def fpd_index_lists(n_real, n_gen, batch_sizes, num_batches=20, seed=42):
+    """Yields, per batch size in order, the int64 array (num_batches, 2, b) of row indices: [k, 0] into the real and [k, 1] into
+    the generated features, drawn with replacement in the order ``fpd`` documents."""
+    if n_real < 1 or n_gen < 1:
+        raise ValueError(f"fpd: an array has no rows ({n_real} and {n_gen})")
+    rs = np.random.RandomState(seed)
+    for b in batch_sizes:
+        out = np.empty((num_batches, 2, int(b)), dtype=np.int64)
+        for k in range(num_batches):
+            out[k, 0] = rs.choice(n_real, size=int(b))
+            out[k, 1] = rs.choice(n_gen, size=int(b))
+        yield out
+
+
+# ---- step 3: the moments (device) -----------------------------------------------------------------------------------------
+
+_workspaces = {}  # device index -> uint8 tensor, grown on demand
+
+
+def _workspace(device, nbytes):
+    ws = _workspaces.get(device.index)
+    if ws is None or ws.numel() < nbytes:
+        _workspaces.pop(device.index, None)
+        ws = _workspaces[device.index] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    return ws
+
+
+def moments_workspace_bytes(d, sets, max_count):
+    nbytes = engine.load_library().cd_fpd_workspace_bytes(int(d), int(sets), int(max_count))
+    if nbytes == 0:
+        engine._check(-1)
+    return nbytes
+
+
+def launch_moments(x, centre, idx, counts, mean, cov, status, workspace=None):
+    """One ``cd_fpd_moments`` call on the current stream, nothing allocated (unless ``workspace`` is None), nothing
+    synchronised.  x (rows, d) float64, centre (d,) float64, idx (sets, idx_stride) int32, mean (sets, d), cov (sets, d, d)
+    float64 and status (1,) int32: contiguous tensors on one device; counts: a sequence of ``sets`` ints (host)."""
+    lib = engine.load_library()
+    sets, d = idx.shape[0], x.shape[1]
+    for t, dt, name in ((x, torch.float64, "x"), (centre, torch.float64, "centre"), (idx, torch.int32, "idx"), (mean, torch.float64, "mean"),
+                        (cov, torch.float64, "cov"), (status, torch.int32, "status")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise ValueError(f"launch_moments: {name} must be a contiguous {dt} CUDA tensor")
+    if len(counts) != sets or centre.numel() != d or mean.numel() != sets * d or cov.numel() != sets * d * d or status.numel() < 1:
+        raise ValueError(f"launch_moments: shapes do not match {sets} sets of {d} features")
+    c_counts = (C.c_int32 * sets)(*[int(c) for c in counts])
+    with torch.cuda.device(x.device):
+        if workspace is None:
+            workspace = _workspace(x.device, moments_workspace_bytes(d, sets, max(c_counts)))
+        engine._check(lib.cd_fpd_moments(x.data_ptr(), x.shape[0], d, centre.data_ptr(), idx.data_ptr(), idx.shape[1], c_counts, sets,
+                                         mean.data_ptr(), cov.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                         engine._stream()))
+
+
+def _device_f64(a, name):
+    """A float64 (rows, d) tensor on the device: a CUDA tensor is cast, anything else is uploaded."""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        t = a.detach().to(torch.float64)
+    else:
+        engine.require_gpu()
+        host = a.detach().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        t = torch.from_numpy(np.array(host, dtype=np.float64, order="C")).cuda()
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a (rows, features) array, got shape {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _pack_lists(index_lists):
+    counts = [len(l) for l in index_lists]
+    if not counts:
+        raise ValueError("bootstrap_moments: no index lists")
+    idx = np.zeros((len(counts), max(max(counts), 1)), dtype=np.int32)
+    for s, l in enumerate(index_lists):
+        l = np.asarray(l)
+        if l.ndim != 1 or l.size < 2:
+            raise ValueError(f"bootstrap_moments: set {s} holds {l.size} rows, a covariance needs at least 2 rows")
+        if l.size and (l.min() < -2 ** 31 or l.max() >= 2 ** 31):
+            raise ValueError(f"bootstrap_moments: set {s} holds an index beyond int32")
+        idx[s, :len(l)] = l
+    return idx, counts
+
+
+def _raise_on_status(status, stride, rows):
+    word = int(status.item())
+    if word:
+        s, k = divmod(word - 1, stride)
+        raise ValueError(f"bootstrap_moments: set {s}, position {k} holds a row index outside [0, {rows})")
+
+
+def bootstrap_moments(x, index_lists, centre=None):
+    """np.mean(x[l], axis=0) and np.cov(x[l], rowvar=False) for every index list l, on the device: (sets, d) and (sets, d, d)
+    float64 NumPy arrays.  ``x``: (rows, d), NumPy or CUDA tensor, cast to float64; lists may differ in length (at least 2
+    entries each, duplicates allowed); ``centre`` (d,): the shift applied before the sums (default: the column mean of x).
+    Raises ``ValueError`` naming the set and position of a row index outside x."""
+    x = _device_f64(x, "x")
+    idx, counts = _pack_lists(index_lists)
+    with torch.cuda.device(x.device):
+        centre = x.mean(dim=0) if centre is None else _device_f64(np.asarray(centre).reshape(1, -1), "centre").reshape(-1)
+        idx_d = torch.from_numpy(idx).to(x.device)
+        sets, d = idx.shape[0], x.shape[1]
+        mean = torch.empty((sets, d), dtype=torch.float64, device=x.device)
+        cov = torch.empty((sets, d, d), dtype=torch.float64, device=x.device)
+        status = torch.zeros((1,), dtype=torch.int32, device=x.device)
+        launch_moments(x, centre.contiguous(), idx_d, counts, mean, cov, status)
+        _raise_on_status(status, idx.shape[1], x.shape[0])
+        return mean.cpu().numpy(), cov.cpu().numpy()
+
+
+# ---- step 4 and 5 (host) ---------------------------------------------------------------------------------------------------
+
+def frechet_distance(mu1, sigma1, mu2, sigma2):
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2).  The last trace is the sum of the roots of the eigenvalues of
+    R S2 R (symmetrised, negative ones clipped), R = S1^(1/2) from the eigen-decomposition of S1 with its eigenvalues clipped
+    at 0: the same spectrum as S1 S2, through symmetric matrices only."""
+    mu1, mu2 = np.asarray(mu1, dtype=np.float64), np.asarray(mu2, dtype=np.float64)
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, dtype=np.float64)), np.atleast_2d(np.asarray(sigma2, dtype=np.float64))
+    if mu1.shape != mu2.shape or s1.shape != s2.shape or s1.shape != (mu1.size, mu1.size):
+        raise ValueError(f"frechet_distance: shapes {mu1.shape}, {s1.shape}, {mu2.shape}, {s2.shape} do not belong together")
+    w, v = np.linalg.eigh(s1)
+    root = (v * np.sqrt(np.maximum(w, 0.0))) @ v.T
+    m = root @ s2 @ root
+    lam = np.linalg.eigvalsh((m + m.T) / 2)
+    diff = mu1 - mu2
+    return float(diff @ diff + np.trace(s1) + np.trace(s2) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
+
+
+def fit_extrapolation(batch_sizes, values):
+    """Least squares of ``a + b / N`` with a >= 0 and b >= 0 -> (a, error of a).  The unconstrained solution where it is
+    feasible, else the best of the edges a = 0 and b = 0 and the origin; error = sqrt(cov[0, 0]), cov = RSS / (M - 2) (A^T A)^-1
+    with A = [1, 1 / N]."""
+    x, y = 1.0 / np.asarray(batch_sizes, dtype=np.float64), np.asarray(values, dtype=np.float64)
+    M = x.size
+    if M < 3 or y.shape != x.shape:
+        raise ValueError(f"fit_extrapolation: needs at least 3 points and as many values, got {M} and {y.size}")
+    xm, ym = x.mean(), y.mean()
+    sxx = ((x - xm) ** 2).sum()
+    if not sxx > 0.0:
+        raise ValueError("fit_extrapolation: all batch sizes are equal")
+    b = ((x - xm) * (y - ym)).sum() / sxx
+    a = ym - b * xm
+    rss = lambda a, b: float(((y - a - b * x) ** 2).sum())  # noqa: E731
+    if a < 0.0 or b < 0.0:
+        edges = [(0.0, max(float((x * y).sum() / (x * x).sum()), 0.0)), (max(float(ym), 0.0), 0.0), (0.0, 0.0)]
+        a, b = min(edges, key=lambda ab: rss(*ab))
+    var_a = rss(a, b) / (M - 2) * (1.0 / M + xm * xm / sxx)  # (A^T A)^-1 [0, 0] = sum x^2 / (M sxx)
+    return float(a), float(np.sqrt(var_a))
+
+
+def fpd(real_features, gen_features, min_samples=20_000, max_samples=50_000, num_batches=20, num_points=10, normalise=True, seed=42):
+    """The Frechet physics distance of two feature arrays (rows, d), extrapolated to infinite sample size: (value, error).
+    NumPy arrays or CUDA tensors, cast to float64; see the module docstring for the definition."""
+    X, Y = _device_f64(real_features, "real_features"), _device_f64(gen_features, "gen_features")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError(f"fpd: {X.shape[1]} real and {Y.shape[1]} generated features")
+    if not 1 <= X.shape[1] <= MAX_FEATURES:
+        raise ValueError(f"fpd: {X.shape[1]} features, the device kernel takes 1 to {MAX_FEATURES}")
+    sizes = fpd_batch_sizes(min_samples, max_samples, num_points)
+    if int(num_batches) < 1:
+        raise ValueError(f"fpd: num_batches must be positive, got {num_batches}")
+    for t, name in ((X, "real_features"), (Y, "gen_features")):
+        if t.shape[0] == 0:
+            raise ValueError(f"fpd: {name} has no rows")
+        if t.shape[0] < min_samples:
+            warnings.warn(f"fpd: {name} has {t.shape[0]} rows, fewer than min_samples = {min_samples}: the bootstrap draws with "
+                          "replacement from too small a set and the result is unreliable", RuntimeWarning, stacklevel=2)
+    with torch.cuda.device(X.device):
+        Y = Y.to(X.device)
+        if normalise:
+            m = X.abs().amax(dim=0)
+            m = torch.where(m == 0, torch.ones_like(m), m)
+            X, Y = X / m, Y / m
+        n_real, d = X.shape
+        Z = torch.cat([X, Y])  # one matrix: set 2 k of a call indexes the real rows, set 2 k + 1 the generated ones
+        del X, Y
+        centre = Z.mean(dim=0)
+        status = torch.zeros((1,), dtype=torch.int32, device=Z.device)
+        pending = []
+        for b, lists in zip(sizes, fpd_index_lists(n_real, Z.shape[0] - n_real, sizes, num_batches, seed)):
+            lists[:, 1] += n_real
+            idx = torch.from_numpy(lists.reshape(2 * num_batches, int(b)).astype(np.int32)).to(Z.device)
+            mean = torch.empty((2 * num_batches, d), dtype=torch.float64, device=Z.device)
+            cov = torch.empty((2 * num_batches, d, d), dtype=torch.float64, device=Z.device)
+            launch_moments(Z, centre, idx, [int(b)] * (2 * num_batches), mean, cov, status)
+            pending.append((idx, mean, cov))
+        values = []
+        for idx, mean, cov in pending:  # the host's eigen-decompositions of one size run beside the device's later sizes
+            mu, sigma = mean.cpu().numpy(), cov.cpu().numpy()
+            values.append(np.mean([frechet_distance(mu[2 * k], sigma[2 * k], mu[2 * k + 1], sigma[2 * k + 1]) for k in range(num_batches)]))
+    return fit_extrapolation(sizes, values)
+
+
+class FDP:
+    """The reference's ``FDP`` (train/evaluate.py:21-79).  Its constructor is spelled ``_init__`` there and never runs; this
+    one takes the same two arguments and works.  ``fpd_kwargs`` go to ``fpd`` (the reference uses jetnet's defaults)."""
+
+    def __init__(self, binning_dataset, particle, **fpd_kwargs):
+        self.hlf = HighLevelFeatures(particle, filename=binning_dataset)
+        self.reference_hlf = HighLevelFeatures(particle, filename=binning_dataset)
+        self.fpd_kwargs = fpd_kwargs
+
+    def pre_process(self, energies, hlf_class, label):
+        """The reference's array, label column included (``feature_matrix`` builds the rest)."""
+        features = hlf_class.feature_matrix(energies)
+        return np.concatenate([features, label * np.ones((features.shape[0], 1))], axis=1)
+
+    def __call__(self, trained_model, eval_data, kwargs=None) -> float:
+        reference_shower, reference_energy = [], []
+        for energy, _, data in eval_data:
+            reference_shower.append(_to_numpy(data))
+            reference_energy.append(_to_numpy(energy))
+        reference_shower = np.concatenate(reference_shower)
+        reference_energy = np.concatenate(reference_energy)
+        generated, energies = trained_model.generate(data_loader=eval_data, sample_steps=trained_model.config.get("NSTEPS"), sample_offset=0)
+        self.hlf.CalculateFeatures(_flat(generated))
+        self.reference_hlf.CalculateFeatures(_flat(reference_shower))
+        source_array = self.pre_process(energies, self.hlf, 0.)[:, :-1]
+        reference_array = self.pre_process(reference_energy, self.reference_hlf, 1.)[:, :-1]
+        try:
+            value, _ = fpd(np.nan_to_num(source_array), np.nan_to_num(reference_array), **self.fpd_kwargs)
+        except ValueError as err:
+            raise FDPCalculationError(err)
+        return value
+
+
+def _to_numpy(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _flat(showers):
+    showers = _to_numpy(showers)
+    return showers.reshape(showers.shape[0], int(np.prod(showers.shape[1:])))

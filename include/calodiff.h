@@ -685,6 +685,37 @@ int cd_hlf_destroy(CdHlf* hlf);
  * stream is not synchronised. */
 int cd_hlf_compute(const CdHlf* hlf, const float* showers, int batch, float threshold, double* out, int32_t* n_hits, void* stream);
 
+/* ---- Frechet physics distance: bootstrap moments of the feature matrix ----------------------------------------------
+ * What the reference's FDP hands to jetnet.evaluation.fpd (train/evaluate.py:66-79) is a feature matrix per shower set; the
+ * distance bootstraps the mean and covariance of row samples drawn with replacement.  cd_fpd_moments computes them for `sets`
+ * index lists in one call.  All arrays but `counts` are on the device.
+ *   x (rows, d) float64, row-major;  centre [d];  idx [sets * idx_stride] int32, set s holding its counts[s] row indices at
+ *   idx[s * idx_stride + k], k < counts[s] (duplicates are normal; entries at k >= counts[s] are never read);  counts [sets]: HOST.
+ * With n = counts[s], y_k = x[idx_k] - centre, S_i = sum_k y_ki and G_ij = sum_k y_ki y_kj:
+ *   mean [s][i] = centre_i + S_i / n,    cov [s][i][j] = (G_ij - S_i S_j / n) / (n - 1)     (np.cov(rowvar=False) of the rows)
+ * mean (sets, d) and cov (sets, d, d) float64; both triangles of cov are written, from the same registers (bitwise symmetric).
+ * G runs on the fp64 matrix instruction (v_mfma_f64_16x16x4_f64) over the 16-column tiles i <= j of d + 1 columns padded to a
+ * multiple of 16: column d is the constant 1, which yields S from the same products.  Rows are split into slices of
+ * CD_FPD_SLICE_ROWS consecutive list positions, a workgroup each; the slices' partial Grams are summed in ascending order by a
+ * second launch -- no floating-point atomics: a set's result is a function of (x, its index list, d, centre) alone, the same
+ * bits alone or among other sets, at any `sets` and idx_stride.
+ * Every index is checked before it is used as an address: one outside [0, rows) is never dereferenced, its set's mean and
+ * cov are NaN, and *status (device int32, zeroed by the call) receives 1 + s * idx_stride + k by atomicMax -- of the one
+ * offender, or of the last of several (cd_preprocess reports its rows the same way).
+ * Limits: 1 <= d <= CD_FPD_MAX_D, counts[s] >= 2, sets >= 1, sets * idx_stride < 2^31 - 1.  Refused with CD_EINVAL before
+ * anything touches the device: a violation of these, a null pointer, rows <= 0, idx_stride < max(counts), a workspace
+ * shorter than cd_fpd_workspace_bytes(d, sets, max(counts)).  Nothing is allocated and the stream is not synchronised. */
+#define CD_FPD_MAX_D 256
+#define CD_FPD_SLICE_ROWS 2048
+/* bytes of workspace for `sets` lists of at most max_count rows (train/evaluate.py:66-79):
+ * sets * ceil(max_count / CD_FPD_SLICE_ROWS) * (T (T + 1) / 2 * 2048 + 256), T = ceil((d + 1) / 16); 0 (and cd_last_error)
+ * for arguments outside the limits. */
+size_t cd_fpd_workspace_bytes(int d, int sets, int max_count);
+/* the bootstrap moments jetnet.evaluation.fpd takes per batch (train/evaluate.py:66-79); see above */
+int cd_fpd_moments(const double* x, int64_t rows, int d, const double* centre, const int32_t* idx, int64_t idx_stride,
+                   const int32_t* counts /* host */, int sets, double* mean, double* cov, int32_t* status, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
  * "bf16x3" (convolutions on an exact three-term bf16 split, 6 MFMAs; attention unfused on the f32-input MFMA: full fp32 range)
