@@ -152,6 +152,11 @@ _SIGNATURES = {
     "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
     "cd_fpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "cd_fpd_moments": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cd_kpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "cd_kpd_sums": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int, _P, _P, _P, C.c_size_t,
+                              _P]),
+    "cd_column_histograms_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "cd_column_histograms": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),

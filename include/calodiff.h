@@ -716,6 +716,59 @@ int cd_fpd_moments(const double* x, int64_t rows, int d, const double* centre, c
                    const int32_t* counts /* host */, int sets, double* mean, double* cov, int32_t* status, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- Kernel physics distance and separation powers: the other two figures over the same feature matrix ----------------
+ * The reference's metrics program (calodiffusion/tests/hgcal_metrics.py:401-432) scores one feature matrix three ways: the
+ * Frechet distance above, jetnet.evaluation.kpd (:424) and a separation power per feature column (:407-415, make_hist ->
+ * utils._separation_power, utils/utils.py:167-175).
+ *
+ * cd_kpd_sums: a batch of the kernel physics distance is an MMD estimate with the polynomial kernel
+ * k(a, b) = (gamma a.b + 1)^degree over m real and n generated rows drawn with replacement.  Sets pair up: set 2 k lists the
+ * real rows X and set 2 k + 1 the generated rows Y of batch k, both as rows of the one matrix x (layout of x, idx and counts
+ * as for cd_fpd_moments; counts[2 k] = m and counts[2 k + 1] = n may differ).  sums (sets / 2, 3) float64 receives
+ *   sums[k] = { sum_{i != j} k(X_i, X_j),   sum_{i != j} k(Y_i, Y_j),   sum_{i, j} k(X_i, Y_j) },
+ * i and j being list POSITIONS: two positions that drew the same row are an ordinary pair and are counted.  The division by
+ * m (m - 1), n (n - 1) and m n and the subtraction are the caller's.  The kernel matrices are never formed: a workgroup owns
+ * one 64 x 64 block (CD_KPD_BLOCK) of the upper triangle of the Gram matrix of the m + n gathered rows, on
+ * v_mfma_f64_16x16x4_f64 over d padded with zeros to a multiple of 4, raises gamma g + 1 to `degree` by repeated
+ * multiplication, weighs each element by its region and leaves one partial triple; a second launch adds a batch's partials
+ * in a fixed order that depends on (m, n) alone -- no floating-point atomics: a batch's sums are a function of (x, its two
+ * lists, d, gamma, degree) alone, the same bits alone or among other batches, at any `sets` and idx_stride.
+ * Indices are guarded as in cd_fpd_moments: one outside [0, rows) is never dereferenced, its batch's three sums are NaN and
+ * *status (device int32, zeroed by the call) receives 1 + s * idx_stride + k by atomicMax.  Entries at k >= counts[s] are
+ * never read.
+ * Limits: 1 <= d <= CD_FPD_MAX_D, sets even and >= 2, 2 <= counts[s] <= CD_KPD_MAX_COUNT, 1 <= degree <= 8,
+ * sets * idx_stride < 2^31 - 1.  Refused with CD_EINVAL before anything touches the device: a violation of these, a null
+ * pointer, rows <= 0, idx_stride < max(counts), a workspace shorter than cd_kpd_workspace_bytes(sets, max(counts)).  Nothing
+ * is allocated and the stream is not synchronised. */
+#define CD_KPD_BLOCK 64
+#define CD_KPD_MAX_COUNT 1048576
+/* bytes of workspace for `sets` lists of at most max_count rows (hgcal_metrics.py:424): sets / 2 * nb (nb + 1) / 2 * 32,
+ * nb = ceil(2 max_count / CD_KPD_BLOCK); 0 (and cd_last_error) for arguments outside the limits. */
+size_t cd_kpd_workspace_bytes(int sets, int max_count);
+/* the three kernel sums jetnet.evaluation.kpd takes per batch (hgcal_metrics.py:424); see above */
+int cd_kpd_sums(const double* x, int64_t rows, int d, const int32_t* idx, int64_t idx_stride, const int32_t* counts /* host */,
+                int sets, double gamma, int degree, double* sums, int32_t* status, void* workspace, size_t workspace_bytes,
+                void* stream);
+/* cd_column_histograms: np.histogram(x[row_begin : row_begin + row_count, j], bins=edges[j]) for every column j of the
+ * row-major float64 matrix x (., d) in one pass, as the reference's make_hist takes them (hgcal_metrics.py:409; the arithmetic
+ * on the counts, utils/utils.py:167-175, is the caller's).  edges (d, nedges) float64, ascending per column; counts
+ * (d, nedges - 1) uint32.  Bin k of column j is [edges[j][k], edges[j][k + 1]), the last one closed on the right; values
+ * outside [edges[j][0], edges[j][nedges - 1]] and NaN are dropped.  The bin is found arithmetically and then corrected
+ * against the edges as given, so the counts are exactly those of np.histogram's binary search whatever rounding the edges
+ * carry.  A workgroup counts CD_HIST_CHUNK_ROWS rows of 64 columns, whose edges it holds in LDS, into tables in LDS, every
+ * thread alone writing its own row of them (no atomics); a second launch adds the workgroups' tables in ascending order.  The
+ * caller guarantees that x holds row_begin + row_count rows.
+ * Limits: 1 <= d <= CD_FPD_MAX_D, 2 <= nedges <= CD_HIST_MAX_EDGES (edges and tables of 64 columns fill 64 KB of LDS), row_begin >= 0,
+ * 1 <= row_count < 2^32; violations, null pointers and a short workspace are CD_EINVAL before anything touches the device.
+ * Nothing is allocated and the stream is not synchronised. */
+#define CD_HIST_CHUNK_ROWS 256
+#define CD_HIST_MAX_EDGES 64
+/* ceil(row_count / CD_HIST_CHUNK_ROWS) * d * (nedges - 1) * 4 bytes (hgcal_metrics.py:409); 0 (and cd_last_error) outside the limits */
+size_t cd_column_histograms_workspace_bytes(int64_t row_count, int d, int nedges);
+/* the per-column counts behind the reference's separation powers (hgcal_metrics.py:407-415, utils/utils.py:167-175); see above */
+int cd_column_histograms(const double* x, int64_t row_begin, int64_t row_count, int d, const double* edges, int nedges,
+                         uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
  * "bf16x3" (convolutions on an exact three-term bf16 split, 6 MFMAs; attention unfused on the f32-input MFMA: full fp32 range)
