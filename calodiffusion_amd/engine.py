@@ -63,6 +63,12 @@ class CdHlfDesc(C.Structure):
                 ("eta", C.POINTER(C.c_double)), ("phi", C.POINTER(C.c_double)), ("with_centres", C.POINTER(C.c_int32))]
 
 
+class CdClassifierDesc(C.Structure):
+    """The classifier test's DNN (calodiffusion_amd.classifier)."""
+    _fields_ = [("struct_size", C.c_uint32), ("input_dim", C.c_int32), ("hidden", C.c_int32), ("num_layer", C.c_int32),
+                ("negative_slope", C.c_float), ("dropout_p", C.c_float)]
+
+
 class CdStep(C.Structure):
     _fields_ = [("sigma", C.c_float), ("sigma_prev_masked", C.c_float), ("ddim_sigma", C.c_float), ("denom", C.c_float)]
 
@@ -157,6 +163,17 @@ _SIGNATURES = {
                               _P]),
     "cd_column_histograms_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "cd_column_histograms": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "cd_classifier_num_params": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_int64)]),
+    "cd_classifier_workspace_bytes": (C.c_int, [C.POINTER(CdClassifierDesc), C.c_int, C.POINTER(C.c_size_t)]),
+    "cd_classifier_forward": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P,
+                                        C.c_size_t, _P]),
+    "cd_classifier_train_step": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, _P, C.c_int64, _P, C.c_int, C.c_uint64,
+                                           C.c_uint64, _P, _P, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double, C.c_float, C.c_int, _P,
+                                           C.c_size_t, _P]),
+    "cd_classifier_train_epoch": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, _P, C.c_int64, _P, C.c_int64, C.c_int,
+                                            C.c_uint64, C.c_uint64, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_float, _P, _P,
+                                            C.c_size_t, _P]),
+    "cd_classifier_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P]),
     "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
     "cd_get_conv_precision": (C.c_char_p, []),
     "cd_profile_begin": (C.c_int, []),
@@ -185,6 +202,10 @@ _SIGNATURES = {
     "cd_op_group_norm_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P,
                                             C.c_size_t, _P]),
     "cd_op_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "cd_op_linear_act": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int,
+                                   _P]),
+    "cd_op_linear_act_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                            C.c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -554,6 +554,29 @@ class KPD(_FeatureMetric):
         return value
 
 
+class ClassifierScore(_FeatureMetric):
+    """The classifier two-sample test as a metric object with ``FDP``'s constructor and call: the AUC of a ``DNN`` trained to tell
+    the model's generated showers (label 1) from the loader's Geant4 ones (label 0) in the space of the same feature arrays
+    (hgcal_metrics.py:434-490; ``calodiffusion_amd.classifier.ClassifierTest``, whose keyword arguments ``classifier_kwargs`` are).
+    0.5 is a perfect generator.  The full result of the last call (accuracy, JSD, calibrated figures) is kept in ``last_result``."""
+
+    def __init__(self, binning_dataset, particle, rounded_scores=False, **classifier_kwargs):
+        super().__init__(binning_dataset, particle)
+        self.rounded_scores, self.classifier_kwargs, self.last_result = rounded_scores, classifier_kwargs, None
+
+    def __call__(self, trained_model, eval_data, kwargs=None) -> float:
+        from .classifier import ClassifierTest
+        source_array, reference_array = self.feature_arrays(trained_model, eval_data)
+        features = np.concatenate([source_array, reference_array], axis=0)
+        labels = np.concatenate([np.ones(source_array.shape[0], dtype=np.float32), np.zeros(reference_array.shape[0], dtype=np.float32)])
+        try:
+            test = ClassifierTest(features.shape[1], **self.classifier_kwargs).fit(features, labels)
+            self.last_result = test.evaluate(rounded_scores=self.rounded_scores)
+        except ValueError as err:
+            raise FDPCalculationError(err)
+        return self.last_result.auc
+
+
 def _to_numpy(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 

@@ -769,6 +769,73 @@ size_t cd_column_histograms_workspace_bytes(int64_t row_count, int d, int nedges
 int cd_column_histograms(const double* x, int64_t row_begin, int64_t row_count, int d, const double* edges, int nedges,
                          uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- classifier two-sample test: the reference's DNN, trained and scored on the device --------------------------------
+ * The third figure of the reference's metrics program (calodiffusion/tests/hgcal_metrics.py:434-490): a DNN (:185-209) learns to
+ * tell generated from Geant4 rows of the feature matrix, and its accuracy, AUC and JSD on held-out rows are the result.  The
+ * network is (num_layer + 1) x [Linear -> LeakyReLU(negative_slope) -> Dropout(dropout_p)] -> Linear(hidden, 1).
+ *
+ * `weights`: a HOST array of 4 + 2 num_layer DEVICE pointers to fp32 tensors of nn.Linear shape, in the order of the module's
+ * parameters: inputlayer.weight (hidden, input_dim), inputlayer.bias, outputlayer.weight (1, hidden), outputlayer.bias, then
+ * weight (hidden, hidden) and bias of every hidden Linear.  `grads`, `exp_avg` and `exp_avg_sq` are flat fp32 device buffers
+ * of cd_classifier_num_params elements holding the tensors in that order.
+ *
+ * Arithmetic: parameters and activations are fp32; every matrix product runs on v_mfma_f32_32x32x16_bf16 as the exact
+ * three-term bf16 split of the operands (24 bits, fp32 range: features may come in any units) with fp32 accumulation.  The
+ * weight gradient sums over the batch (<= CD_CLS_MAX_BATCH) inside one accumulator: no split-K, no floating-point atomics, and
+ * every other reduction has a fixed order -- a step is bitwise reproducible.
+ * Dropout: the decision of element (row-in-batch r, column c) of layer l at step s is word r & 3 of Philox4x32-10 at counter
+ * {c, r >> 2, l, lo32(s)} under key {lo32(seed), hi32(seed) ^ hi32(s)}: dropped where the word is < floor(p 2^32), else scaled
+ * by 1 / (1 - p).  It depends on the row's place in the batch, not on which matrix row sits there, and is recomputed by the
+ * backward pass; this stream is this library's own, not torch's.
+ * A row index outside [0, rows_total) is never dereferenced: its row is staged as NaN, so its logit (and a step's loss) is NaN.
+ * Limits: 1 <= input_dim, hidden <= CD_CLS_MAX_DIM, 0 <= num_layer <= CD_CLS_MAX_LAYERS, negative_slope >= 0 (the backward pass
+ * reads the activation's derivative off its output), 0 <= dropout_p < 1, 1 <= max_rows_per_call <= CD_CLS_MAX_ROWS_PER_CALL.
+ * Violations, null pointers and a short or misaligned (256 bytes) workspace are CD_EINVAL before anything touches the device.
+ * No entry point allocates or synchronises the stream. */
+#define CD_CLS_MAX_DIM 4096
+#define CD_CLS_MAX_LAYERS 8
+#define CD_CLS_MAX_BATCH 256
+#define CD_CLS_MAX_ROWS_PER_CALL 65536
+typedef struct CdClassifierDesc {
+  uint32_t struct_size;  /* = sizeof(CdClassifierDesc) */
+  int32_t input_dim;
+  int32_t hidden;
+  int32_t num_layer;     /* hidden Linear layers after the input layer (hgcal_metrics.py:198-201) */
+  float negative_slope;  /* torch.nn.LeakyReLU(): 0.01 */
+  float dropout_p;
+} CdClassifierDesc;
+/* elements of the flat gradient / Adam buffers: the parameters of DNN (hgcal_metrics.py:185-204) */
+int cd_classifier_num_params(const CdClassifierDesc* desc, int64_t* numel);
+/* bytes of workspace for calls that take at most max_rows_per_call rows at a time (a training batch counts as its rows):
+ * the gathered rows, num_layer + 3 activation-sized buffers and three row vectors (hgcal_metrics.py:68-84, 105-123) */
+int cd_classifier_workspace_bytes(const CdClassifierDesc* desc, int max_rows_per_call, size_t* bytes);
+/* model.eval() forward (hgcal_metrics.py:107-115): logits[i] for row idx[i] of x (rows_total, input_dim), or row i where idx is
+ * NULL; `count` rows, any number, taken max_rows_per_call at a time (the size the workspace was asked for).  idx: device int32,
+ * repeats allowed. */
+int cd_classifier_forward(const CdClassifierDesc* desc, const float* const* weights, const float* x, int64_t rows_total,
+                          const int32_t* idx /* nullable */, int64_t count, float* logits, int max_rows_per_call, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* One training step (hgcal_metrics.py:77-84): forward in train mode over the rows batch_idx[0 .. batch) of x with labels
+ * labels[batch_idx[.]] (fp32, rows_total of them), dropout keyed by (seed, step); the stable BCE with logits
+ * max(z, 0) - z y + log1p(exp(-|z|)), mean over the batch, into *loss (device fp64); dL/dz = (sigmoid(z) - y) / batch; the
+ * gradient of every parameter into `grads`.  apply_adam != 0: then torch.optim.Adam's update (cd_adam_step, no weight decay)
+ * with step number adam_step >= 1; exp_avg / exp_avg_sq may be NULL otherwise.  1 <= batch <= CD_CLS_MAX_BATCH. */
+int cd_classifier_train_step(const CdClassifierDesc* desc, float* const* weights, const float* x, const float* labels, int64_t rows_total,
+                             const int32_t* batch_idx, int batch, uint64_t seed, uint64_t step, float* grads, double* loss, int apply_adam,
+                             float* exp_avg /* nullable */, float* exp_avg_sq /* nullable */, double lr, double beta1, double beta2, float eps,
+                             int adam_step, void* workspace, size_t workspace_bytes, void* stream);
+/* One epoch (train_cls, hgcal_metrics.py:68-84): perm (device int32, n_train row indices into x) is cut into batches of
+ * batch_size, the last one ragged; batch k is a training step with dropout step first_step + k and Adam step number
+ * first_step + k + 1, its loss in losses[k] (device fp64, ceil(n_train / batch_size) of them).  All steps are enqueued on
+ * `stream`: no host synchronisation, no graph capture. */
+int cd_classifier_train_epoch(const CdClassifierDesc* desc, float* const* weights, const float* x, const float* labels, int64_t rows_total,
+                              const int32_t* perm, int64_t n_train, int batch_size, uint64_t seed, uint64_t first_step, float* grads,
+                              float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, float eps, double* losses,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* The dropout mask of (seed, step, layer) as bytes (rows, n), 1 = kept: what torch.nn.Dropout (hgcal_metrics.py:197-201) draws
+ * from its own stream, from this library's; the device function the training kernels call. */
+int cd_classifier_dropout_mask(uint64_t seed, uint64_t step, int layer, float dropout_p, int rows, int n, uint8_t* mask, void* stream);
+
 /* Arithmetic of the matrix-core kernels, process-wide: "f16x2" (default; fp32 operands as two-term fp16 splits, 3 MFMAs per
  * block, fp16 RANGE -- the 3x3x3 / strided / transposed convolutions and the fused attention's projections and products),
  * "bf16x3" (convolutions on an exact three-term bf16 split, 6 MFMAs; attention unfused on the f32-input MFMA: full fp32 range)
@@ -847,6 +914,17 @@ int cd_op_group_norm_backward(const float* x, const float* gamma, const float* b
                               float* dbeta, float* dadd, int batch, int channels, int64_t voxels, int groups, int silu,
                               void* workspace, size_t workspace_bytes, void* stream);
 size_t cd_op_scratch_bytes(int batch, int max_channels, int64_t max_voxels);
+/* The classifier's layer kernels on their own -- the launches cd_classifier_train_step makes (hgcal_metrics.py:194-201).
+ * y (rows, n_out) = dropout(act(x (rows, n_in) . w (n_out, n_in)^T + bias)): act != 0: LeakyReLU(negative_slope); dropout_p > 0:
+ * the mask of (seed, step, layer), kept values scaled by 1 / (1 - dropout_p).  bias nullable.  rows <= CD_CLS_MAX_ROWS_PER_CALL. */
+int cd_op_linear_act(const float* x, const float* w, const float* bias /* nullable */, float* y, int rows, int n_in, int n_out, int act,
+                     float negative_slope, float dropout_p, uint64_t seed, uint64_t step, int layer, void* stream);
+/* Its gradients for an arbitrary dy (rows, n_out): g = dy * mask * keep_scale * act'(y), y being the forward output;
+ * dx (rows, n_in) = g . w (nullable), dw (n_out, n_in) = g^T . x, db = the column sums of g.  mask: bytes (rows, n_out), 1 = kept,
+ * or NULL (no dropout; keep_scale is ignored).  rows <= CD_CLS_MAX_BATCH; workspace: rows * n_out * 4 bytes, 16-byte aligned. */
+int cd_op_linear_act_backward(const float* x, const float* w, const float* y, const float* dy, const uint8_t* mask /* nullable */,
+                              float keep_scale, int act, float negative_slope, float* dx /* nullable */, float* dw, float* db, int rows,
+                              int n_in, int n_out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
