@@ -601,7 +601,7 @@ class DPMAdaptive(DPM):
     * with ETA = 0 the ancestral noise has amplitude sqrt(sigma_t^2 - sigma_t'^2) = 0: the trajectory is deterministic.
 
     Three denoiser calls per step at order 3 (two at order 2), each one cd_denoise_safe call.  Pinned by the same loop on the
-    CPU oracle (tests/test_host.py, tests/test_gpu_round3.py)."""
+    CPU oracle (tests/test_host.py, tests/test_gpu_samplers.py)."""
 
     def __init__(self, config):
         super().__init__(config)

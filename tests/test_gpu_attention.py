@@ -42,11 +42,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
-from helpers import attn_block_weights, seeded_unet
+from helpers import TOL_OP, attn_block_weights, profiled_launches, seeded_model_cfg, seeded_unet, unet_kwargs
 
 pytestmark = pytest.mark.gpu
 
-TOL_OP = 1e-5
 BRANCH_FLOOR = 2e-6
 SETTINGS = {"a": {}, "b": {"qscale": 12.0}, "c": {"kscale": 12.0}, "d": {"bias": 3.0}}
 
@@ -265,17 +264,16 @@ def test_two_pass_form_at_64_channels_through_unet_forward():
     """CondUnet.forward on a net whose 64-channel level has 1100 voxels, against the oracle: attn_kv_context / attn_out <2> as the
     plan calls them."""
     from oracle import torch_oracle as O
-    from test_gpu_deep import _deep_level_launches, _unet_kwargs
     _f16x2_only()
     B = 2
-    net = seeded_unet(_unet_kwargs(PLAN_GRID, PLAN_SIZES), 77).cuda()
+    net = seeded_unet(unet_kwargs(PLAN_GRID, PLAN_SIZES), 77).cuda()
     g = torch.Generator().manual_seed(5)
     x = torch.randn([B, 3] + list(PLAN_GRID), generator=g)
     cond, time = torch.randn((B, 9), generator=g), torch.rand((B,), generator=g)
     spec = O.UnetSpec(layer_sizes=list(PLAN_SIZES), channels=3, cond_size=9, data_shape=PLAN_GRID)
     with torch.no_grad():
         want = O.cond_unet_forward({k: v.cpu() for k, v in net.state_dict().items()}, spec, x, cond, time)
-    launches = _deep_level_launches(lambda: net(x.cuda(), cond=cond.cuda(), time=time.cuda()))
+    launches = profiled_launches(lambda: net(x.cuda(), cond=cond.cuda(), time=time.cuda()))
     assert "attn_kv_context C64 n1100" in launches and "attn_out C64 n1100" in launches, sorted(launches)
     got = net(x.cuda(), cond=cond.cuda(), time=time.cuda())
     err = rel_l2(got.cpu().numpy(), want.numpy())
@@ -288,9 +286,85 @@ def test_training_step_with_1100_voxels_at_64_channels():
     autograd through the fp32 oracle at test_gpu_grad_batch's bars -- attn_block_train / attn_block_bwd, the per-sample attention
     weight gradient and the exp-norm pointwise prologue at 64 channels and more than 1024 voxels (elsewhere <= 120)."""
     from oracle import torch_oracle as O
-    from test_gpu_grad_batch import _model, _train_steps_vs_oracle
+    from grad_cases import train_steps_vs_oracle
     shape = [-1, 1] + list(PLAN_GRID)
-    m, cfg = _model("tiny", LAYER_SIZE_UNET=list(PLAN_SIZES), SHAPE_PAD=shape, SHAPE_FINAL=shape)
+    m, cfg = seeded_model_cfg("tiny", dict(LAYER_SIZE_UNET=list(PLAN_SIZES), SHAPE_PAD=shape, SHAPE_FINAL=shape))
     assert O.spec_from_config(cfg).layer_sizes == list(PLAN_SIZES)
     assert tuple(O.spec_from_config(cfg).data_shape) == PLAN_GRID == tuple(m.engine().grid)
-    _train_steps_vs_oracle(f"tiny {PLAN_GRID} {PLAN_SIZES} B=2 train", m, cfg, 2, seed=11)
+    train_steps_vs_oracle(f"tiny {PLAN_GRID} {PLAN_SIZES} B=2 train", m, cfg, 2, seed=11)
+
+
+@pytest.mark.parametrize("parts", [2, 4])
+def test_cooperating_workgroups_attention_equals_the_single_workgroup_form(parts, tmp_path):
+    """attn_coop_kernel (CD_ATTN_COOP: a sample's voxels dealt to several co-operating workgroups with two in-launch barriers)
+    against the one-workgroup-per-sample attn_small_kernel at Dataset-2's level-1 grids (736 voxels, 32 and 64 channels, batch a
+    multiple of 8 so that a sample's workgroups share an XCD) -- run in a child process, CD_ATTN_COOP is read once.  The two forms
+    merge their {max, sum, context} partials differently, so they agree to rounding, not bit for bit; the range flag must stay
+    clear (a barrier that times out raises it)."""
+    import os
+    import subprocess
+    import sys
+    code = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from helpers import seeded_model
+m = seeded_model("dataset2")
+g = torch.Generator().manual_seed(5)
+B = 16
+x = torch.randn((B, 1, 45, 16, 9), generator=g).cuda()
+E, layers = torch.rand((B, 1), generator=g).cuda(), torch.randn((B, 46), generator=g).cuda()
+sig = torch.linspace(0.05, 30.0, B).cuda()
+eng = m.engine()
+eng.safe_denoise = False
+y = m.denoise(x, E=E, sigma=sig, layers=layers)
+torch.cuda.synchronize()
+eng.check_status()
+np.save(sys.argv[1], y.cpu().numpy())
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = {}
+    for tag, env in (("single", {}), ("coop", {"CD_ATTN_COOP": str(parts)})):
+        path = str(tmp_path / f"coop_{parts}_{tag}.npy")
+        e = dict(os.environ, **env)
+        subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests")), path], check=True, env=e, timeout=600)
+        outs[tag] = np.load(path)
+    err = rel_l2(outs["coop"], outs["single"])
+    print(f"co-operative attention ({parts} workgroups per sample) vs single workgroup: rel L2 {err:.2e}")
+    assert err < 3e-6
+
+
+@pytest.mark.parametrize("shape,batch", [((45, 16, 9), 4), ((28, 12, 21), 3), ((45, 50, 18), 2)])
+def test_attention_moment_form_equals_the_separate_closing_pass(shape, batch, monkeypatch):
+    """Level-0 attention (32 channels, > 1024 voxels): the moment form -- pass 1 also accumulates sum(softmax(q) - 1/32) and its
+    32 x 32 second moment, pass 2 derives the closing GroupNorm(1)'s mean / variance from them and the folded weights and writes
+    gn(y) + x directly -- beside the three-launch form (y written, channel sums, gn_apply), both against the oracle in float64, on grids with a ragged last tile,
+    for near-uniform softmaxes (default-init scale), peaked ones (q weights x 12) and an output projection with a large bias
+    (mean^2 >> variance: the cancellation case of E[y^2] - mean^2)."""
+    import os
+    from calodiffusion_amd import engine
+    if os.environ.get("CD_CONV_PRECISION", "f16x2") != "f16x2":
+        pytest.skip("the fused attention passes (and with them the moment form) run in the default f16x2 mode only")
+    monkeypatch.setenv("CD_ATTN_MOM_MIN", "0")  # (the plan takes this form from 4 M elements per tensor)
+    ops = engine.Ops()
+    gen = torch.Generator().manual_seed(23)
+    D, H, W = shape
+    C = 32
+    x = (torch.randn((batch, D, H, W, C), generator=gen) * 1.5 + 0.3).cuda()
+    for qscale, bias in ((1.0, 0.0), (12.0, 0.0), (1.0, 3.0)):
+        sd = {k: v.cuda().contiguous() for k, v in attn_block_weights(C, gen, qscale=qscale, bias=bias).items()}
+        y_mom = ops.linear_attention(x, sd)
+        monkeypatch.setenv("CD_NO_ATTN_MOMENTS", "1")
+        y_sep = ops.linear_attention(x, sd)
+        monkeypatch.delenv("CD_NO_ATTN_MOMENTS")
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(y_mom).all())
+        assert not torch.equal(y_mom, y_sep)  # (the two forms really are different launches)
+        # both against the oracle in float64, on the attention branch alone (the residual x is common and larger than it)
+        from oracle import torch_oracle
+        sd64 = {"a." + k: v.double().cpu() for k, v in sd.items()}
+        x64 = x.double().cpu().permute(0, 4, 1, 2, 3)
+        want = (torch_oracle.attn_residual(sd64, "a", x64, True) - x64).permute(0, 2, 3, 4, 1).numpy()
+        e_mom = rel_l2((y_mom.double().cpu() - x.double().cpu()).numpy(), want)
+        e_sep = rel_l2((y_sep.double().cpu() - x.double().cpu()).numpy(), want)
+        print(f"{shape} q x{qscale} bias {bias}: rel L2 of the branch against float64 -- moment form {e_mom:.2e}, closing pass {e_sep:.2e}")
+        assert e_mom < 2e-6, (shape, qscale, bias, e_mom, e_sep)

@@ -8,24 +8,14 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from helpers import TOL_BWD, back, ops  # noqa: F401  (ops: a fixture)
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-5
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from calodiffusion_amd.engine import Ops
-    return Ops()
 
 
 def cl(ops, a):
     return ops.to_channels_last(a.detach().cuda())
-
-
-def back(ops, y_cl):
-    return ops.to_ncdhw(y_cl).cpu().numpy()
 
 
 def _conv_case(ops, cin, cout, shape, k, stride, gen, split=None, dy_scale=1.0):
@@ -41,9 +31,9 @@ def _conv_case(ops, cin, cout, shape, k, stride, gen, split=None, dy_scale=1.0):
         dx, dw, db = ops.conv_backward(cl(ops, x0), w.detach().cuda(), cl(ops, dy), stride=stride, x1_cl=cl(ops, x1))
     else:
         dx, dw, db = ops.conv_backward(cl(ops, x), w.detach().cuda(), cl(ops, dy), stride=stride)
-    assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL, ("dx", cin, cout, k)
-    assert rel_l2(dw.cpu().numpy(), w.grad.numpy()) < TOL, ("dw", cin, cout, k)
-    assert rel_l2(db.cpu().numpy(), b.grad.numpy()) < TOL, ("db", cin, cout, k)
+    assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL_BWD, ("dx", cin, cout, k)
+    assert rel_l2(dw.cpu().numpy(), w.grad.numpy()) < TOL_BWD, ("dw", cin, cout, k)
+    assert rel_l2(db.cpu().numpy(), b.grad.numpy()) < TOL_BWD, ("db", cin, cout, k)
 
 
 def test_conv_backward(ops):
@@ -117,9 +107,9 @@ def test_conv_transpose_backward(ops):
         dy = torch.randn(y.shape, generator=gen)
         y.backward(dy)
         dx, dw, db = ops.conv_transpose_backward(cl(ops, x), w.detach().cuda(), cl(ops, dy), kz, zs, op)
-        assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL, ("dx", shp, kz, op)
-        assert rel_l2(dw.cpu().numpy(), w.grad.numpy()) < TOL, ("dw", shp, kz, op)
-        assert rel_l2(db.cpu().numpy(), b.grad.numpy()) < TOL, ("db", shp, kz, op)
+        assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL_BWD, ("dx", shp, kz, op)
+        assert rel_l2(dw.cpu().numpy(), w.grad.numpy()) < TOL_BWD, ("dw", shp, kz, op)
+        assert rel_l2(db.cpu().numpy(), b.grad.numpy()) < TOL_BWD, ("db", shp, kz, op)
 
 
 def test_group_norm_backward(ops):
@@ -138,10 +128,10 @@ def test_group_norm_backward(ops):
         y.backward(dy)
         dx, dg, db, dadd = ops.group_norm_backward(cl(ops, x), gm.detach().cuda(), bt.detach().cuda(), cl(ops, dy), G, silu=silu,
                                                    want_dadd=True)
-        assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL, ("dx", C, G)
-        assert rel_l2(dg.cpu().numpy(), gm.grad.numpy()) < TOL, ("dgamma", C, G)
-        assert rel_l2(db.cpu().numpy(), bt.grad.numpy()) < TOL, ("dbeta", C, G)
-        assert rel_l2(dadd.cpu().numpy(), add.grad.numpy()) < TOL, ("dadd", C, G)
+        assert rel_l2(back(ops, dx), x.grad.numpy()) < TOL_BWD, ("dx", C, G)
+        assert rel_l2(dg.cpu().numpy(), gm.grad.numpy()) < TOL_BWD, ("dgamma", C, G)
+        assert rel_l2(db.cpu().numpy(), bt.grad.numpy()) < TOL_BWD, ("dbeta", C, G)
+        assert rel_l2(dadd.cpu().numpy(), add.grad.numpy()) < TOL_BWD, ("dadd", C, G)
 
 
 @pytest.mark.parametrize("nblk", [None, "3", "8"])

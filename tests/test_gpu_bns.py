@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from helpers import seeded_model_cfg
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +24,7 @@ def _cfg(name):
 
 
 def _model(name):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    cfg = _cfg(name)
-    torch.manual_seed(1234)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"]), cfg
+    return seeded_model_cfg(_cfg(name))
 
 
 def _oracle(cfg, m):

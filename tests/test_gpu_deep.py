@@ -7,27 +7,9 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import seeded_unet, t
+from helpers import TOL_OP, profiled_launches, seeded_model, seeded_unet, t, unet_kwargs
 
 pytestmark = pytest.mark.gpu
-
-TOL_OP = 1e-5
-
-
-def _unet_kwargs(grid, sizes=(32, 32, 64, 32), channels=3, cond_size=9, **over):
-    kw = dict(out_dim=1, layer_sizes=list(sizes), channels=channels, cond_dim=128, resnet_block_groups=8, mid_attn=True,
-              block_attn=True, compress_Z=True, cylindrical=True, data_shape=[1, channels] + list(grid), time_embed=False,
-              cond_embed=False, cond_size=cond_size)
-    kw.update(over)
-    return kw
-
-
-def _deep_level_launches(fn):
-    """Run fn() under the per-launch profiler and return {category: launches}."""
-    from calodiffusion_amd import engine
-    engine.profile_begin()
-    fn()
-    return {k: v["launches"] for k, v in engine.profile_end().items()}
 
 
 @pytest.mark.parametrize("grid,sizes,B", [
@@ -39,7 +21,7 @@ def _deep_level_launches(fn):
 ])
 def test_deep_level_through_unet_forward_matches_oracle(grid, sizes, B):
     from oracle import torch_oracle as O
-    kw = _unet_kwargs(grid, sizes)
+    kw = unet_kwargs(grid, sizes)
     net = seeded_unet(kw, 77).cuda()
     g = torch.Generator().manual_seed(5)
     x = torch.randn([B, 3] + list(grid), generator=g)
@@ -47,7 +29,7 @@ def test_deep_level_through_unet_forward_matches_oracle(grid, sizes, B):
     spec = O.UnetSpec(layer_sizes=list(sizes), channels=3, cond_size=9, data_shape=tuple(grid))
     with torch.no_grad():
         want = O.cond_unet_forward({k: v.cpu() for k, v in net.state_dict().items()}, spec, x, cond, time)
-    launches = _deep_level_launches(lambda: net(x.cuda(), cond=cond.cuda(), time=time.cuda()))
+    launches = profiled_launches(lambda: net(x.cuda(), cond=cond.cuda(), time=time.cuda()))
     assert any(k.startswith("deep_level") for k in launches), sorted(launches)
     got = net(x.cuda(), cond=cond.cuda(), time=time.cuda())
     err = rel_l2(got.cpu().numpy(), want.numpy())
@@ -58,8 +40,7 @@ def test_deep_level_through_unet_forward_matches_oracle(grid, sizes, B):
 def test_deep_level_equals_the_per_op_kernels(monkeypatch):
     """Same model, same inputs: the one-launch level against the 13 launches it replaces (both fp32-grade, different summation
     orders); and the launch count of a denoise step."""
-    from test_gpu_parity import _model
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     cfg = m.config
     B = 5
     g = torch.Generator().manual_seed(17)
@@ -67,10 +48,10 @@ def test_deep_level_equals_the_per_op_kernels(monkeypatch):
     E, layers = torch.rand((B, 1), generator=g).cuda(), torch.randn((B, cfg["SHAPE_PAD"][2] + 1), generator=g).cuda()
     sig = torch.tensor([80.0, 5.0, 1.0, 0.3, 0.02]).cuda()
     fused = m.denoise(x, E=E, sigma=sig, layers=layers)
-    n_fused = _deep_level_launches(lambda: m.denoise(x, E=E, sigma=sig, layers=layers))
+    n_fused = profiled_launches(lambda: m.denoise(x, E=E, sigma=sig, layers=layers))
     monkeypatch.setenv("CD_NO_DEEP_LEVEL", "1")
     per_op = m.denoise(x, E=E, sigma=sig, layers=layers)
-    n_per_op = _deep_level_launches(lambda: m.denoise(x, E=E, sigma=sig, layers=layers))
+    n_per_op = profiled_launches(lambda: m.denoise(x, E=E, sigma=sig, layers=layers))
     monkeypatch.delenv("CD_NO_DEEP_LEVEL")
     err = float((fused - per_op).norm() / per_op.norm())
     print(f"deep level vs per-op kernels: rel L2 {err:.2e}; launches per denoise {sum(n_fused.values())} vs {sum(n_per_op.values())}")
@@ -87,8 +68,7 @@ def test_deep_level_equals_the_per_op_kernels(monkeypatch):
 
 def test_deep_level_flags_fp16_overflow_like_the_convs_it_replaces():
     """An out-of-range activation inside the level raises the plan's range flag (and the safe denoise falls back)."""
-    from test_gpu_parity import _model
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     cfg = m.config
     x = torch.randn([1] + list(cfg["SHAPE_PAD"][1:]), device="cuda")
     E, layers = torch.rand((1, 1), device="cuda"), torch.randn((1, cfg["SHAPE_PAD"][2] + 1), device="cuda")

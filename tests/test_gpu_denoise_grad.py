@@ -7,19 +7,10 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from helpers import seeded_model_cfg
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def _model(name, objective=None):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = dict(load_config(name))
-    if objective is not None:
-        cfg["TRAINING_OBJ"] = objective
-    torch.manual_seed(1234)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"]), cfg
 
 
 def _inputs(cfg, B, seed=11):
@@ -48,7 +39,7 @@ CASES = [("tiny", 3, None), ("tiny", 2, "noise_pred"), ("tiny", 2, "mean_pred"),
 
 @pytest.mark.parametrize("name,B,objective", CASES)
 def test_input_and_parameter_gradients_match_autograd(name, B, objective):
-    m, cfg = _model(name, objective)
+    m, cfg = seeded_model_cfg(name, {} if objective is None else {"TRAINING_OBJ": objective})
     x, E, layers, sigma, w = _inputs(cfg, B)
     om = _oracle(cfg, m)
     xo = x.clone().requires_grad_(True)
@@ -85,7 +76,7 @@ def _chain(den, x0, theta, sigmas):
 @pytest.mark.parametrize("name,B", [("tiny", 2), ("dataset2", 1)])
 def test_chained_denoise_gradients(name, B):
     """x_{i+1} = theta[0,i] x_i + theta[1,i] denoise(x_i, sigma_i): the gradients reach theta and x_0 through every call."""
-    m, cfg = _model(name)
+    m, cfg = seeded_model_cfg(name)
     x, E, layers, _, w = _inputs(cfg, B, seed=5)
     theta0 = torch.tensor([[0.9, 0.8, 0.7], [0.3, 0.5, 0.6]])
     sigmas = [torch.full((B,), s) for s in (8.0, 1.5, 0.2)]
@@ -108,7 +99,7 @@ def test_chained_denoise_gradients(name, B):
 
 def test_vjp_reproduces_training_step_gradients():
     """gy = d(hybrid l2 loss)/dD formed in torch: cd_denoise_vjp then gives cd_train_step's flat gradient."""
-    m, cfg = _model("dataset2")
+    m, cfg = seeded_model_cfg("dataset2")
     B = 2
     gen = torch.Generator().manual_seed(21)
     shape = [B] + list(cfg["SHAPE_PAD"][1:])
@@ -136,7 +127,7 @@ def test_vjp_reproduces_training_step_gradients():
 @pytest.mark.parametrize("name,B", [("dataset2", 3), ("hgcal", 2)])
 def test_input_only_mode_is_the_same_dx(name, B):
     import ctypes as C
-    m, cfg = _model(name)
+    m, cfg = seeded_model_cfg(name)
     x, E, layers, sigma, w = _inputs(cfg, B, seed=9)
     eng = m.engine()
     cond = m.cond_tensor(E.cuda(), _cuda(layers))
@@ -155,7 +146,7 @@ def test_input_only_mode_is_the_same_dx(name, B):
 
 
 def test_graph_free_calls_are_unchanged():
-    m, cfg = _model("tiny")
+    m, cfg = seeded_model_cfg("tiny")
     x, E, layers, sigma, _ = _inputs(cfg, 3, seed=3)
     xc, Ec, lc, sc = x.cuda(), E.cuda(), _cuda(layers), sigma.cuda()
     eng = m.engine()
@@ -178,7 +169,7 @@ def test_graph_free_calls_are_unchanged():
 
 def test_parameter_only_gradients_via_requires_grad_x():
     """x.requires_grad_() is the documented switch for parameter gradients alone; a frozen model gets the input-only call."""
-    m, cfg = _model("tiny")
+    m, cfg = seeded_model_cfg("tiny")
     x, E, layers, sigma, w = _inputs(cfg, 2, seed=4)
     xc, Ec, lc, sc, wc = x.cuda(), E.cuda(), _cuda(layers), sigma.cuda(), w.cuda()
     m.zero_grad()
@@ -202,7 +193,7 @@ def test_parameter_only_gradients_via_requires_grad_x():
 
 
 def test_vjp_allocates_nothing_after_the_first_call():
-    m, cfg = _model("tiny")
+    m, cfg = seeded_model_cfg("tiny")
     x, E, layers, sigma, w = _inputs(cfg, 3, seed=8)
     eng = m.engine()
     cond = m.cond_tensor(E.cuda(), _cuda(layers))

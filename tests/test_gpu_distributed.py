@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import seeded_model
+
 pytestmark = pytest.mark.gpu
 
 WORLD = 2
@@ -38,14 +40,6 @@ def _global_conditions():
     return torch.rand((B_GLOBAL, 3), generator=g), torch.randn((B_GLOBAL, 9), generator=g)
 
 
-def _model():
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = load_config("tiny")
-    torch.manual_seed(1234)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
-
-
 def _grads(m, rank):
     data, E, layers, noise, rnd = (v.cuda() for v in _inputs(rank))
     m.zero_grad()
@@ -61,7 +55,7 @@ def _rank_main(rank, port, out_dir):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=WORLD)
     from calodiffusion_amd.utils import shard_batch
-    m = _model()
+    m = seeded_model("tiny")
     loss, g = _grads(m, rank)  # _TrainStep.forward all-reduces the flat device buffer over the group
     np.save(os.path.join(out_dir, f"grad{rank}.npy"), g)
     # batch-sharded sampling: this rank's rows of the global batch and of the global Philox stream (bench.py does the same)
@@ -91,7 +85,7 @@ def test_two_ranks_train_step_and_sharded_sampling(tmp_path):
             pytest.fail("rank timed out")
         assert p.exitcode == 0, f"rank exited with {p.exitcode}"
     # single-process references, in this process
-    m = _model()
+    m = seeded_model("tiny")
     singles = [_grads(m, r)[1] for r in range(WORLD)]
     mean = sum(singles) / WORLD
     for r in range(WORLD):

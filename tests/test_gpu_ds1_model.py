@@ -2,7 +2,7 @@
 act on the flat 368-voxel shower with NNConverter's enc / dec inside the device calls (cd_plan_set_radial) -- against the
 reference's own results (tools/gen_golden_ds1_model.py) on the synthetic binning file.
 
-Bounds: TOL_OP 1e-5 per call and TOL_TRAJ 1e-4 per trajectory (test_gpu_parity.py), 2e-6 for batch independence and for two forms of
+Bounds: TOL_OP 1e-5 per call and TOL_TRAJ 1e-4 per trajectory (helpers.py), 2e-6 for batch independence and for two forms of
 one computation, 5e-6 for gradients (test_gpu_train.py).  The NN_embed gradients are held to 5e-6 per matrix; the reference's own
 float32 gradients lie up to 1.8e-6 (encs) and 3.3e-7 (decs) from a float64 restatement (fixture, ``f64.dist``), so twice that
 distance would be the tighter bound where 5e-6 were missed."""
@@ -11,35 +11,11 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import SEED, t
+from helpers import SEED, TOL_GRAD, TOL_OP, TOL_ROW, TOL_TRAJ, t
 import ds1_model_cases as K
+from ds1_model_cases import inputs as _inputs, model as _model
 
 pytestmark = pytest.mark.gpu
-
-TOL_OP, TOL_TRAJ, TOL_ROW, TOL_GRAD = 1e-5, 1e-4, 2e-6, 5e-6
-_models = {}
-
-
-def _model(objective="hybrid_weight", time_embed="log", loss_type="l2", fresh=False):
-    """The seeded model with the fixture's perturbed NN_embed matrices (one per case, shared by the tests that only read it)."""
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    key = (objective, time_embed, loss_type)
-    if fresh or key not in _models:
-        cfg = K.config(objective, time_embed, LOSS_TYPE=loss_type)
-        torch.manual_seed(SEED)
-        m = CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=loss_type)
-        g = gold("ds1_model")
-        m.NN_embed.load_state_dict({k[3:]: t(g[k]) for k in g.files if k.startswith("nn.")})
-        m.eval()
-        if fresh:
-            return m
-        _models[key] = m
-    return _models[key]
-
-
-def _inputs(*names):
-    g = gold("ds1_model")
-    return [t(g[n]).cuda() for n in names]
 
 
 @pytest.mark.parametrize("objective", K.OBJECTIVES)

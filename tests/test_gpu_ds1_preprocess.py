@@ -222,7 +222,7 @@ def test_generate_ends_in_physical_showers():
     """generate(geometry=NN_embed) on the Dataset-1 model: physical (N, V) showers, bitwise ReverseNormCaloChall applied by hand
     to the normalised-space output of the same noise.  (The 4-step samples of this untrained model reach |x| ~ 120: float32
     exp overflows on them, and reverse_logit saturates at 1 where the reference's exp / (1 + exp) would be NaN.)"""
-    from test_gpu_ds1_model import _inputs, _model
+    from ds1_model_cases import inputs as _inputs, model as _model
     import ds1_model_cases as K
     from calodiffusion_amd.postprocess import ReverseNormCaloChall
     m = _model()
@@ -248,7 +248,7 @@ def test_one_training_step_from_raw_data():
     """compute_loss on PreprocessDS1(raw) equals compute_loss on the reference-pre-processed tensors of the fixture (same noise,
     same sigma draw) within the relative 1e-5 tests/test_gpu_train.py holds the loss to; backward reaches every parameter, the
     geometry embedding's matrices included."""
-    from test_gpu_ds1_model import _model
+    from ds1_model_cases import model as _model
     from calodiffusion_amd.preprocess import PreprocessDS1
     tag = "ph.flat.layer"
     g = gold("ds1_preprocess")

@@ -58,89 +58,11 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from grad_cases import check_parameter_gradients, cuda, inputs, oracle_of, train_steps_vs_oracle
+from helpers import seeded_model_cfg
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def _model(name, **overrides):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = dict(load_config(name))
-    cfg.update(overrides)
-    torch.manual_seed(1234)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"]), cfg
-
-
-def _cuda(t):
-    return None if t is None else t.cuda()
-
-
-def _inputs(cfg, B, seed):
-    """One batch on the CPU: shower, noise (the VJP's weights w), conditions, and one sigma per sample, log-uniform over
-    [0.05, 30]."""
-    gen = torch.Generator().manual_seed(seed)
-    shape = [B] + list(cfg["SHAPE_PAD"][1:])
-    x = torch.randn(shape, generator=gen)
-    w = torch.randn(shape, generator=gen)
-    E = torch.rand((B, 3 if cfg.get("HGCAL") else 1), generator=gen)
-    layers = torch.randn((B, 1 + cfg["SHAPE_FINAL"][2]), generator=gen) if "layer" in cfg["SHOWERMAP"] else None
-    sigma = torch.exp(np.log(0.05) + np.log(30.0 / 0.05) * torch.rand((B,), generator=gen))
-    tsteps = torch.randint(0, cfg["NSTEPS"], (B,), generator=gen)
-    return x, w, E, layers, sigma, tsteps
-
-
-def _oracle(cfg, m):
-    sd = {k[6:]: v.detach().cpu().clone().requires_grad_(True) for k, v in m.state_dict().items()}
-    return O.OracleModel(cfg, sd)
-
-
-def _check_parameter_gradients(tag, m, want):
-    """Every parameter tensor of the model against `want` {name: gradient}: the worst tensor and all of them together."""
-    worst = []
-    for kname, p in m.model.named_parameters():
-        assert p.grad is not None, kname
-        worst.append((rel_l2(p.grad.cpu().numpy(), want[kname].numpy()), kname))
-    worst.sort(reverse=True)
-    got_all = np.concatenate([p.grad.cpu().numpy().ravel() for _, p in m.model.named_parameters()])
-    want_all = np.concatenate([want[k].numpy().ravel() for k, _ in m.model.named_parameters()])
-    err_all = rel_l2(got_all, want_all)
-    print(f"[{tag}] worst tensor {worst[0][0]:.3e} ({worst[0][1]}), all gradients together {err_all:.3e}")
-    assert worst[0][0] < 1e-4, worst[:8]
-    assert err_all < 5e-6
-    return got_all
-
-
-def _train_steps_vs_oracle(tag, m, cfg, B, seed, steps=1):
-    """`steps` identical training steps, each against autograd through the oracle's loss (test_parameter_gradients_match_autograd's
-    assertions); returns [(loss, all gradients)] per step.  The noise level is the loss's own draw from the inputs: exp(1.2 rnd -
-    1.2) with rnd placed so that sigma is log-uniform over [0.05, 30] (log schedule), the table's entry of `time` (cosine)."""
-    data, noise, E, layers, sigma, tsteps = _inputs(cfg, B, seed)
-    rnd = (sigma.log() + 1.2) / 1.2
-    om = _oracle(cfg, m)
-    t0 = time.perf_counter()
-    want_loss = om.hybrid_l2_loss(data, E, noise, layers, rnd_normal=rnd, time=tsteps, n_steps=cfg["NSTEPS"])
-    want_loss.backward()
-    want_loss, want = float(want_loss.detach()), {k: v.grad for k, v in om.sd.items()}
-    t_oracle = time.perf_counter() - t0
-    sig = m.loss_function.draw_sigma(data, time=tsteps, rnd_normal=rnd).cuda()  # (on the CPU: the oracle's bits)
-    dev = [data.cuda(), E.cuda(), noise.cuda(), _cuda(layers)]
-    out = []
-    for rep in range(steps):
-        m.zero_grad()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        loss = m.loss_function.loss_function(m, dev[0], dev[1], sigma=sig, noise=dev[2], layers=dev[3])
-        assert loss.requires_grad and loss.dim() == 0
-        loss.backward()
-        torch.cuda.synchronize()
-        t_dev = time.perf_counter() - t0
-        got_loss = float(loss.detach())
-        err_loss = abs(got_loss - want_loss) / abs(want_loss)
-        print(f"[{tag}] step {rep}: loss rel {err_loss:.3e}, device {t_dev:.3f} s, oracle {t_oracle:.2f} s")
-        assert err_loss <= 1e-5
-        out.append((got_loss, torch.from_numpy(_check_parameter_gradients(f"{tag} step {rep}", m, want))))
-    return out
 
 
 def _vjp_vs_oracle(tag, m, cfg, B, seed, params=True):
@@ -148,8 +70,8 @@ def _vjp_vs_oracle(tag, m, cfg, B, seed, params=True):
     OracleModel.denoise (test_input_and_parameter_gradients_match_autograd's assertions); the input gradient also per sample.
     `params=False`: the input gradient alone.  Returns the device tensors (x, sigma, cond, w, dx) for a caller that goes on with
     the engine."""
-    x, w, E, layers, sigma, _ = _inputs(cfg, B, seed)
-    om = _oracle(cfg, m)
+    x, w, E, layers, sigma, _ = inputs(cfg, B, seed)
+    om = oracle_of(cfg, m)
     xo = x.clone().requires_grad_(True)
     t0 = time.perf_counter()
     (om.denoise(xo, E, sigma, layers) * w).sum().backward()
@@ -159,7 +81,7 @@ def _vjp_vs_oracle(tag, m, cfg, B, seed, params=True):
     xg, sg, wg = x.cuda().requires_grad_(True), sigma.cuda(), w.cuda()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = m.denoise(xg, E=E.cuda(), sigma=sg, layers=_cuda(layers))
+    out = m.denoise(xg, E=E.cuda(), sigma=sg, layers=cuda(layers))
     assert out.requires_grad
     (out * wg).sum().backward()
     torch.cuda.synchronize()
@@ -172,23 +94,23 @@ def _vjp_vs_oracle(tag, m, cfg, B, seed, params=True):
     assert err_x < 2e-5
     assert max(rows) < 2e-5, sorted(zip(rows, range(B)), reverse=True)[:4]  # (a whole-batch norm averages one bad sample away)
     if params:
-        _check_parameter_gradients(tag, m, {k: v.grad for k, v in om.sd.items()})
-    return xg.detach(), sg, m.cond_tensor(E.cuda(), _cuda(layers)), wg, xg.grad
+        check_parameter_gradients(tag, m, {k: v.grad for k, v in om.sd.items()})
+    return xg.detach(), sg, m.cond_tensor(E.cuda(), cuda(layers)), wg, xg.grad
 
 
 def test_dataset2_training_step_batch97():
     """Level 0 of Dataset-2 with every split of the backward path in its batch-limited branch (the table's B = 97 lines).  The first
     step carries the warm-up and the autotune; the two after it run the same kernels and must agree bitwise."""
-    m, cfg = _model("dataset2")
-    steps = _train_steps_vs_oracle("dataset2 B=97 train", m, cfg, 97, seed=97, steps=3)
+    m, cfg = seeded_model_cfg("dataset2")
+    steps = train_steps_vs_oracle("dataset2 B=97 train", m, cfg, 97, seed=97, steps=3)
     assert steps[1][0] == steps[2][0], (steps[1][0], steps[2][0])
     assert torch.equal(steps[1][1], steps[2][1])
 
 
 def test_dataset3_training_step_batch9():
     """The cosine schedule (sigma from the table's entry of `time`) and the head's loop (1424 -> 1024 blocks)."""
-    m, cfg = _model("dataset3")
-    _train_steps_vs_oracle("dataset3 B=9 train", m, cfg, 9, seed=9)
+    m, cfg = seeded_model_cfg("dataset3")
+    train_steps_vs_oracle("dataset3 B=9 train", m, cfg, 9, seed=9)
 
 
 def test_dataset3_denoise_vjp_input_gradient_batch9():
@@ -202,7 +124,7 @@ def test_dataset3_denoise_vjp_input_gradient_batch9():
     ups.2.0.block1.proj.conv.weight: 364 500 fp32 terms per weight) where the device is 1.9e-6 away from that fp64 evaluation, so
     the 5e-6 bar lies below what this reference resolves (device against the fp32 oracle: 5.9e-6).  Its input gradient is good to
     6.5e-7 (device against fp64: 3.1e-7)."""
-    m, cfg = _model("dataset3")
+    m, cfg = seeded_model_cfg("dataset3")
     x, sigma, cond, w, dx = _vjp_vs_oracle("dataset3 B=9 vjp", m, cfg, 9, seed=19, params=False)
     dx_only, none = m.engine().denoise_vjp(x, sigma, cond, w, param_grads=False)
     assert none is None
@@ -212,7 +134,7 @@ def test_dataset3_denoise_vjp_input_gradient_batch9():
 def test_hgcal_denoise_vjp_batch90():
     """cd_denoise_vjp with three E columns and the phi input channel at B*vox = 635 040: dx and every parameter gradient; then the
     input-only mode (the GroupNorm queue's `discard` path, no weight-gradient queue) gives bitwise the same dx."""
-    m, cfg = _model("hgcal")
+    m, cfg = seeded_model_cfg("hgcal")
     x, sigma, cond, w, dx = _vjp_vs_oracle("hgcal B=90 vjp", m, cfg, 90, seed=90)
     eng = m.engine()
     dx_full, flat = eng.denoise_vjp(x, sigma, cond, w, param_grads=True)
@@ -225,9 +147,9 @@ def test_hgcal_denoise_vjp_batch90():
 def test_dataset2_vjp_reproduces_training_step_batch97():
     """gy = d(hybrid l2 loss)/dD formed in torch: cd_denoise_vjp then gives cd_train_step's flat gradient
     (test_vjp_reproduces_training_step_gradients at the batch of test_dataset2_training_step_batch97)."""
-    m, cfg = _model("dataset2")
+    m, cfg = seeded_model_cfg("dataset2")
     B = 97
-    data, noise, E, layers, sigma, _ = (_cuda(t) for t in _inputs(cfg, B, seed=21))
+    data, noise, E, layers, sigma, _ = (cuda(t) for t in inputs(cfg, B, seed=21))
     eng = m.engine()
     cond = m.cond_tensor(E, layers)
     _, flat_train = eng.train_step(data, noise, sigma, cond, "l2")
@@ -248,8 +170,8 @@ def test_dataset2_vjp_reproduces_training_step_batch97():
 def test_tiny_training_step_batch300():
     """Many small samples: 300 workgroups (one per sample) in gn_bwd_small_kernel, the attention's per-sample dctx weight gradient,
     embed_bwd and linear_wgrad; the 27-tap weight gradient in 2 chunks against a cap of 4."""
-    m, cfg = _model("tiny")
-    _train_steps_vs_oracle("tiny B=300 train", m, cfg, 300, seed=300)
+    m, cfg = seeded_model_cfg("tiny")
+    train_steps_vs_oracle("tiny B=300 train", m, cfg, 300, seed=300)
 
 
 # Deeper than the shipped four-entry nets: nets whose steps fill GnParamJobs (64 jobs) resp. WgradReduceQueue (80 jobs) and flush them
@@ -272,8 +194,8 @@ def test_deeper_nets_flush_the_queues_mid_step(depth):
         five   56 GroupNorm jobs, 74 weight-gradient reductions: neither queue fills (the next depth up from the shipped nets)
         six    68 GroupNorm jobs: flushed at 64, 4 at the end;  78 weight-gradient reductions: not yet 80, hence the third net
         seven  80 GroupNorm jobs: flushed at 64, 16 at the end;  94 weight-gradient reductions: flushed at 80, 14 at the end"""
-    m, cfg = _model("tiny", **DEEP[depth])
+    m, cfg = seeded_model_cfg("tiny", DEEP[depth])
     assert O.spec_from_config(cfg).layer_sizes == DEEP[depth]["LAYER_SIZE_UNET"]
     assert tuple(O.spec_from_config(cfg).data_shape) == tuple(DEEP[depth]["SHAPE_FINAL"][2:]) == tuple(m.engine().grid)
-    _train_steps_vs_oracle(f"tiny/{depth} B=2 train", m, cfg, 2, seed=6)
+    train_steps_vs_oracle(f"tiny/{depth} B=2 train", m, cfg, 2, seed=6)
     _vjp_vs_oracle(f"tiny/{depth} B=2 vjp", m, cfg, 2, seed=7)

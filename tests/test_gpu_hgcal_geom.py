@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t
+from helpers import per_layer_worst, t
 from hgcal_geom_cases import apply64, bound, sparse64, sparse_bound, sparse_matrix, worst_ratio
 
 pytestmark = pytest.mark.gpu
@@ -190,7 +190,6 @@ def test_reverse_norm_hgcal_with_the_device_converter():
     """postprocess.ReverseNormHGCal(embed=True, NN_embed=<device converter>) against the reference's ReverseNormHGCal around its
     own Decoder, at the bounds of the existing HGCal reverse-norm test (1e-5 overall, 3e-5 per (shower, layer) row)."""
     from calodiffusion_amd import postprocess
-    from test_oracle_golden import per_layer_worst
     g, conv, _ = _fixture()
     data, gen = postprocess.ReverseNorm(g["rn.vox"], g["rn.e"], hgcal=True, emax=1000., emin=1., max_deposit=2, logE=True,
                                         layerE=g["rn.layerE"], showerMap="layer-logit-norm", dataset_num=111, embed=True, NN_embed=conv)

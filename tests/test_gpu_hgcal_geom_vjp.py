@@ -4,8 +4,7 @@ geometries: "g" (tests/golden/hgcal_geom.npz), "m" and "t" (tools/gen_golden_hgc
 lane-per-column gather crosses a workgroup).  The reference's autograd is the fixture's for "t" (``Embeder`` / ``Decoder`` of the
 reference under ``backward()``) and a float64 restatement of the same einsum through ``mat * mask`` for all three.
 
-Bounds: TOL_OP 1e-5 per call, TOL_GRAD 5e-6 for gradients, TOL_ROW 2e-6 for batch independence (test_gpu_parity.py,
-test_gpu_train.py)."""
+Bounds: TOL_OP 1e-5 per call, TOL_GRAD 5e-6 for gradients, TOL_ROW 2e-6 for batch independence (helpers.py)."""
 import ctypes as C
 
 import numpy as np
@@ -13,12 +12,11 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t
+from helpers import TOL_GRAD, TOL_OP, TOL_ROW, t
 import hgcal_model_cases as K
 
 pytestmark = pytest.mark.gpu
 
-TOL_OP, TOL_ROW, TOL_GRAD = 1e-5, 2e-6, 5e-6
 TAGS = ("g", "m", "t")
 
 

@@ -3,7 +3,7 @@ denoise, samplers, loss and gradients act on the cell-space shower (B, 1, 8, 61)
 calls (cd_plan_set_geom) and whose two maps train through ``mat * mask`` -- against the reference's own results
 (tools/gen_golden_hgcal_model.py) on the synthetic geometry "m".
 
-Bounds: TOL_OP 1e-5 per call and TOL_TRAJ 1e-4 per trajectory (test_gpu_parity.py), 2e-6 for batch independence and for two forms of
+Bounds: TOL_OP 1e-5 per call and TOL_TRAJ 1e-4 per trajectory (helpers.py), 2e-6 for batch independence and for two forms of
 one computation, 5e-6 for gradients (test_gpu_train.py).  The two ``mat`` gradients are held to the larger of 5e-6 and twice the
 fixture's ``f64.dist``, the distance of the reference's own float32 gradients from a float64 restatement: 1.9e-6 (embeder.mat)
 and 1.6e-6 (decoder.mat) as generated, so the bound is 5e-6 for both."""
@@ -12,12 +12,11 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import SEED, t
+from helpers import SEED, TOL_GRAD, TOL_OP, TOL_ROW, TOL_TRAJ, t
 import hgcal_model_cases as K
 
 pytestmark = pytest.mark.gpu
 
-TOL_OP, TOL_TRAJ, TOL_ROW, TOL_GRAD = 1e-5, 1e-4, 2e-6, 5e-6
 BINS = [-1, 1] + list(K.GRID)
 _models = {}
 

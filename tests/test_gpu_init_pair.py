@@ -7,13 +7,12 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from helpers import TOL_ORACLE, TOL_REASSOC, seeded_model_cfg
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 SWITCH = "CD_NO_INIT_PAIR"
-TOL_REASSOC = 2e-6   # the project's per-conv bound (tests/test_gpu_side_conv.py)
-TOL_ORACLE = 1e-5    # test_denoise_matches_reference's bound
 TOL_STATS = 1e-6     # test_chunking_of_the_skip_half_changes_no_output_bit's bound, of the summed terms
 _SIGMAS = [0.3, 2.5, 0.05, 11.0, 80.0, 1.0, 0.02, 5.0]
 
@@ -165,8 +164,7 @@ def _batch(cfg, n, seed):
 
 def _fixture(name, n):
     """One model, one seeded batch of n samples (smaller batches are prefixes) and the CPU oracle's denoise of the first three."""
-    from test_gpu_denoise_grad import _model
-    m, cfg = _model(name)
+    m, cfg = seeded_model_cfg(name)
     x, E, layers, sigma = _batch(cfg, n, 29)
     om = O.OracleModel(cfg, {k: v.detach().cpu() for k, v in m.state_dict().items()})
     with torch.no_grad():

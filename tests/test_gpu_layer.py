@@ -5,13 +5,10 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t, verify_checksums
+from helpers import TOL_OP, TOL_TRAJ, t, verify_checksums
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-TOL_OP = 1e-5
-TOL_TRAJ = 1e-4
 
 
 def _model(**extra):

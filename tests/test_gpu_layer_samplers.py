@@ -10,11 +10,11 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
+from helpers import TOL_TRAJ
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-TOL_TRAJ = 1e-4  # test_gpu_layer.py
 DIM = 46  # dataset2: SHAPE_FINAL[2] + 1
 
 

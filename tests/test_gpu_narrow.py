@@ -12,13 +12,13 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import SEED, t
+from helpers import SEED, TOL_GRAD, TOL_OP, TOL_ROW, TOL_TRAJ, t
 from oracle import torch_oracle as O
 import narrow_cases as N
 
 pytestmark = pytest.mark.gpu
 
-TOL_OP, TOL_TRAJ, TOL_ROW, TOL_LOSS, TOL_GRAD_WORST, TOL_GRAD_ALL, TOL_DX = 1e-5, 1e-4, 2e-6, 1e-5, 1e-4, 5e-6, 2e-5
+TOL_LOSS, TOL_GRAD_WORST, TOL_GRAD_ALL, TOL_DX = 1e-5, 1e-4, TOL_GRAD, 2e-5
 _models = {}
 
 

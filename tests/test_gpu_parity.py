@@ -11,26 +11,11 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import d1grid_kwargs, seeded_unet, t, verify_checksums
+from conv_cases import conv_case
+from helpers import ops  # noqa: F401  (a fixture)
+from helpers import TOL_OP, TOL_REASSOC, TOL_ROW, TOL_TRAJ, back, cl, d1grid_kwargs, seeded_model, seeded_unet, t, verify_checksums
 
 pytestmark = pytest.mark.gpu
-
-TOL_OP = 1e-5
-TOL_TRAJ = 1e-4
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from calodiffusion_amd.engine import Ops
-    return Ops()
-
-
-def cl(ops, a):
-    return ops.to_channels_last(t(a).cuda())
-
-
-def back(ops, y_cl):
-    return ops.to_ncdhw(y_cl).cpu().numpy()
 
 
 def test_library_is_the_hip_one_and_device_is_gfx950():
@@ -98,19 +83,6 @@ def test_halo_tiled_kernels_match_too(ops, monkeypatch):
         assert err < TOL_OP, (tag, err)
 
 
-def _halo_tiled_errors():
-    """(child process of the test below) 3x3x3 convs, one of them over a concatenated input, and a golden down-sampling conv."""
-    from calodiffusion_amd.engine import Ops
-    ops = Ops()
-    gen = torch.Generator().manual_seed(17)
-    errs = {"c32": _conv_case(ops, gen, 2, 32, 0, 32, (9, 16, 9)), "c32+32": _conv_case(ops, gen, 2, 32, 32, 64, (6, 4, 2))}
-    g = gold("primitives_conv")
-    y = back(ops, ops.cyl_conv(cl(ops, g["down_d2.x"]), t(g["down_d2.w"]).cuda(), t(g["down_d2.b"]).cuda(),
-                               stride=(2 if int(g["down_d2.cz"]) else 1, 2, 2)))
-    errs["down_d2"] = rel_l2(y, g["down_d2.y"])
-    return errs
-
-
 @pytest.mark.parametrize("mode", ["f16x2", "bf16x3", "f32"])
 def test_halo_tiled_kernels_in_every_precision(mode):
     """With the flat-range, z-slide and whole-sample kernels switched off every conv runs on a halo-tiled kernel, in the arithmetic
@@ -122,7 +94,7 @@ def test_halo_tiled_kernels_in_every_precision(mode):
     here = os.path.dirname(os.path.abspath(__file__))
     env = dict(os.environ, CD_CONV_PRECISION=mode, CD_NO_FLAT="1", CD_NO_ZSLIDE="1", CD_NO_CONV_SMALL="1", CD_NO_AUTOTUNE="1")
     code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r);"
-            "from test_gpu_parity import _halo_tiled_errors; print(json.dumps(_halo_tiled_errors()))" % (os.path.dirname(here), here))
+            "from conv_cases import halo_tiled_errors; print(json.dumps(halo_tiled_errors()))" % (os.path.dirname(here), here))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     errs = json.loads(out.stdout.strip().splitlines()[-1])
@@ -147,34 +119,20 @@ def test_concat_conv_equals_conv_of_concat(ops):
     assert rel_l2(y, want) < TOL_OP
 
 
-def _conv_case(ops, gen, B, c0, c1, cout, shape, nb=3):
-    from oracle import torch_oracle as O
-    cin = c0 + c1
-    x = torch.randn((B, cin) + shape, generator=gen)
-    w, bias = torch.randn((cout, cin, 3, 3, 3), generator=gen) * 0.05, torch.randn(cout, generator=gen)
-    nb = B if nb is None else min(B, nb)
-    want = O.cyl_conv3d(x[:nb], w, bias, padding=(1, 1, 1)).numpy()
-    if c1:
-        y = ops.cyl_conv(cl(ops, x[:, :c0].contiguous().numpy()), w.cuda(), bias.cuda(), x1_cl=cl(ops, x[:, c0:].contiguous().numpy()))
-    else:
-        y = ops.cyl_conv(cl(ops, x.numpy()), w.cuda(), bias.cuda())
-    return rel_l2(back(ops, y)[:nb], want)
-
-
 def test_full_resolution_conv_kernel(ops):
     """The z-slide f16x2 kernel (kernels_conv_zs.hip) takes 3x3x3 convs on grids whose planes hold 128..160 voxels: Dataset-2's
     level 0 (16x9) in every channel configuration the U-Net uses there, ragged chunk ends, one and many samples."""
     gen = torch.Generator().manual_seed(11)
     for B, c0, c1, cout, shape in ((1, 32, 0, 32, (45, 16, 9)), (3, 32, 0, 32, (45, 16, 9)), (2, 32, 32, 32, (10, 16, 9)),
                                    (2, 32, 0, 64, (7, 16, 8)), (5, 64, 0, 32, (3, 16, 9)), (64, 32, 0, 32, (45, 16, 9))):
-        err = _conv_case(ops, gen, B, c0, c1, cout, shape, nb=None)  # every sample, the 64 of the headline shape included
-        assert err < 2e-6, (B, c0, c1, cout, shape, err)
+        err = conv_case(ops, gen, B, c0, c1, cout, shape, nb=None)  # every sample, the 64 of the headline shape included
+        assert err < TOL_REASSOC, (B, c0, c1, cout, shape, err)
     # wider planes run as phi strips with halo rows and a 5-plane ring: Dataset-3 (50x18 -> 10 strips of 5 rows), HGCal
     # (12x21 -> 3 strips of 4 rows), a two-strip grid with a concatenated input
     for B, c0, c1, cout, shape in ((1, 32, 0, 32, (6, 50, 18)), (2, 32, 0, 32, (9, 12, 21)), (1, 32, 0, 32, (45, 50, 18)),
                                    (2, 32, 32, 32, (5, 10, 18))):
-        err = _conv_case(ops, gen, B, c0, c1, cout, shape)
-        assert err < 2e-6, (B, c0, c1, cout, shape, err)
+        err = conv_case(ops, gen, B, c0, c1, cout, shape)
+        assert err < TOL_REASSOC, (B, c0, c1, cout, shape, err)
 
 
 def test_wide_plane_images_of_the_full_resolution_conv(ops):
@@ -185,8 +143,8 @@ def test_wide_plane_images_of_the_full_resolution_conv(ops):
     for B, c0, c1, cout, shape in ((3, 32, 0, 32, (23, 25, 9)), (2, 32, 32, 32, (7, 25, 9)), (2, 32, 0, 64, (5, 14, 13)),
                                    (2, 32, 0, 32, (11, 12, 17)), (3, 32, 0, 32, (28, 12, 21)), (2, 32, 32, 64, (6, 20, 18)),
                                    (2, 64, 0, 32, (4, 16, 16)), (1, 32, 0, 32, (3, 8, 32))):
-        err = _conv_case(ops, gen, B, c0, c1, cout, shape, nb=None)
-        assert err < 2e-6, (B, c0, c1, cout, shape, err)
+        err = conv_case(ops, gen, B, c0, c1, cout, shape, nb=None)
+        assert err < TOL_REASSOC, (B, c0, c1, cout, shape, err)
 
 
 def test_strip_conv_many_samples_every_sample_checked(ops):
@@ -195,14 +153,14 @@ def test_strip_conv_many_samples_every_sample_checked(ops):
     a few random samples of a large batch only.  Every sample of a 16-shower Dataset-3 batch is compared."""
     gen = torch.Generator().manual_seed(12)
     for B, c0, c1, cout, shape in ((16, 32, 0, 32, (45, 50, 18)), (24, 32, 32, 32, (12, 16, 9))):
-        err = _conv_case(ops, gen, B, c0, c1, cout, shape, nb=B)
-        assert err < 2e-6, (B, c0, c1, cout, shape, err)
+        err = conv_case(ops, gen, B, c0, c1, cout, shape, nb=B)
+        assert err < TOL_REASSOC, (B, c0, c1, cout, shape, err)
 
 
 def test_batched_denoise_equals_single_samples_dataset3():
     """Showers are independent: a Dataset-3 batch of 12 equals its showers denoised one at a time (catches races that only
     show with many workgroups in flight)."""
-    m = _model("dataset3")
+    m = seeded_model("dataset3")
     gen = torch.Generator().manual_seed(5)
     B = 12
     x = torch.randn([B] + list(m.config["SHAPE_PAD"][1:]), generator=gen).cuda()
@@ -212,7 +170,7 @@ def test_batched_denoise_equals_single_samples_dataset3():
     assert torch.isfinite(y).all()
     for i in (0, 5, 11):
         yi = m.denoise(x[i:i + 1], E=E[i:i + 1], sigma=sig[i:i + 1], layers=None)
-        assert rel_l2(y[i:i + 1].cpu().numpy(), yi.cpu().numpy()) < 2e-6, i
+        assert rel_l2(y[i:i + 1].cpu().numpy(), yi.cpu().numpy()) < TOL_ROW, i
 
 
 def test_whole_sample_conv_kernel(ops):
@@ -222,8 +180,8 @@ def test_whole_sample_conv_kernel(ops):
     for B, c0, c1, cout, shape in ((2, 32, 0, 32, (12, 4, 2)), (3, 64, 0, 64, (12, 4, 2)), (2, 32, 32, 32, (12, 4, 2)),
                                    (1, 128, 0, 64, (5, 5, 5)), (2, 96, 0, 32, (3, 1, 4)), (2, 32, 0, 32, (1, 2, 3)),
                                    (2, 64, 64, 96, (4, 4, 8))):
-        err = _conv_case(ops, gen, B, c0, c1, cout, shape)
-        assert err < 2e-6, (B, c0, c1, cout, shape, err)
+        err = conv_case(ops, gen, B, c0, c1, cout, shape)
+        assert err < TOL_REASSOC, (B, c0, c1, cout, shape, err)
 
 
 def test_conv_precision_modes_agree(ops, monkeypatch):
@@ -235,9 +193,9 @@ def test_conv_precision_modes_agree(ops, monkeypatch):
         # the mode is latched at the first conv launch of a process: run the comparison in a child interpreter
         import subprocess, sys, json
         code = ("import sys, json, torch; sys.path.insert(0, %r); sys.path.insert(0, %r);"
-                "from test_gpu_parity import _conv_case; from calodiffusion_amd.engine import Ops;"
+                "from conv_cases import conv_case; from calodiffusion_amd.engine import Ops;"
                 "g = torch.Generator().manual_seed(13);"
-                "print(json.dumps([_conv_case(Ops(), g, 2, 32, 0, 32, (9, 16, 9)), _conv_case(Ops(), g, 2, 64, 0, 64, (6, 4, 2))]))"
+                "print(json.dumps([conv_case(Ops(), g, 2, 32, 0, 32, (9, 16, 9)), conv_case(Ops(), g, 2, 64, 0, 64, (6, 4, 2))]))"
                 % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))))
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stderr[-2000:]
@@ -250,7 +208,7 @@ def test_fp16_range_flag_and_fallback_of_plain_denoise():
     poisons the raw cd_denoise output with inf/NaN AND raises the plan's sticky flag; denoise() as the samplers' callback
     (cd_denoise_safe) recovers instead: the call is re-run with the full-range kernels and equals the bf16x3 result."""
     from calodiffusion_amd import engine
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     cfg = m.config
     B = 2
     shape = [B] + list(cfg["SHAPE_PAD"][1:])
@@ -298,7 +256,7 @@ def test_trained_scale_residual_stream_needs_no_fallback():
     itself -- shortcut sums, attention inputs, the f16x2-staged conv inputs -- carries the magnitude): denoise must still
     equal the fp32 oracle to 1e-5 without leaving the fp16 range."""
     from oracle import torch_oracle as O
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     with torch.no_grad():
         sd = m.model.state_dict()
         sd["init_conv.conv.weight"].mul_(3.0e3)
@@ -369,19 +327,10 @@ def test_linear_attention_blocks(ops):
         assert err < TOL_OP, (tag, err)
 
 
-def _model(name):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = load_config(name)
-    torch.manual_seed(1234)
-    m = CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
-    return m
-
-
 @pytest.mark.parametrize("name", ["tiny", "dataset2", "hgcal", "dataset3"])
 def test_denoise_matches_reference(name):
     g = gold(f"model_{name}")
-    m = _model(name)
+    m = seeded_model(name)
     verify_checksums({k[6:]: v.cpu() for k, v in m.state_dict().items()}, g)
     x, E = t(g["x"]).cuda(), t(g["E"]).cuda()
     layers = t(g["layers"]).cuda() if "layers" in g.files else None
@@ -402,7 +351,7 @@ def test_unet_forward_d1_grid():
 
 def test_ddim_trajectories_dataset2():
     g = gold("ddim_dataset2")
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     for n in (2, 10, 50, 400):
         out = m.sample(E, layers, num_steps=n, start=start)
@@ -436,7 +385,7 @@ def test_generate_returns_physical_showers():
     """Diffusion.generate (diffusion.py:118-197): sampling loop over a loader + inverse pre-processing on the device; the
     output has the reference's shapes (SHAPE_ORIG, (N, 1)) and equals ReverseNorm applied to the normalised-space showers."""
     from calodiffusion_amd.postprocess import ReverseNorm
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     cfg = m.config
     gen = torch.Generator().manual_seed(3)
     loader = [(torch.rand((3, 1), generator=gen), torch.randn((3, 46), generator=gen), None) for _ in range(2)]
@@ -457,7 +406,7 @@ def test_edm_euler_sampler_dataset2():
     reference's own Euler trajectories."""
     from calodiffusion_amd import sample
     g = gold("euler_dataset2")
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     eul = sample.Euler(m.config)
     for n in (5, 18):
@@ -473,7 +422,7 @@ def test_edm_euler_sampler_dataset2():
 
 
 def test_graph_replay_equals_eager_bitwise():
-    m = _model("tiny")
+    m = seeded_model("tiny")
     g = gold("ddpm_tiny")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     from calodiffusion_amd import sample
@@ -492,7 +441,7 @@ def test_stochastic_sampler_graph_replay_equals_eager_bitwise():
     step graph serves a stochastic trajectory too: same (seed, offset) => graph and eager runs are bitwise identical, and a
     second trajectory (new offset) re-uses the graph and differs."""
     from calodiffusion_amd import sample
-    m = _model("tiny")
+    m = seeded_model("tiny")
     g = gold("ddpm_tiny")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     outs = {}
@@ -511,7 +460,7 @@ def test_stochastic_sampler_graph_replay_equals_eager_bitwise():
 
 def test_ddpm_tiny_with_reference_noise_stream():
     g = gold("ddpm_tiny")
-    m = _model("tiny")
+    m = seeded_model("tiny")
     assert type(m.sampler_algorithm).__name__ == "DDPM"
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     torch.manual_seed(int(g["noise_seed"]))
@@ -529,13 +478,13 @@ def test_ddpm_tiny_with_reference_noise_stream():
 
 def test_loss_values():
     g = gold("loss_dataset2")
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     loss = m.compute_loss(t(g["data"]).cuda(), t(g["E"]).cuda(), noise=t(g["noise"]).cuda(), layers=t(g["layers"]).cuda(),
                           rnd_normal=t(g["rnd_normal"]).cuda())
     assert loss.dim() == 0
     assert abs(float(loss) - float(g["loss"])) <= 1e-5 * abs(float(g["loss"]))
     g = gold("loss_dataset3")
-    m = _model("dataset3")
+    m = seeded_model("dataset3")
     sig = m.loss_function.draw_sigma(t(g["data"]).cuda(), time=torch.from_numpy(g["time"]).cuda())
     loss = m.loss_function.loss_function(m, t(g["data"]).cuda(), t(g["E"]).cuda(), sigma=sig, noise=t(g["noise"]).cuda(), layers=None)
     assert abs(float(loss) - float(g["loss"])) <= 1e-5 * abs(float(g["loss"]))
@@ -556,7 +505,7 @@ def test_philox_stream_properties():
 
 def test_full_size_properties_dataset2_batch64():
     """BASELINE's headline size (B = 64): size-independent properties instead of a 64-sample oracle run."""
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     gen = torch.Generator().manual_seed(11)
     x = torch.randn((64, 1, 45, 16, 9), generator=gen).cuda()
     E = torch.rand((64, 1), generator=gen).cuda()
@@ -566,7 +515,7 @@ def test_full_size_properties_dataset2_batch64():
     assert torch.isfinite(y).all()
     # (1) batch independence: no op mixes showers
     y8 = m.denoise(x[5:13].contiguous(), E=E[5:13].contiguous(), sigma=sig[5:13].contiguous(), layers=layers[5:13].contiguous())
-    assert rel_l2(y8.cpu().numpy(), y[5:13].cpu().numpy()) < 2e-6
+    assert rel_l2(y8.cpu().numpy(), y[5:13].cpu().numpy()) < TOL_ROW
     # (2) phi periodicity: Dataset-2 has no phi input channel, so rolling the input along phi by a multiple of 4
     #     (two stride-2 levels) rolls the output
     yr = m.denoise(torch.roll(x, 4, dims=3).contiguous(), E=E, sigma=sig, layers=layers)
@@ -584,7 +533,7 @@ def test_full_size_properties_dataset2_batch64():
 
 
 def test_weight_update_is_picked_up():
-    m = _model("tiny")
+    m = seeded_model("tiny")
     g = gold("model_tiny")
     x, E, layers = t(g["x"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     sig = torch.full((4,), 1.0, device="cuda")

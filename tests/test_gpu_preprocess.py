@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from test_oracle_golden import per_layer_worst
+from helpers import per_layer_worst
 
 pytestmark = pytest.mark.gpu
 

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
+from helpers import per_layer_worst
 from preprocess_hgcal_cases import BATCH, CASES, MAPS, SCALE, bins, config, converter, embedded
-from test_oracle_golden import per_layer_worst
 
 pytestmark = pytest.mark.gpu
 

@@ -2,30 +2,16 @@
 the other samplers as step programs (cd_sampler_run), sinusoidal embeddings, the fp16-range fallback of the sampler loops,
 reference-generated gradients, Dataset-3 / HGCal trajectories and full-size properties, batch-sharded Philox streams, and the
 training loop with FusedAdam."""
-import copy
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import seeded_unet, t, verify_checksums
+from helpers import TOL_OP, TOL_TRAJ, seeded_model, seeded_unet, t
 from sampler_cases import CASES, options, replay_noise
-from test_oracle_golden import check_sampler_case
+from sampler_oracles import check_sampler_case
 
 pytestmark = pytest.mark.gpu
-
-TOL_OP = 1e-5
-TOL_TRAJ = 1e-4
-
-
-def _model(name, over=None, seed=1234):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = copy.deepcopy(load_config(name))
-    cfg.update(over or {})
-    torch.manual_seed(seed)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
 
 
 # ---------------------------------------------------------------------------------------------- samplers
@@ -39,7 +25,7 @@ def test_sampler_programs_match_reference_trajectories(tag):
     opts = options(g, tag)
     if opts:
         cfg_over["SAMPLER_OPTIONS"] = opts
-    m = _model("tiny", cfg_over)
+    m = seeded_model("tiny", cfg_over)
     smp = m.sampler_algorithm
     assert type(smp).__name__ == name
     n = int(g[f"{tag}.n"])
@@ -93,7 +79,7 @@ def test_sampler_program_graph_replay_equals_eager_and_philox():
     Philox positions; a second trajectory re-uses the graph, draws new noise and differs."""
     outs = {}
     for use_graph in (True, False):
-        m = _model("tiny", {"SAMPLER": "Heun", "NOISY_SAMPLE": True, "SAMPLER_OPTIONS": {"HIP_GRAPH": use_graph}})
+        m = seeded_model("tiny", {"SAMPLER": "Heun", "NOISY_SAMPLE": True, "SAMPLER_OPTIONS": {"HIP_GRAPH": use_graph}})
         gen = torch.Generator().manual_seed(5)
         E, layers = torch.rand((4, 3), generator=gen).cuda(), torch.randn((4, 9), generator=gen).cuda()
         m.noise_offset = 0
@@ -110,10 +96,10 @@ def test_samplers_on_dataset2_and_by_name():
     from calodiffusion_amd.utils import load_attr
     g = gold("samplers_dataset2")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
-    m = _model("dataset2", {"SAMPLER": "Heun"})
+    m = seeded_model("dataset2", {"SAMPLER": "Heun"})
     _, xs, x0s = m.sample(E, layers, num_steps=4, start=start, debug=True)
     assert rel_l2(xs[3].cpu().numpy(), g["heun_xs3"]) < TOL_TRAJ and rel_l2(x0s[3].cpu().numpy(), g["heun_x0s3"]) < TOL_TRAJ
-    m = _model("dataset2", {"SAMPLER": "LMS"})
+    m = seeded_model("dataset2", {"SAMPLER": "LMS"})
     assert rel_l2(m.sample(E, layers, num_steps=6, start=start), g["lms_6"]) < TOL_TRAJ
     for name in ("DDim", "DDPM", "Euler", "Heun", "DPM2", "LMS", "Restart", "DPM", "DPMPP2S", "DPMPP2M", "Consistency", "DPMAdaptive",
                  "DPMPPSDE", "DPMPP2MSDE", "DPMPP3MSDE"):
@@ -140,7 +126,7 @@ def test_unet_sinusoidal_embeddings():
         y = net(t(g[f"{tag}.x"]).cuda(), cond=t(g[f"{tag}.cond"]).cuda(), time=t(g[f"{tag}.time"]).cuda())
         assert rel_l2(y.cpu().numpy(), g[f"{tag}.y"]) < TOL_OP, tag
     with pytest.raises(KeyError):
-        _model("tiny", {"TIME_EMBED": "sin"})
+        seeded_model("tiny", {"TIME_EMBED": "sin"})
     with pytest.raises(ValueError, match="cd_unet_forward only"):
         net.engine().denoise(torch.zeros(1, 1, 8, 8, 8, device="cuda"), torch.ones(1, device="cuda"), torch.zeros(1, 1, device="cuda"))
 
@@ -149,7 +135,7 @@ def test_unet_sinusoidal_embeddings():
 def test_sampler_recovers_from_fp16_range_overflow():
     """An activation beyond the fp16 range trips the f16x2 convolutions' flag; the sampler loops then re-run the trajectory
     with the exact bf16x3 convolutions instead of losing the batch: finite, and equal to a run in bf16x3 mode from the start."""
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     gen = torch.Generator().manual_seed(8)
     start = torch.randn((2, 1, 45, 16, 9), generator=gen).cuda()
     E, layers = torch.rand((2, 1), generator=gen).cuda(), torch.randn((2, 46), generator=gen).cuda()
@@ -182,7 +168,7 @@ def test_gradients_match_the_reference(name):
     grads3; the HGCal fixture carries its own inputs)."""
     g = gold(f"grads_{name}")
     gl = g if name == "hgcal" else gold(f"loss_{name}")
-    m = _model(name)
+    m = seeded_model(name)
     data, E, noise = t(gl["data"]).cuda(), t(gl["E"]).cuda(), t(gl["noise"]).cuda()
     layers = t(gl["layers"]).cuda() if "layers" in gl.files else None
     if name in ("dataset2", "hgcal"):
@@ -209,7 +195,7 @@ def test_gradients_match_the_reference(name):
 def test_parameter_gradients_match_autograd_hgcal():
     """HGCal ([32,32,64,96], kZ = 4 up-convs, 4-channel init conv): every parameter gradient against autograd through the oracle."""
     from oracle import torch_oracle as O
-    m = _model("hgcal")
+    m = seeded_model("hgcal")
     cfg = m.config
     gen = torch.Generator().manual_seed(79)
     shape = [1] + list(cfg["SHAPE_PAD"][1:])
@@ -232,13 +218,13 @@ def test_parameter_gradients_match_autograd_hgcal():
 # ---------------------------------------------------------------------------------------------- trajectories, full sizes
 def test_dataset3_ddim_and_hgcal_ddpm_trajectories():
     g = gold("ddim_dataset3")
-    m = _model("dataset3")
+    m = seeded_model("dataset3")
     start, E = t(g["start"]).cuda(), t(g["E"]).cuda()
     for n in (10, 50):
         err = rel_l2(m.sample(E, None, num_steps=n, start=start), g[f"ddim_{n}"])
         assert err < TOL_TRAJ, (n, err)
     g = gold("ddpm_hgcal")
-    m = _model("hgcal")
+    m = seeded_model("hgcal")
     assert type(m.sampler_algorithm).__name__ == "DDPM"
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     torch.manual_seed(int(g["noise_seed"]))
@@ -254,7 +240,7 @@ def test_full_size_properties(name, B):
     """BASELINE's batch sizes for Dataset-3 (32) and HGCal (16 per GPU): batch independence, determinism, and the oracle on
     two of the showers."""
     from oracle import torch_oracle as O
-    m = _model(name)
+    m = seeded_model(name)
     cfg = m.config
     gen = torch.Generator().manual_seed(13)
     x = torch.randn([B] + list(cfg["SHAPE_PAD"][1:]), generator=gen).cuda()
@@ -278,7 +264,7 @@ def test_ddpm_50_error_against_the_reference_is_recorded():
     """The stochastic tiny-config trajectory with the reference's seeded noise stream: observed error printed, held to the
     north_star's 1e-4."""
     g = gold("ddpm_tiny")
-    m = _model("tiny")
+    m = seeded_model("tiny")
     start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
     torch.manual_seed(int(g["noise_seed"]))
     m.sampler_algorithm.step_noise = torch.stack([torch.randn(start.shape) for _ in range(50)]).cuda()
@@ -296,7 +282,7 @@ def test_batch_shards_draw_their_rows_of_one_global_stream():
     gen = torch.Generator().manual_seed(21)
     B = 6
     E, layers = torch.rand((B, 3), generator=gen).cuda(), torch.randn((B, 9), generator=gen).cuda()
-    m = _model("tiny")
+    m = seeded_model("tiny")
     m.noise_offset = 0
     full_start = m.noise_generation([B, 1, 8, 8, 8]).clone()
     m.noise_offset = 0
@@ -306,7 +292,7 @@ def test_batch_shards_draw_their_rows_of_one_global_stream():
         parts = [[], []]
         for rank in range(world):
             sl = shard_batch(B, world, rank)
-            ms = _model("tiny")
+            ms = seeded_model("tiny")
             ms.set_noise_shard(sl.start, B)
             ms.noise_offset = 0
             st = ms.noise_generation([sl.stop - sl.start, 1, 8, 8, 8])
@@ -334,7 +320,7 @@ def test_training_loop_with_fused_adam_updates_the_plan():
     sig = torch.full((4,), 1.0, device="cuda")
     runs = {}
     for kind in ("fused", "torch"):
-        m = _model("tiny")
+        m = seeded_model("tiny")
         opt = (FusedAdam if kind == "fused" else torch.optim.Adam)(m.parameters(), lr=2e-5)
         y0 = m.denoise(data, E=E, sigma=sig, layers=layers).clone()
         losses = []
@@ -355,7 +341,7 @@ def test_training_loop_with_fused_adam_updates_the_plan():
 
 
 def test_generate_refuses_to_skip_the_inverse_preprocessing():
-    m = _model("tiny")
+    m = seeded_model("tiny")
     gen = torch.Generator().manual_seed(3)
     loader = [(torch.rand((2, 3), generator=gen), torch.randn((2, 9), generator=gen), None)]
     with pytest.raises(ValueError, match="inverse pre-processing"):
@@ -372,7 +358,7 @@ def test_all_weights_in_one_call_equals_one_tensor_at_a_time():
     transposed / 1x1 / init convs, raw tensors)."""
     import ctypes as C
     from calodiffusion_amd import engine as E_
-    m = _model("dataset2")
+    m = seeded_model("dataset2")
     gen = torch.Generator().manual_seed(11)
     x = torch.randn((2, 1, 45, 16, 9), generator=gen).cuda()
     En, layers = torch.rand((2, 1), generator=gen).cuda(), torch.randn((2, 46), generator=gen).cuda()

@@ -1,12 +1,11 @@
-"""GPU (MI355X): round-3 changes -- the sampler loop's embeddings computed a chunk of steps ahead, the DDIM update inside the head
-kernel, the loss types, DPMAdaptive and the HGCal reverse normalisation -- against the kernels they replace and the reference's
-goldens."""
+"""GPU (MI355X): round-3 changes -- the block close by the shortcut conv, the loss types and the HGCal reverse normalisation --
+against the kernels they replace and the reference's goldens."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t
+from helpers import per_layer_worst, seeded_model, t
 
 pytestmark = pytest.mark.gpu
 
@@ -17,8 +16,7 @@ def test_block_close_by_the_shortcut_conv_equals_the_elementwise_pass(name, B, m
     epilogue, partial last tiles included: 6480 = 50 x 128 + 80 voxels) against the separate shortcut conv + gn_apply launches
     (CD_NO_PW_CLOSE=1), with fewer launches."""
     from calodiffusion_amd import engine
-    from test_gpu_parity import _model
-    m = _model(name)
+    m = seeded_model(name)
     cfg = m.config
     g = torch.Generator().manual_seed(31)
     x = torch.randn([B] + list(cfg["SHAPE_PAD"][1:]), generator=g).cuda()
@@ -45,33 +43,12 @@ def test_block_close_by_the_shortcut_conv_equals_the_elementwise_pass(name, B, m
     assert gn(n_fused) < gn(n_plain)
 
 
-def test_ddim_with_chunked_embeddings_matches_the_reference_over_chunk_boundaries():
-    """The sampler loop computes its embeddings 16 steps ahead in one launch and updates x inside the head kernel: 50 steps cross
-    three chunk boundaries and end on a partial chunk; against the reference's DDIM trajectory (golden) in graph and eager mode,
-    with trajectories recorded (debug) and without."""
-    from test_gpu_parity import _model
-    g = gold("ddim_dataset2")
-    start, E, layers = t(g["start"]).cuda(), t(g["E"]).cuda(), t(g["layers"]).cuda()
-    outs = []
-    for use_graph in (True, False):
-        m = _model("dataset2")
-        assert type(m.sampler_algorithm).__name__ == "DDim"
-        m.sampler_algorithm.use_graph = use_graph
-        x = m.sample(E, layers, num_steps=50, start=start)
-        assert rel_l2(x, g["ddim_50"]) < 1e-4
-        outs.append(x)
-    assert np.array_equal(outs[0], outs[1])
-    xd, xs, x0s = m.sample(E, layers, num_steps=50, start=start, debug=True)
-    assert np.array_equal(xd, outs[0]) and len(xs) == 50 and len(x0s) == 50
-
-
 @pytest.mark.parametrize("lt", ["l1", "mse", "huber", "l2"])
 def test_training_step_loss_types_match_the_reference(lt):
     """cd_train_step with every LOSS_TYPE of Loss._loss: loss and gradients against .grad of the reference's own
     compute_loss(...).backward() (tests/golden/losstypes_tiny.npz); the no-grad evaluation (cd_loss_hybrid) gives the same value."""
-    from test_gpu_round2 import _model
     g = gold("losstypes_tiny")
-    m = _model("tiny", {"LOSS_TYPE": lt})
+    m = seeded_model("tiny", {"LOSS_TYPE": lt})
     assert m.loss_function.loss_type == lt
     data, E, noise, layers = (t(g[k]).cuda() for k in ("data", "E", "noise", "layers"))
     rnd = t(g["rnd_normal"]).cuda()
@@ -96,22 +73,6 @@ def test_training_step_loss_types_match_the_reference(lt):
     print(f"[{lt}] loss {float(loss):.6f} (reference {want:.6f}); worst whole-tensor gradient error {worst:.2e}")
 
 
-def test_dpm_adaptive_on_the_device_equals_the_same_loop_on_the_oracle():
-    """DPMAdaptive (host loop, one cd_denoise_safe call per model evaluation): the device against the CPU oracle running the
-    identical loop -- the reference's own class raises for every input (see the class docstring), so the oracle is the pin."""
-    from test_host import dpm_adaptive_on_oracle
-    from test_gpu_round2 import _model
-    opts = {"ORDER": 3, "H_INIT": 0.25, "R_TOL": 0.5}  # (large steps: ~30 of them, each three oracle evaluations on the CPU)
-    (start, E, layers), want, calls, steps = dpm_adaptive_on_oracle(opts, 8)
-    m = _model("tiny", {"SAMPLER": "DPMAdaptive", "SAMPLER_OPTIONS": opts})
-    assert type(m.sampler_algorithm).__name__ == "DPMAdaptive"
-    got = m.sample(E.cuda(), layers.cuda(), num_steps=8, start=start.cuda())
-    smp = m.sampler_algorithm
-    err = rel_l2(got, want.numpy())
-    print(f"DPMAdaptive: {smp.steps_taken} steps, {smp.denoise_calls} denoise calls; device vs oracle loop rel L2 {err:.2e}")
-    assert (smp.steps_taken, smp.denoise_calls) == (steps, calls) and err < 1e-4
-
-
 def test_reverse_norm_hgcal_on_device():
     """postprocess.ReverseNormHGCal = two device stages around the caller's geometry decode, against the reference's own
     utils.ReverseNormHGCal (fixture: oracle/gen_golden.py renorm_hgcal, stand-in decoder)."""
@@ -129,7 +90,6 @@ def test_reverse_norm_hgcal_on_device():
     # 1e-5 like the CaloChallenge maps, over the whole array AND per (shower, layer) row -- round 3 had widened this to 3e-5:
     # the layer energies were transformed with utils.py's alpha (1e-6) instead of HGCal_utils.py's (1e-8), which the
     # energy-weighted norm only just showed
-    from test_oracle_golden import per_layer_worst
     e_all, e_row = rel_l2(data, g["layer.data"]), per_layer_worst(data, g["layer.data"])
     print(f"ReverseNormHGCal 111 layer mode: rel L2 {e_all:.2e}, worst (shower, layer) row {e_row:.2e}")
     assert e_all < 1e-5 and e_row < 3e-5

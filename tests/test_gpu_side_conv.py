@@ -7,13 +7,12 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from helpers import TOL_ORACLE, TOL_REASSOC, seeded_model_cfg
 from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 SWITCH = "CD_NO_DEEP_SIDE_CONV"
-TOL_REASSOC = 2e-6   # the project's per-conv bound for a changed fp32 summation order (relative L2)
-TOL_ORACLE = 1e-5    # test_denoise_matches_reference's bound
 BMAX = 66
 _SIGMAS = [0.3, 2.5, 0.05, 11.0, 80.0, 1.0, 0.02, 5.0]
 
@@ -22,8 +21,7 @@ _SIGMAS = [0.3, 2.5, 0.05, 11.0, 80.0, 1.0, 0.02, 5.0]
 def ds2():
     """One Dataset-2 model, one seeded batch of BMAX samples (smaller batches are prefixes) and the CPU oracle's denoise of the first
     three samples (the oracle treats samples independently)."""
-    from test_gpu_denoise_grad import _model
-    m, cfg = _model("dataset2")
+    m, cfg = seeded_model_cfg("dataset2")
     gen = torch.Generator().manual_seed(29)
     x = torch.randn([BMAX] + list(cfg["SHAPE_PAD"][1:]), generator=gen)
     E = torch.rand((BMAX, 1), generator=gen)

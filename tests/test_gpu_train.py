@@ -5,31 +5,15 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import t
-from oracle import torch_oracle as O
+from grad_cases import oracle_grads, steps_across_batch_sizes
+from helpers import seeded_model, seeded_model_cfg, t
 
 pytestmark = pytest.mark.gpu
 
 
-def _model(name):
-    from calodiffusion_amd.calodiffusion import CaloDiffusion
-    from calodiffusion_amd.configs import load_config
-    cfg = load_config(name)
-    torch.manual_seed(1234)
-    return CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"]), cfg
-
-
-def _oracle_grads(cfg, sd, data, E, noise, layers, rnd, tsteps):
-    sd = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    om = O.OracleModel(cfg, sd)
-    loss = om.hybrid_l2_loss(data, E, noise, layers, rnd_normal=rnd, time=tsteps)
-    loss.backward()
-    return float(loss), {k: v.grad for k, v in om.sd.items()}
-
-
 @pytest.mark.parametrize("name,B", [("tiny", 3), ("dataset2", 2), ("dataset3", 1)])
 def test_parameter_gradients_match_autograd(name, B):
-    m, cfg = _model(name)
+    m, cfg = seeded_model_cfg(name)
     gen = torch.Generator().manual_seed(77)
     shape = [B] + list(cfg["SHAPE_PAD"][1:])
     data = torch.randn(shape, generator=gen)
@@ -39,7 +23,7 @@ def test_parameter_gradients_match_autograd(name, B):
     rnd = torch.randn((B,), generator=gen)
     tsteps = torch.randint(0, cfg["NSTEPS"], (B,), generator=gen)  # Dataset-3 (cosine schedule) draws sigma from the table
     sd_cpu = {k[6:]: v.detach().cpu() for k, v in m.state_dict().items()}
-    want_loss, want = _oracle_grads(cfg, sd_cpu, data, E, noise, layers, rnd, tsteps)
+    want_loss, want = oracle_grads(cfg, sd_cpu, data, E, noise, layers, rnd, tsteps)
 
     # Two identical steps (the weight gradients' slot reductions queued and run as one launch, WgradReduceQueue): both against the
     # reference's gradients, and against each other.
@@ -72,7 +56,7 @@ def test_parameter_gradients_match_autograd(name, B):
 def test_training_loop_protocol_one_adam_step():
     """zero_grad -> compute_loss -> backward -> Adam.step, as TrainDiffusion.training_loop does (train_diffusion.py:52-63);
     the updated weights are picked up by the next forward."""
-    m, cfg = _model("tiny")
+    m, cfg = seeded_model_cfg("tiny")
     opt = torch.optim.Adam(m.parameters(), lr=2e-5)  # small steps: the loss must go down monotonically on a fixed batch
     gen = torch.Generator().manual_seed(5)
     data = torch.randn((4, 1, 8, 8, 8), generator=gen).cuda()
@@ -126,7 +110,7 @@ def test_queued_weight_gradient_reductions_follow_the_batch_size():
     """The weight gradients' partials wait for their single reduction launch in blocks of the step's own workspace, which the
     engine sizes per batch size: batch 2, 2, 5, 5, 2 on one model -- every step, the first at a new batch size included, queues
     the same way -- every step against autograd through the oracle."""
-    _steps_across_batch_sizes()
+    steps_across_batch_sizes()
 
 
 def test_immediate_weight_gradient_reductions_follow_the_batch_size():
@@ -136,32 +120,9 @@ def test_immediate_weight_gradient_reductions_follow_the_batch_size():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = "import sys; sys.path[:0] = [%r, %r]; from test_gpu_train import _steps_across_batch_sizes; _steps_across_batch_sizes()"
+    code = "import sys; sys.path[:0] = [%r, %r]; from grad_cases import steps_across_batch_sizes; steps_across_batch_sizes()"
     subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests"))], check=True,
                    env=dict(os.environ, CD_NO_WGRAD_QUEUE="1"), timeout=900)
-
-
-def _steps_across_batch_sizes():
-    m, cfg = _model("tiny")
-    sd_cpu = {k[6:]: v.detach().cpu() for k, v in m.state_dict().items()}
-    for step, B in enumerate((2, 2, 5, 5, 2)):
-        gen = torch.Generator().manual_seed(100 + step)
-        shape = [B] + list(cfg["SHAPE_PAD"][1:])
-        data, noise = torch.randn(shape, generator=gen), torch.randn(shape, generator=gen)
-        E = torch.rand((B, 3 if cfg.get("HGCAL") else 1), generator=gen)
-        layers = torch.randn((B, 1 + cfg["SHAPE_FINAL"][2]), generator=gen) if "layer" in cfg["SHOWERMAP"] else None
-        rnd = torch.randn((B,), generator=gen)
-        tsteps = torch.randint(0, cfg["NSTEPS"], (B,), generator=gen)
-        want_loss, want = _oracle_grads(cfg, sd_cpu, data, E, noise, layers, rnd, tsteps)
-        m.zero_grad()
-        sigma = m.loss_function.draw_sigma(data.cuda(), time=tsteps.cuda(), rnd_normal=rnd.cuda())
-        loss = m.loss_function.loss_function(m, data.cuda(), E.cuda(), sigma=sigma, noise=noise.cuda(),
-                                             layers=None if layers is None else layers.cuda())
-        assert abs(float(loss) - want_loss) <= 1e-5 * abs(want_loss), (step, B)
-        loss.backward()
-        got_all = np.concatenate([p.grad.cpu().numpy().ravel() for _, p in m.model.named_parameters()])
-        want_all = np.concatenate([want[k].numpy().ravel() for k, _ in m.model.named_parameters()])
-        assert rel_l2(got_all, want_all) < 5e-6, (step, B, rel_l2(got_all, want_all))
 
 
 def _dataset2_step(m, B, seed):
@@ -178,11 +139,11 @@ def test_a_training_step_allocates_no_device_memory_of_its_own():
     words -- in the caller's workspace (include/calodiff.h): on a fresh Dataset-2 engine, steps at batch 1, 2, 1 take no device
     memory besides what torch allocates (workspaces, gradient buffers).  Kernels and the autotune are warmed on a throwaway engine
     first (code objects and the tuner's timing runs are the process's, not the step's)."""
-    warm, _ = _model("dataset2")
+    warm, _ = seeded_model_cfg("dataset2")
     for B in (1, 2):
         warm.engine().train_step(*_dataset2_step(warm, B, B))
     torch.cuda.synchronize()
-    m, _ = _model("dataset2")
+    m, _ = seeded_model_cfg("dataset2")
     eng = m.engine()
     torch.cuda.synchronize()
     free0, reserved0 = torch.cuda.mem_get_info()[0], torch.cuda.memory_reserved()
@@ -201,9 +162,9 @@ def test_the_first_training_step_equals_the_steady_state():
     identical inputs give bitwise-equal loss and gradients.  The autotune (per process, keyed by shape) is warmed on a throwaway
     engine first, so that both steps run the same kernels."""
     B = 2
-    warm, _ = _model("dataset2")
+    warm, _ = seeded_model_cfg("dataset2")
     warm.engine().train_step(*_dataset2_step(warm, B, 21))
-    m, _ = _model("dataset2")
+    m, _ = seeded_model_cfg("dataset2")
     eng = m.engine()
     args = _dataset2_step(m, B, 21)
     steps = []
@@ -212,3 +173,43 @@ def test_the_first_training_step_equals_the_steady_state():
         steps.append((float(loss), torch.cat([g.flatten() for g in eng.param_grads(flat)]).cpu()))
     assert steps[0][0] == steps[1][0], (steps[0][0], steps[1][0])
     assert torch.equal(steps[0][1], steps[1][1])
+
+
+@pytest.mark.parametrize("obj", ["noise_pred", "mean_pred"])
+def test_objectives_match_the_reference(obj):
+    """TRAINING_OBJ noise_pred / mean_pred: cd_denoise objectives 1 / 2 (calodiffusion.py:161-165) at three noise levels, a 6-step
+    DDIM trajectory on that denoiser, and the loss classes of models/loss.py:181-210 -- value (cd_loss_hybrid) and every
+    gradient (cd_train_step) for LOSS_TYPE l2 and huber -- against the reference (tests/golden/objectives_tiny.npz)."""
+    g = gold("objectives_tiny")
+    data, E, noise, layers = (t(g[k]).cuda() for k in ("data", "E", "noise", "layers"))
+    rnd = t(g["rnd_normal"]).cuda()
+    m = seeded_model("tiny", {"TRAINING_OBJ": obj, "LOSS_TYPE": "l2", "SAMPLER": "DDim"})  # (the tiny config's own sampler is DDPM)
+    assert type(m.loss_function).__name__ == obj and type(m.sampler_algorithm).__name__ == "DDim"
+    with torch.no_grad():
+        for i, sg in enumerate(g["sigmas"]):
+            xin = data * float(np.sqrt(1.0 + float(sg) ** 2))
+            got = m.denoise(xin, E=E, sigma=torch.full((4,), float(sg)).cuda(), layers=layers)
+            err = rel_l2(got.cpu().numpy(), g[f"{obj}.denoise_{i}"])
+            assert err < 1e-5, (obj, i, err)
+        x = m.sample(E, layers, num_steps=6, start=data)
+        assert rel_l2(x, g[f"{obj}.ddim_6"]) < 1e-4
+    for lt in ("l2", "huber"):
+        m = seeded_model("tiny", {"TRAINING_OBJ": obj, "LOSS_TYPE": lt})
+        m.zero_grad()
+        loss = m.compute_loss(data, E, noise=noise, layers=layers, rnd_normal=rnd)
+        loss.backward()
+        want = float(g[f"{obj}.{lt}.loss"])
+        assert abs(float(loss) - want) <= 1e-5 * abs(want), (obj, lt, float(loss), want)
+        with torch.no_grad():
+            assert abs(float(m.compute_loss(data, E, noise=noise, layers=layers, rnd_normal=rnd)) - want) <= 1e-5 * abs(want)
+        grads = dict(m.model.named_parameters())
+        pre, worst = f"{obj}.{lt}.grad.", 0.0
+        for k in g.files:
+            if k.startswith(pre):
+                err = rel_l2(grads[k[len(pre):]].grad.cpu().numpy(), g[k])
+                worst = max(worst, err)
+                assert err < 1e-4, (k, err)
+        for k, (s1, s2) in zip(g[f"{obj}.{lt}.ck_keys"], g[f"{obj}.{lt}.ck_vals"]):
+            gr = grads[str(k)].grad.double()
+            assert abs(float((gr * gr).sum()) - s2) <= 2e-4 * max(s2, 1e-30), (obj, lt, k)
+        print(f"[{obj}/{lt}] loss {float(loss):.6f} (reference {want:.6f}); worst whole-tensor gradient error {worst:.2e}")

@@ -9,6 +9,8 @@ import torch
 
 from conftest import ROOT, gold, rel_l2
 from helpers import seeded_unet, t, verify_checksums
+from sampler_oracles import (SDE_CASES, OracleBackedModel, check_sampler_case, dpm_adaptive_on_oracle, interpret_program,
+                             sde_oracle_run)
 from oracle import torch_oracle as O
 from calodiffusion_amd import engine, schedule, utils
 from calodiffusion_amd.calodiffusion import CaloDiffusion
@@ -153,40 +155,12 @@ def test_layerdiffusion_surface_and_checkpoints(tmp_path):
         assert not m.layer_loss  # the state is restored on failure
 
 
-def _interpret_program(prog, denoise, start, noise):
-    """Host-side interpreter of a sampler step program (the semantics of cd_sampler_run, include/calodiff.h) in torch on the
-    CPU, with the oracle as the denoiser: checks the program BUILDERS without a GPU."""
-    from calodiffusion_amd.engine import SOP_DENOISE, SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD
-    bufs = [torch.zeros_like(start) for _ in range(prog.n_bufs)]
-    bufs[0] = start * np.float32(prog.start_scale)
-    n_steps = prog.coefs.shape[0]
-    xs, x0s = [None] * n_steps, [None] * n_steps
-    it = iter(noise)
-    for i in range(n_steps):
-        ops = prog.ops if prog.op_begin is None else prog.ops[prog.op_begin[i]:prog.op_begin[i + 1]]
-        row = torch.from_numpy(prog.coefs[i])
-        for kind, dst, src, col in ops:
-            if kind in (SOP_LINCOMB, SOP_LINDIV):
-                acc = row[col] * bufs[src[0]]
-                for k in range(1, len(src)):
-                    acc = acc + row[col + k] * bufs[src[k]]
-                bufs[dst] = acc / row[col + len(src)] if kind == SOP_LINDIV else acc
-            elif kind == SOP_DENOISE:
-                bufs[dst] = denoise(bufs[src[0]], row[col])
-            elif kind == SOP_RANDN:
-                bufs[dst] = next(it)
-            elif kind == SOP_RECORD:
-                (xs if dst == 0 else x0s)[i] = bufs[src[0]]
-    return bufs[0], xs, x0s
-
-
 def test_sampler_programs_reproduce_the_reference_trajectories():
     """Every step program of calodiffusion_amd.sample (EDM Euler+churn / Heun / DPM2 / LMS / Restart, DPM / DPM++2S / DPM++2M,
     Consistency), interpreted on the CPU with the oracle as denoiser, against trajectories of the reference's own sampler
     classes (tests/golden/samplers_tiny.npz)."""
     import copy
     from sampler_cases import CASES, options, replay_noise
-    from test_oracle_golden import check_sampler_case
     g = gold("samplers_tiny")
     base = load_config("tiny")
     om = O.OracleModel(base, seeded_unet("tiny").state_dict())
@@ -214,7 +188,7 @@ def test_sampler_programs_reproduce_the_reference_trajectories():
             assert prog.n_randn == len(noise), (tag, prog.n_randn, len(noise))
         den = lambda x, s: om.denoise(x, E, s.float().expand(rows), layers)  # noqa: E731
         with torch.no_grad():
-            x, xs, x0s = _interpret_program(prog, den, start, noise if prog.n_randn else [])
+            x, xs, x0s = interpret_program(prog, den, start, noise if prog.n_randn else [])
         if name == "Restart":
             xs, x0s = None, [x0s[i] for i in smp._main_steps]
         if name in ("LMS", "DPM", "DPMPP2S", "DPMPP2M"):
@@ -278,40 +252,13 @@ def test_reference_module_paths_resolve_to_this_package():
     assert A is not None
 
 
-class _OracleBackedModel:
-    """What a sampler sees of CaloDiffusion -- denoise, nsteps, loss_function -- with the CPU oracle as the denoiser."""
-
-    def __init__(self, cfg):
-        self.om = O.OracleModel(cfg, seeded_unet("tiny").state_dict())
-        self.host = CaloDiffusion(cfg, n_steps=cfg["NSTEPS"], loss_type=cfg["LOSS_TYPE"])
-        self.loss_function, self.nsteps = self.host.loss_function, self.host.nsteps
-
-    def denoise(self, x, E=None, sigma=None, layers=None):
-        with torch.no_grad():
-            return self.om.denoise(x, E, sigma.reshape(-1), layers)
-
-
-def dpm_adaptive_on_oracle(opts, n, rows=3, seed=41):
-    """(inputs, final x, denoise calls, steps) of calodiffusion_amd.sample.DPMAdaptive run on the CPU oracle."""
-    import copy
-    from calodiffusion_amd import sample
-    cfg = copy.deepcopy(load_config("tiny"))
-    cfg["SAMPLER_OPTIONS"] = opts
-    gen = torch.Generator().manual_seed(seed)
-    start = torch.randn((rows, 1, 8, 8, 8), generator=gen)
-    E, layers = torch.rand((rows, 3), generator=gen), torch.randn((rows, 9), generator=gen)
-    smp = sample.DPMAdaptive(cfg)
-    x, _, _ = smp(_OracleBackedModel(cfg), start, E, layers, n)
-    return (start, E, layers), x, smp.denoise_calls, smp.steps_taken
-
-
 def test_dpm_adaptive_host_loop():
     """The host-decision sampler on the oracle: step count = the t-range over H_INIT (the reference's controller never changes
     the step), 3 / 2 model evaluations per step at order 3 / 2, a halved step lands within the error estimate's scale of the
     full one, and a rejected step raises instead of looping forever."""
     import math
     _, x3, calls3, steps3 = dpm_adaptive_on_oracle({"ORDER": 3}, 8)
-    m = _OracleBackedModel(load_config("tiny"))
+    m = OracleBackedModel(load_config("tiny"))
     from calodiffusion_amd import sample
     sig = sample.DPMAdaptive(load_config("tiny")).setup_sigmas(m, 8)
     span = float(torch.log(sig[0] / sig[-1]))
@@ -324,22 +271,6 @@ def test_dpm_adaptive_host_loop():
         dpm_adaptive_on_oracle({"ORDER": 2, "H_INIT": 3.0, "R_TOL": 1e-6, "A_TOL": 1e-8}, 8)
     with pytest.raises(ValueError):
         dpm_adaptive_on_oracle({"ORDER": 4}, 8)
-
-
-SDE_CASES = [("DPMPPSDE", {}), ("DPMPPSDE", {"ETA": 1.0, "S_NOISE": 1.1}), ("DPMPPSDE", {"ETA": 0.6, "R": 0.4}),
-             ("DPMPP2MSDE", {}), ("DPMPP2MSDE", {"ETA": 1.0}), ("DPMPP2MSDE", {"ETA": 0.7, "SOLVER": "midpoint", "S_NOISE": 0.9}),
-             ("DPMPP3MSDE", {}), ("DPMPP3MSDE", {"ETA": 1.0}), ("DPMPP3MSDE", {"ETA": 0.5, "S_NOISE": 1.2})]
-
-
-def sde_oracle_run(name, opts, den, start, sig, noise):
-    """One SDE case on the CPU restatement (oracle/samplers_oracle.py) with the given unit normals."""
-    from oracle import samplers_oracle as SO
-    eta, s_noise = opts.get("ETA", 0.0), opts.get("S_NOISE", 1.0)
-    if name == "DPMPPSDE":
-        return SO.dpmpp_sde(den, start, sig, iter(noise), eta, s_noise, opts.get("R", 0.5))
-    if name == "DPMPP2MSDE":
-        return SO.dpmpp_2m_sde(den, start, sig, iter(noise), eta, s_noise, opts.get("SOLVER", "heun"))
-    return SO.dpmpp_3m_sde(den, start, sig, iter(noise), eta, s_noise)
 
 
 @pytest.mark.parametrize("name,opts", SDE_CASES)
@@ -372,12 +303,12 @@ def test_sde_sampler_programs_equal_the_restated_loops(name, opts):
     noise = [torch.randn(start.shape, generator=gen) for _ in range(prog.n_randn)]
     den = lambda x, s: om.denoise(x, E, torch.as_tensor(s).float().expand(rows), layers)  # noqa: E731
     with torch.no_grad():
-        got, _, _ = _interpret_program(prog, den, start, noise)
+        got, _, _ = interpret_program(prog, den, start, noise)
         want = sde_oracle_run(name, opts, den, start, sig, noise)
     err = rel_l2(got.numpy(), want.numpy())
     assert err < 2e-5, (name, opts, err)
     if opts.get("ETA"):
         # the noise matters: another set of normals moves the end point by far more than the bound above
         with torch.no_grad():
-            other, _, _ = _interpret_program(prog, den, start, [torch.randn(start.shape, generator=gen) for _ in range(prog.n_randn)])
+            other, _, _ = interpret_program(prog, den, start, [torch.randn(start.shape, generator=gen) for _ in range(prog.n_randn)])
         assert rel_l2(other.numpy(), want.numpy()) > 1e-2

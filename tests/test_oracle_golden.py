@@ -4,7 +4,8 @@ import pytest
 import torch
 
 from conftest import gold, rel_l2
-from helpers import d1grid_kwargs, seeded_unet, t, verify_checksums
+from helpers import d1grid_kwargs, per_layer_worst, seeded_unet, t, verify_checksums
+from sampler_oracles import check_sampler_case
 from oracle import torch_oracle as O
 from calodiffusion_amd.configs import load_config
 
@@ -108,13 +109,6 @@ def test_reverse_norm():
         assert np.array_equal(np.asarray(energy, dtype=np.float32), g[f"{tag}.energy"])
         assert rel_l2(np.asarray(data, dtype=np.float32), g[f"{tag}.data"]) < 2e-6, tag
         assert ((np.asarray(data) == 0) == (g[f"{tag}.data"] == 0)).mean() > 0.9999  # same voxels under the read-out threshold
-
-
-def per_layer_worst(got, want):
-    """Worst relative L2 over the (shower, layer) rows: an energy-weighted norm over the whole array hides the low-energy layers."""
-    num = np.linalg.norm((got - want).reshape(got.shape[0], got.shape[1], -1), axis=-1)
-    den = np.linalg.norm(want.reshape(got.shape[0], got.shape[1], -1), axis=-1)
-    return float((num / np.maximum(den, 1e-30)).max())
 
 
 def test_reverse_norm_hgcal():
@@ -295,20 +289,6 @@ def oracle_sampler(tag, g, m, start, E, layers, noise):
         x, xs, x0 = S.consistency(den, start, O.ddim_tables(over["CONSIS_NSTEPS"]), over["CONSIS_NSTEPS"], n, it)
         return x, xs, None
     raise KeyError(name)
-
-
-def check_sampler_case(tag, g, x, xs, x0s, tol):
-    """Final tensor (where the reference's is finite) and the stored trajectory slots of one sampler case."""
-    want = g[f"{tag}.x"]
-    if np.isfinite(want).all():
-        assert rel_l2(np.asarray(x), want) < tol, (tag, rel_l2(np.asarray(x), want))
-    else:  # Heun / DPM2 divide by t_next = 0 on their last step (see calodiffusion_amd/sample.py): not finite here either
-        assert not np.isfinite(np.asarray(x)).all(), tag
-    for k in g.files:
-        if k.startswith(tag + ".xs") and xs is not None:
-            assert rel_l2(np.asarray(xs[int(k.split("xs")[1])]), g[k]) < tol, k
-        if k.startswith(tag + ".x0s") and x0s is not None:
-            assert rel_l2(np.asarray(x0s[int(k.split("x0s")[1])]), g[k]) < tol, k
 
 
 def test_other_samplers_against_reference_trajectories():

@@ -7,7 +7,7 @@ import numpy as np, torch
 from conftest import gold, rel_l2
 from helpers import seeded_unet, t
 from sampler_cases import CASES
-from test_host import _interpret_program
+from sampler_oracles import interpret_program
 from oracle import torch_oracle as O
 from calodiffusion_amd.calodiffusion import CaloDiffusion
 from calodiffusion_amd.configs import load_config
@@ -33,8 +33,8 @@ def den_d(x, s):
     calls.append((float(s), rel_l2(y.numpy(), yo.numpy()), float(yo.norm()), float(x.norm())))
     return y
 with torch.no_grad():
-    xo = _interpret_program(prog, den_o, start, [])[0]
-    xd = _interpret_program(prog, den_d, start, [])[0]
+    xo = interpret_program(prog, den_o, start, [])[0]
+    xd = interpret_program(prog, den_d, start, [])[0]
 print("oracle-interpreted vs golden", rel_l2(xo.numpy(), g[f"{tag}.x"]))
 print("device-denoise-interpreted vs golden", rel_l2(xd.numpy(), g[f"{tag}.x"]))
 for c in calls: print("sigma %.4g: device vs oracle denoise rel %.2e (|D| %.3g, |x| %.3g)" % c)
