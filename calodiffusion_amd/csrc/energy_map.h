@@ -1,5 +1,5 @@
 // The incident-energy map between physical units and the conditioning value e, one device function per direction, shared by
-// cd_preprocess (kernels_preprocess.hip) and the generator's conditioning kernel (generator.hip) so that their bits agree.
+// cd_preprocess (kernels_preprocess.hip), cd_preprocess_hgcal (kernels_geom.hip) and the generator's conditioning kernel (generator.hip) so that their bits agree.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,18 @@ __device__ __forceinline__ float energy_to_cond(float e, float emin, float emax,
 __device__ __forceinline__ float cond_to_energy(float e, float emin, float base, float span, int logE) {
   if (logE) return __fmul_rn(emin, (float)pow((double)base, (double)e));
   return __fadd_rn(emin, __fmul_rn(span, e));
+}
+
+// HGCal: DataLoaderHGCal's per-column map (calodiffusion/utils/HGCal_utils.py:131-132, 158), np.array(emin) being float64: a
+// double computation rounded once.  Shared by cd_preprocess_hgcal (kernels_geom.hip) and the generator's conditioning kernel.
+__device__ __forceinline__ float energy_to_cond_hgcal(float e, double emin, double emax) {
+  return (float)(((double)e - emin) / (emax - emin));
+}
+
+// The physical energy ReverseNormHGCal scales by (HGCal_utils.py:195-199): emin + (emax - emin) * e on float64 arrays, rounded to
+// float32 at the end.  span = emax - emin formed in double on the host; product and sum are rounded one by one, nothing fused.
+__device__ __forceinline__ float cond_to_energy_hgcal(float e, double emin, double span) {
+  return (float)__dadd_rn(emin, __dmul_rn(span, (double)e));
 }
 
 }  // namespace cd

@@ -1,4 +1,5 @@
-// Reader of the generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file").
+// Reader of the generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file"), format
+// versions 1 (regular grids) and 2 (HGCal: a GEOM section with the geometry maps by their sparse entries).
 // Pure C++17, no HIP: cd_generator_create (generator.hip) and tools/generator_blob_check.cpp share it.
 //
 // parse() validates everything before anything is dereferenced: magic, version, total length, checksum, every section's
@@ -10,24 +11,30 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
+
+#include "geom_csr_check.h"
 
 namespace cdgen {
 
 constexpr char kMagic[8] = {'C', 'D', 'G', 'E', 'N', 'B', 'L', 'B'};
-constexpr uint32_t kVersion = 1;
+constexpr uint32_t kVersion = 1;      // regular-grid files
+constexpr uint32_t kVersionGeom = 2;  // HGCal files: a GEOM section, per-column EMAX / EMIN in RNRM
 constexpr uint64_t kHeaderBytes = 64, kSectionEntryBytes = 24, kAlign = 64;
 constexpr uint64_t kStepBytes = 16, kOpBytes = 40;  // sizeof(CdStep), sizeof(CdSamplerOp): generator.hip asserts both
 constexpr uint64_t kWeightRecordBytes = 112, kWeightNameBytes = 96;
 constexpr uint64_t kNetHeaderBytes = 32, kSamplerHeaderBytes = 64, kMetaBytes = 128, kRevNormBytes = 80;
+constexpr uint64_t kRevNormGeomBytes = 96, kGeomHeaderBytes = 64, kGeomMapHeaderBytes = 64;  // version 2
+constexpr int32_t kMaxEnergyCols = 8;                                                         // cd_preprocess_hgcal's limit
 
 constexpr uint32_t fourcc(char a, char b, char c, char d) {
   return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
 }
 constexpr uint32_t kTagMeta = fourcc('M', 'E', 'T', 'A'), kTagUnet = fourcc('U', 'N', 'E', 'T'), kTagLayer = fourcc('L', 'A', 'Y', 'R'),
                    kTagUnetSampler = fourcc('U', 'S', 'M', 'P'), kTagLayerSampler = fourcc('L', 'S', 'M', 'P'),
-                   kTagRevNorm = fourcc('R', 'N', 'R', 'M');
+                   kTagRevNorm = fourcc('R', 'N', 'R', 'M'), kTagGeom = fourcc('G', 'E', 'O', 'M');
 
 inline uint64_t fnv1a64(const unsigned char* p, uint64_t n) {
   uint64_t h = 0xcbf29ce484222325ull;
@@ -78,7 +85,26 @@ struct RevNorm {
   int32_t layer_map = 0, logE = 0, dataset_num = 0;
   float consts[6] = {0, 0, 0, 0, 0, 0};
   float max_deposit = 0, ecut = 0;
-  double emax = 0, emin = 0;
+  double emax = 0, emin = 0;  // version 2: column 0 of the lists below
+  // version 2 (HGCal); a version-1 file reads as one column, alpha and layer_eps unused
+  int32_t energy_cols = 1;
+  float alpha = 0, layer_eps = 0;  // cd_reverse_norm_staged's
+  double emax_col[kMaxEnergyCols] = {0}, emin_col[kMaxEnergyCols] = {0};
+};
+
+// one map of the GEOM section: per-layer CSR over layers * rows lines, little-endian arrays (views, possibly unaligned)
+struct GeomMap {
+  int32_t rows = 0, cols = 0, nnz = 0, is_mask = 0;
+  const unsigned char* row_ptr = nullptr;  // layers * rows + 1 int32
+  const unsigned char* col_idx = nullptr;  // nnz int32
+  const unsigned char* val = nullptr;      // nnz fp32
+};
+
+struct Geom {
+  int32_t form = -1;  // -1: no GEOM section; 0: pre-embedded (decoder only); 1: in-model (encoder and decoder)
+  int32_t layers = 0, alpha = 0, r = 0, cells = 0, n_maps = 0;
+  float embed_mean = 0, embed_std = 1;  // the converter's norm as its dec / enc apply it (0, 1: none)
+  GeomMap enc, dec;
 };
 
 struct Blob {
@@ -87,6 +113,7 @@ struct Blob {
   std::vector<Section> sections;
   Meta meta;
   RevNorm rev;
+  Geom geom;
   Net unet, layer;
   Sampler unet_sampler, layer_sampler;
 };
@@ -133,7 +160,55 @@ struct Cursor {
     uint64_t n;
     return mul_ok(count, elem, &n) && take(n, out);
   }
+  void align(uint64_t a) {  // the next array starts on a multiple of `a` (a section's last padding may be cut)
+    const uint64_t up = (pos + a - 1) / a * a;
+    pos = up < size ? up : size;
+  }
 };
+
+// GEOM: header {form, L, A, R, N, n_maps, embed_mean, embed_std}, then n_maps records {rows, cols, nnz, is_mask} each followed by
+// row_ptr, col_idx and val, every piece on a 64-byte boundary.  Counts against the section, shapes against the bins, then the CSR
+// invariants -- all before a consumer reads a record.
+inline bool parse_geom(const unsigned char* sec, uint64_t size, Geom* g, std::string* err) {
+  Cursor c{sec, size, 0};
+  const unsigned char* h;
+  if (!c.take(kGeomHeaderBytes, &h)) return *err = "GEOM: section shorter than its header", false;
+  int32_t* f[6] = {&g->form, &g->layers, &g->alpha, &g->r, &g->cells, &g->n_maps};
+  for (int i = 0; i < 6; ++i) *f[i] = rd<int32_t>(h + 4 * i);
+  g->embed_mean = rd<float>(h + 24);
+  g->embed_std = rd<float>(h + 28);
+  if (g->form != 0 && g->form != 1) return g->form = -1, *err = "GEOM: unknown form (0: pre-embedded, 1: in-model)", false;
+  if (g->n_maps != g->form + 1) return *err = "GEOM: form 0 holds one map (the decoder), form 1 two (encoder, decoder)", false;
+  if (g->layers < 1 || g->alpha < 1 || g->r < 1 || g->cells < 1 || g->layers > 65536 || g->alpha > 65536 || g->r > 65536 ||
+      (uint64_t)g->layers * (uint64_t)g->cells > (1ull << 28) || (uint64_t)g->alpha * (uint64_t)g->r > (1ull << 28))
+    return *err = "GEOM: bins or cell count out of range", false;
+  if (!std::isfinite(g->embed_mean) || !std::isfinite(g->embed_std) || g->embed_std == 0.f)
+    return *err = "GEOM: embed_mean / embed_std must be finite and embed_std not 0", false;
+  if (g->form == 1 && (g->embed_mean != 0.f || g->embed_std != 1.f)) return *err = "GEOM: an in-model converter has no norm", false;
+  const int32_t grid = g->alpha * g->r;
+  for (int k = 0; k < g->n_maps; ++k) {
+    const bool is_enc = g->form == 1 && k == 0;
+    GeomMap* m = is_enc ? &g->enc : &g->dec;
+    const std::string what = is_enc ? "GEOM encoder" : "GEOM decoder";
+    if (!c.take(kGeomMapHeaderBytes, &h)) return *err = what + ": record header overflows the section", false;
+    m->rows = rd<int32_t>(h); m->cols = rd<int32_t>(h + 4); m->nnz = rd<int32_t>(h + 8); m->is_mask = rd<int32_t>(h + 12);
+    if (m->rows != (is_enc ? grid : g->cells) || m->cols != (is_enc ? g->cells : grid))
+      return *err = what + ": its shape is not that of the bins and the cell count", false;
+    if (m->nnz < 0) return *err = what + ": negative entry count", false;
+    if (g->form == 0 && m->is_mask) return *err = what + ": a pre-embedded file holds a frozen decoder, not a mask's pattern", false;
+    uint64_t lines;
+    if (!mul_ok((uint64_t)g->layers, (uint64_t)m->rows, &lines) || !add_ok(lines, 1, &lines) || !c.take_array(lines, 4, &m->row_ptr))
+      return *err = what + ": row_ptr overflows the section", false;
+    c.align(kAlign);
+    if (!c.take_array((uint64_t)m->nnz, 4, &m->col_idx)) return *err = what + ": " + std::to_string(m->nnz) + " columns overflow the section", false;
+    c.align(kAlign);
+    if (!c.take_array((uint64_t)m->nnz, 4, &m->val)) return *err = what + ": " + std::to_string(m->nnz) + " values overflow the section", false;
+    c.align(kAlign);
+    std::string why;
+    if (!cdgeom::csr_valid(m->row_ptr, m->col_idx, m->val, g->layers, m->rows, m->cols, m->nnz, &why)) return *err = what + ": " + why, false;
+  }
+  return true;
+}
 
 inline bool parse_net(const unsigned char* sec, uint64_t size, const char* what, bool with_coords, Net* net, std::string* err) {
   Cursor c{sec, size, 0};
@@ -217,8 +292,10 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   if (bytes < kHeaderBytes) return *err = "generator file: shorter than its 64-byte header", false;
   if (memcmp(p, kMagic, 8) != 0) return *err = "generator file: wrong magic (not a generator file)", false;
   out->version = rd<uint32_t>(p + 8);
-  if (out->version != kVersion)
-    return *err = "generator file: format version " + std::to_string(out->version) + ", this reader knows version " + std::to_string(kVersion), false;
+  if (out->version != kVersion && out->version != kVersionGeom)
+    return *err = "generator file: format version " + std::to_string(out->version) + ", this reader knows versions " + std::to_string(kVersion) +
+                  " and " + std::to_string(kVersionGeom), false;
+  const bool v2 = out->version == kVersionGeom;
   const uint32_t n_sections = rd<uint32_t>(p + 12);
   out->total_bytes = rd<uint64_t>(p + 16);
   out->checksum = rd<uint64_t>(p + 24);
@@ -246,9 +323,12 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   const Section* sr = find_section(*out, kTagRevNorm);
   const Section* su = find_section(*out, kTagUnet);
   const Section* sus = find_section(*out, kTagUnetSampler);
+  const Section* sg = find_section(*out, kTagGeom);
+  if (v2 && !sg) return *err = "generator file: format version 2 must have a GEOM section (a version-1 payload under a version-2 header?)", false;
+  if (!v2 && sg) return *err = "generator file: a GEOM section in a format version 1 file", false;
   if (!sm || !sr || !su || !sus) return *err = "generator file: a required section (META, RNRM, UNET, USMP) is missing", false;
+  if (sr->bytes < (v2 ? kRevNormGeomBytes : kRevNormBytes)) return *err = "RNRM: section shorter than its record", false;
   if (sm->bytes < kMetaBytes) return *err = "META: section shorter than its record", false;
-  if (sr->bytes < kRevNormBytes) return *err = "RNRM: section shorter than its record", false;
 
   Meta& m = out->meta;
   const unsigned char* q = p + sm->off;
@@ -269,6 +349,29 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   r.max_deposit = rd<float>(q + 48); r.ecut = rd<float>(q + 52);
   r.emax = rd<double>(q + 56); r.emin = rd<double>(q + 64);
 
+  if (v2) {
+    r.energy_cols = rd<int32_t>(q + 80);
+    r.alpha = rd<float>(q + 88); r.layer_eps = rd<float>(q + 92);
+    uint64_t need;
+    if (r.energy_cols < 1 || r.energy_cols > kMaxEnergyCols || !mul_ok((uint64_t)r.energy_cols, 16, &need) ||
+        !add_ok(need, kRevNormGeomBytes, &need) || need > sr->bytes)
+      return *err = "RNRM: 1 to 8 energy columns, each with its EMAX and EMIN inside the section", false;
+    for (int k = 0; k < r.energy_cols; ++k) {
+      r.emax_col[k] = rd<double>(q + kRevNormGeomBytes + 8 * k);
+      r.emin_col[k] = rd<double>(q + kRevNormGeomBytes + 8 * (r.energy_cols + k));
+      if (!(r.emax_col[k] > r.emin_col[k]) || !std::isfinite(r.emax_col[k]) || !std::isfinite(r.emin_col[k]))
+        return *err = "RNRM: EMAX must exceed EMIN in every energy column", false;
+    }
+    if (r.emax != r.emax_col[0] || r.emin != r.emin_col[0]) return *err = "RNRM: EMAX / EMIN are not column 0 of their lists", false;
+    if (!(r.alpha >= 0.f) || !(r.alpha < 0.5f) || !(r.layer_eps >= 0.f) || !std::isfinite(r.layer_eps))
+      return *err = "RNRM: the staged constants (alpha, layer eps) are out of range", false;
+    if (m.energy_cols != r.energy_cols) return *err = "META: energy_cols disagrees with the RNRM record", false;
+    if (!parse_geom(p + sg->off, sg->bytes, &out->geom, err)) return false;
+  } else {
+    r.energy_cols = 1;
+    r.emax_col[0] = r.emax; r.emin_col[0] = r.emin;
+  }
+
   // the records against each other
   uint64_t vox = 1;
   for (int i = 0; i < 3; ++i) {
@@ -276,16 +379,23 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
     vox *= (uint64_t)r.dims[i];
   }
   if (vox > (1ull << 28)) return *err = "RNRM: more than 2^28 voxels", false;
-  if (m.data_ndim != 4 || m.data_shape[0] != 1 || m.data_shape[1] != r.dims[0] || m.data_shape[2] != r.dims[1] || m.data_shape[3] != r.dims[2])
+  const Geom& g = out->geom;
+  if (v2 && (g.layers != r.dims[0] || g.alpha != r.dims[1] || g.r != r.dims[2])) return *err = "GEOM: its bins are not the RNRM grid", false;
+  if (v2 && g.form == 1) {
+    if (m.data_ndim != 3 || m.data_shape[0] != 1 || m.data_shape[1] != g.layers || m.data_shape[2] != g.cells || m.data_shape[3] != 0)
+      return *err = "META: the data shape of an in-model file is not (1, L, N) of its GEOM section", false;
+    if (m.has_layer_stage) return *err = "META: a layer stage over an in-model embedding is not provided", false;
+  } else if (m.data_ndim != 4 || m.data_shape[0] != 1 || m.data_shape[1] != r.dims[0] || m.data_shape[2] != r.dims[1] || m.data_shape[3] != r.dims[2]) {
     return *err = "META: the data shape is not (1, D, H, W) of the RNRM grid", false;
-  if (m.energy_cols != 1) return *err = "META: one incident-energy column is the only form of format version 1", false;
+  }
+  if (!v2 && m.energy_cols != 1) return *err = "META: one incident-energy column is the only form of format version 1", false;
   if (m.sample_steps < 1 || m.sample_steps > (1 << 20) || m.sample_offset < 0 || m.layer_steps < 0 || m.layer_steps > (1 << 20))
     return *err = "META: step counts out of range", false;
   if ((m.takes_layers != 0) != (r.layer_map != 0)) return *err = "META: takes_layers disagrees with the shower map", false;
   if (m.takes_layers && m.layer_dim != r.dims[0] + 1) return *err = "META: layer_dim is not D + 1", false;
   if (m.cond_size != m.energy_cols + (m.takes_layers ? m.layer_dim : 0)) return *err = "META: conditioning width disagrees with the map", false;
   if (m.has_layer_stage && !m.takes_layers) return *err = "META: a layer stage needs a 'layer-' shower map", false;
-  if (!(r.emax > r.emin) || (r.logE && !(r.emin > 0)) || !(r.max_deposit > 0))
+  if (!(r.emax > r.emin) || (!v2 && r.logE && !(r.emin > 0)) || !(r.max_deposit > 0))
     return *err = "RNRM: EMAX must exceed EMIN (> 0 with logE) and MAXDEP must be positive", false;
 
   if (!parse_net(p + su->off, su->bytes, "UNET", true, &out->unet, err)) return false;

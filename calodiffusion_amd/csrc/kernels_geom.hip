@@ -2,9 +2,11 @@
 // for the sparse decode, the column-major view of its entries > 1e-6), the product with a batch of showers, and
 // generate_sparse_mat's sampled decode in two gather passes, and the HGCal forward pre-processing, which applies the packed encoder
 // inside its own launch (cd_preprocess_hgcal).  Kernels and their C ABI; nothing here touches a plan.
+#include "energy_map.h"
 #include "philox.h"
 #include "guarded.h"
 #include "kernels_geom.h"
+#include "geom_csr_check.h"
 
 #include <climits>
 #include <type_traits>
@@ -247,8 +249,7 @@ __global__ void __launch_bounds__(kHgThreads) preprocess_hgcal_kernel(PreHgcalAr
   }
   // np.array(emin) is float64: a double computation rounded once (HGCal_utils.py:131-132, 158)
   if (tid < a.gen_cols)
-    a.e_out[(size_t)b * a.gen_cols + tid] =
-        (float)(((double)a.gen_info[(size_t)b * a.gen_cols + tid] - a.emin[tid]) / (a.emax[tid] - a.emin[tid]));
+    a.e_out[(size_t)b * a.gen_cols + tid] = energy_to_cond_hgcal(a.gen_info[(size_t)b * a.gen_cols + tid], a.emin[tid], a.emax[tid]);
   double* lsum = hg_smem;
   float* q_lds = (float*)(hg_smem + ((L + 1) & ~1));
   const float denom = __fmul_rn(a.max_deposit, e);
@@ -431,6 +432,143 @@ static void geom_create(const float* dense, const float* mask, int layers, int r
   own.m = nullptr;
 }
 
+// ---- a packed map from its sparse entries (cd_geom_create_csr) -------------------------------------------------------
+// The CSR arrays are the caller's, uploaded as they are.  ent_row: a thread per line writes its own number over its entries.
+__global__ void __launch_bounds__(256) geom_csr_ent_row_kernel(const int* __restrict__ row_ptr, int n_lines, int* __restrict__ ent_row) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_lines) return;
+  for (int p = row_ptr[r]; p < row_ptr[r + 1]; ++p) ent_row[p] = r;
+}
+
+// The two views by column, without the dense tensor: a thread per entry counts its (layer, column) line (integer atomics), the
+// scan turns counts into line starts, a thread per entry takes a slot of its line (in whatever order the threads arrive) and a
+// thread per line sorts its slots by CSR position -- a line holds at most one entry of a row and positions ascend with the
+// rows, so the sorted line is rows ascending and no longer depends on the order of arrival.  positive_only: the entries
+// > SPARSE_EPS (the sampled decode's view); otherwise all of them (the transposed view).
+__device__ __forceinline__ bool csr_kept(const float* __restrict__ val, int p, int positive_only) {
+  return !positive_only || val[p] > SPARSE_EPS;
+}
+__device__ __forceinline__ int csr_line(const int* __restrict__ ent_row, const int* __restrict__ col_idx, int p, int rows, int cols) {
+  return (ent_row[p] / rows) * cols + col_idx[p];
+}
+template <bool FILL>
+__global__ void __launch_bounds__(256) geom_csr_by_column_kernel(const int* __restrict__ ent_row, const int* __restrict__ col_idx,
+                                                                 const float* __restrict__ val, int nnz, int rows, int cols,
+                                                                 int positive_only, int* cursor, int* __restrict__ slot) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= nnz || !csr_kept(val, p, positive_only)) return;
+  const int at = atomicAdd(&cursor[csr_line(ent_row, col_idx, p, rows, cols)], 1);
+  if (FILL) slot[at] = p;
+}
+// ptr: the scanned line starts.  out_row: the row within the layer; out_pos (transposed view) or out_val (column view).
+__global__ void __launch_bounds__(256) geom_csr_sort_lines_kernel(const int* __restrict__ ptr, int n_lines, int* __restrict__ slot,
+                                                                  const int* __restrict__ ent_row, const float* __restrict__ val,
+                                                                  int rows, int* __restrict__ out_row, int* __restrict__ out_pos,
+                                                                  float* __restrict__ out_val) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_lines) return;
+  const int lo = ptr[c], hi = ptr[c + 1];
+  for (int i = lo + 1; i < hi; ++i) {  // insertion sort: a line holds a handful of entries
+    const int key = slot[i];
+    int j = i - 1;
+    for (; j >= lo && slot[j] > key; --j) slot[j + 1] = slot[j];
+    slot[j + 1] = key;
+  }
+  for (int i = lo; i < hi; ++i) {
+    const int p = slot[i];
+    out_row[i] = ent_row[p] % rows;
+    if (out_pos) out_pos[i] = p;
+    if (out_val) out_val[i] = val[p];
+  }
+}
+
+struct DeviceInts {  // scratch of one view's build
+  int* p = nullptr;
+  ~DeviceInts() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// kPackColumns or kPackTransposed from the uploaded CSR arrays (and ent_row)
+static void pack_csr_view(CdGeomMap* m, GeomPack kind, hipStream_t s) {
+  const int n_lines = m->layers * m->cols, nnz = m->nnz, positive_only = kind == kPackColumns;
+  int* ptr = nullptr;
+  CD_HIP(hipMalloc(&ptr, sizeof(int) * ((size_t)n_lines + 1)));
+  (kind == kPackColumns ? m->col_ptr : m->t_ptr) = ptr;
+  CD_HIP(hipMemsetAsync(ptr, 0, sizeof(int) * ((size_t)n_lines + 1), s));
+  const dim3 per_entry((unsigned)((nnz + 255) / 256)), per_line((unsigned)((n_lines + 255) / 256));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(geom_csr_by_column_kernel<false>, per_entry, dim3(256), 0, s, m->ent_row, m->col_idx, m->val, nnz, m->rows, m->cols,
+                       positive_only, ptr, (int*)nullptr);
+    CD_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(1024), 0, s, ptr, n_lines);
+  CD_HIP(hipGetLastError());
+  int kept = 0;
+  CD_HIP(hipMemcpyAsync(&kept, ptr + n_lines, sizeof(int), hipMemcpyDeviceToHost, s));
+  CD_HIP(hipStreamSynchronize(s));
+  const size_t n = (size_t)(kept > 0 ? kept : 1);
+  if (kind == kPackColumns) {
+    CD_HIP(hipMalloc(&m->row_idx, sizeof(int) * n));
+    CD_HIP(hipMalloc(&m->cval, sizeof(float) * n));
+  } else {
+    CD_HIP(hipMalloc(&m->t_row, sizeof(int) * n));
+    CD_HIP(hipMalloc(&m->t_pos, sizeof(int) * n));
+  }
+  if (kept == 0) return;
+  DeviceInts cursor, slot;
+  CD_HIP(hipMalloc(&cursor.p, sizeof(int) * (size_t)n_lines));
+  CD_HIP(hipMalloc(&slot.p, sizeof(int) * n));
+  CD_HIP(hipMemcpyAsync(cursor.p, ptr, sizeof(int) * (size_t)n_lines, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(geom_csr_by_column_kernel<true>, per_entry, dim3(256), 0, s, m->ent_row, m->col_idx, m->val, nnz, m->rows, m->cols,
+                     positive_only, cursor.p, slot.p);
+  CD_HIP(hipGetLastError());
+  hipLaunchKernelGGL(geom_csr_sort_lines_kernel, per_line, dim3(256), 0, s, ptr, n_lines, slot.p, m->ent_row, m->val, m->rows,
+                     kind == kPackColumns ? m->row_idx : m->t_row, kind == kPackColumns ? (int*)nullptr : m->t_pos,
+                     kind == kPackColumns ? m->cval : (float*)nullptr);
+  CD_HIP(hipGetLastError());
+  CD_HIP(hipStreamSynchronize(s));  // the scratch goes
+}
+
+static void geom_create_csr(const int32_t* row_ptr, const int32_t* col_idx, const float* val, int layers, int rows, int cols, int flags,
+                            CdGeomMap** out, hipStream_t s) {
+  CD_REQUIRE(row_ptr && out && layers > 0 && rows > 0 && cols > 0, "bad argument");
+  CD_REQUIRE((flags & ~(CD_GEOM_COLUMNS | CD_GEOM_TRANSPOSED)) == 0, "cd_geom_create_csr: unknown flag");
+  CD_REQUIRE((int64_t)layers * (rows > cols ? rows : cols) <= cdgeom::kMaxLines, "cd_geom_create_csr: layers * max(rows, cols) must stay within 2^30");
+  const int n_lines = layers * rows;
+  const int nnz = row_ptr[n_lines];
+  CD_REQUIRE(nnz >= 0 && (nnz == 0 || (col_idx && val)), "cd_geom_create_csr: col_idx and val are required for a map with entries");
+  std::string err;
+  if (!cdgeom::csr_valid((const unsigned char*)row_ptr, (const unsigned char*)col_idx, (const unsigned char*)val, layers, rows, cols, nnz, &err))
+    throw Fail{CD_EINVAL, "cd_geom_create_csr: " + err};
+  struct Owner {
+    CdGeomMap* m;
+    ~Owner() { delete m; }
+  } own{new CdGeomMap};
+  CdGeomMap* m = own.m;
+  m->layers = layers; m->rows = rows; m->cols = cols; m->nnz = nnz;
+  const size_t n = (size_t)(nnz > 0 ? nnz : 1);
+  bool zeros = false;  // a pattern with zeros is a mask's (cd_geom_create_ex's `masked`)
+  for (int p = 0; p < nnz && !zeros; ++p) zeros = val[p] == 0.f;
+  m->masked = zeros;
+  CD_HIP(hipMalloc(&m->row_ptr, sizeof(int) * ((size_t)n_lines + 1)));
+  CD_HIP(hipMalloc(&m->col_idx, sizeof(int) * n));
+  CD_HIP(hipMalloc(&m->val, sizeof(float) * n));
+  CD_HIP(hipMalloc(&m->ent_row, sizeof(int) * n));
+  CD_HIP(hipMemcpyAsync(m->row_ptr, row_ptr, sizeof(int) * ((size_t)n_lines + 1), hipMemcpyHostToDevice, s));
+  if (nnz > 0) {
+    CD_HIP(hipMemcpyAsync(m->col_idx, col_idx, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    CD_HIP(hipMemcpyAsync(m->val, val, sizeof(float) * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(geom_csr_ent_row_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, s, m->row_ptr, n_lines, m->ent_row);
+    CD_HIP(hipGetLastError());
+  }
+  if (flags & CD_GEOM_COLUMNS) pack_csr_view(m, kPackColumns, s);
+  if (flags & CD_GEOM_TRANSPOSED) pack_csr_view(m, kPackTransposed, s);
+  CD_HIP(hipStreamSynchronize(s));  // the caller may free its arrays when this returns
+  *out = m;
+  own.m = nullptr;
+}
+
 // grid of the two per-row kernels: x covers the rows, y the layers, z the batch rows (both strided past the grid limit)
 static dim3 row_grid(const CdGeomMap* m, int64_t batch_rows) {
   return dim3((unsigned)((m->rows + 255) / 256), (unsigned)(m->layers < 65535 ? m->layers : 65535),
@@ -448,6 +586,11 @@ int cd_geom_create(const float* dense_dev, int layers, int rows, int cols, int w
 int cd_geom_create_ex(const float* dense_dev, const float* mask_dev, int layers, int rows, int cols, int flags, CdGeomMap** out,
                       void* stream) {
   return guarded([&] { geom_create(dense_dev, mask_dev, layers, rows, cols, flags, out, (hipStream_t)stream); });
+}
+
+int cd_geom_create_csr(const int32_t* row_ptr, const int32_t* col_idx, const float* val, int layers, int rows, int cols, int flags,
+                       CdGeomMap** out, void* stream) {
+  return guarded([&] { geom_create_csr(row_ptr, col_idx, val, layers, rows, cols, flags, out, (hipStream_t)stream); });
 }
 
 int cd_geom_refresh(CdGeomMap* map, const float* dense_dev, void* stream) {

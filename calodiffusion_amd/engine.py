@@ -63,6 +63,16 @@ class CdHlfDesc(C.Structure):
                 ("eta", C.POINTER(C.c_double)), ("phi", C.POINTER(C.c_double)), ("with_centres", C.POINTER(C.c_int32))]
 
 
+class CdGeneratorRun(C.Structure):
+    """The arguments of cd_generator_run_ex."""
+    _fields_ = [("struct_size", C.c_uint32), ("batch", C.c_int32), ("energy", C.c_void_p), ("energy_is_normalised", C.c_int32),
+                ("sparse_mode", C.c_int32), ("layers", C.c_void_p), ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("first_row", C.c_int32), ("global_batch", C.c_int32), ("showers", C.c_void_p), ("layers_out", C.c_void_p),
+                ("next_offset", C.POINTER(C.c_uint64)), ("decode_seed", C.c_uint64), ("decode_offset", C.c_uint64),
+                ("next_decode_offset", C.POINTER(C.c_uint64)), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
 class CdClassifierDesc(C.Structure):
     """The classifier test's DNN (calodiffusion_amd.classifier)."""
     _fields_ = [("struct_size", C.c_uint32), ("input_dim", C.c_int32), ("hidden", C.c_int32), ("num_layer", C.c_int32),
@@ -122,6 +132,7 @@ _SIGNATURES = {
                                       C.POINTER(C.c_double), C.c_float, _P]),
     "cd_geom_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
     "cd_geom_create_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
+    "cd_geom_create_csr": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
     "cd_geom_refresh": (C.c_int, [_P, _P, _P]),
     "cd_geom_destroy": (C.c_int, [_P]),
     "cd_geom_apply_vjp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
@@ -153,6 +164,7 @@ _SIGNATURES = {
     "cd_generator_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_generator_run": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64),
                                    _P, C.c_size_t, _P]),
+    "cd_generator_run_ex": (C.c_int, [_P, C.POINTER(CdGeneratorRun)]),
     "cd_hlf_create": (C.c_int, [C.POINTER(CdHlfDesc), C.POINTER(_P), _P]),
     "cd_hlf_destroy": (C.c_int, [_P]),
     "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),

@@ -7,8 +7,10 @@ sampler exactly as the Python path hands it to the library, and the inverse pre-
 file into "incident energies in, physical showers out"; ``Generator`` is the thin ctypes wrapper over them, and
 tools/cd_generate_example.c the same from C.
 
-First-version scope: DATASET_NUM 2 / 3 with a ``[layer-]logit-norm`` map, any width the plan takes, any sampler that compiles to a
-CdStep table or to a step program that does not depend on the batch.  Everything else is refused at export, by name.
+Scope: DATASET_NUM 2 / 3 (format version 1) and HGCal (format version 2, whose ``GEOM`` section carries the geometry maps by
+their sparse entries: the decoder of a pre-embedded model's ``geometry=`` converter, or both maps of a model with the converter
+inside) with a ``[layer-]logit-norm`` map, any width the plan takes, any sampler that compiles to a CdStep table or to a step
+program that does not depend on the batch.  Everything else is refused at export, by name.
 """
 from __future__ import annotations
 
@@ -23,10 +25,13 @@ import torch
 from . import engine
 
 MAGIC = b"CDGENBLB"
-FORMAT_VERSION = 1
+FORMAT_VERSION = 1       # regular-grid files: written as they always were, byte for byte
+FORMAT_VERSION_GEOM = 2  # HGCal files: a GEOM section, energy columns, per-column EMAX / EMIN in RNRM
+STAGED_ALPHA = STAGED_LAYER_EPS = 1e-8  # ReverseNormHGCal's reverse_logit alpha and layer threshold (postprocess.py)
 HEADER_BYTES, SECTION_ENTRY_BYTES, ALIGN = 64, 24, 64
 WEIGHT_RECORD_BYTES, WEIGHT_NAME_BYTES = 112, 96
 TAG_META, TAG_UNET, TAG_LAYER, TAG_UNET_SAMPLER, TAG_LAYER_SAMPLER, TAG_REVNORM = b"META", b"UNET", b"LAYR", b"USMP", b"LSMP", b"RNRM"
+TAG_GEOM = b"GEOM"
 
 
 def fnv1a64(data: bytes) -> int:
@@ -147,17 +152,77 @@ def _net_section(desc, state_dict, coords=()) -> bytes:
     return _pad(front + records, 64) + data
 
 
-def _refuse_out_of_scope(model, debug):
+def _geom_map_record(m, layers: int) -> bytes:
+    """One map of the GEOM section: {rows, cols, nnz, is_mask}, then row_ptr, col_idx, val, each piece 64-byte aligned.  The
+    pattern is the one ``m.packed()`` has: the non-zeros of a frozen map, the mask of a trainable one."""
+    from .hgcal import map_entries
+    row_ptr, col_idx, val = map_entries(m.mat, m.mask if m.trainable else None)
+    rows, cols = (int(v) for v in m.mat.shape[1:])
+    assert row_ptr.shape == (layers * rows + 1,)
+    return (_pad(struct.pack("<4i", rows, cols, len(col_idx), int(m.trainable)), 64) + _pad(row_ptr.astype("<i4").tobytes(), 64) +
+            _pad(col_idx.astype("<i4").tobytes(), 64) + _pad(val.astype("<f4").tobytes(), 64))
+
+
+def _geom_section(conv, form: int) -> bytes:
+    """GEOM: {form, L, A, R, N, n_maps, embed_mean, embed_std} and the decoder (form 0), or the encoder then the decoder (form 1)."""
+    L, A, R = conv.num_layers, conv.num_alpha_bins, conv.num_r_bins
+    N = int(conv.decoder.mat.shape[1])
+    std, mean = conv._affine()
+    maps = [conv.decoder] if form == 0 else [conv.embeder, conv.decoder]
+    head = struct.pack("<6i2f", form, L, A, R, N, len(maps), float(mean), float(std))
+    return _pad(head, 64) + b"".join(_geom_map_record(m, L) for m in maps)
+
+
+def _hgcal_form(model, geometry):
+    """None for a regular-grid model; else (form, converter) of an HGCal model, or the refusal by name."""
+    from .hgcal import HGCalConverter
+    from .postprocess import DATASET_PARAMS
+    cfg = model.config
+    if not (cfg.get("HGCAL", False) or getattr(model, "hgcal", False)):
+        if geometry is not None:
+            raise ValueError("export_generator: geometry= is for HGCal models (a pre-embedded one's converter); this model has none")
+        return None
+    if getattr(model, "do_embed", False):
+        if not isinstance(model.NN_embed, HGCalConverter):
+            raise NotImplementedError("export_generator: an HGCal model with an in-model embedding (do_embed) that is not an "
+                                      "hgcal.HGCalConverter is not provided")
+        if geometry is not None:
+            raise ValueError("export_generator: this HGCal model has its converter inside (do_embed): the file takes model.NN_embed, "
+                             "geometry= must not be given")
+        form, conv = 1, model.NN_embed
+    else:
+        if geometry is None:
+            raise NotImplementedError("export_generator: a pre-embedded HGCal model needs its geometry maps in the file: pass "
+                                      "geometry=<hgcal.HGCalConverter>, what generate(geometry=) takes")
+        if not isinstance(geometry, HGCalConverter):
+            raise TypeError("export_generator(geometry=) takes an hgcal.HGCalConverter")
+        if geometry.trainable:
+            raise NotImplementedError("export_generator: the geometry= converter of a pre-embedded HGCal model must be frozen "
+                                      "(trainable=False): the sampled decode's view holds values, not a trainable map's mask")
+        form, conv = 0, geometry
+    if cfg.get("DATASET_NUM") not in DATASET_PARAMS:
+        raise NotImplementedError(f"export_generator: no HGCal constants for DATASET_NUM {cfg.get('DATASET_NUM')!r} "
+                                  "(postprocess.DATASET_PARAMS)")
+    grid = tuple(int(v) for v in cfg["SHAPE_FINAL"][2:])
+    if (conv.num_layers, conv.num_alpha_bins, conv.num_r_bins) != grid:
+        raise ValueError(f"export_generator: the converter maps onto (layers, alpha, r) = "
+                         f"{(conv.num_layers, conv.num_alpha_bins, conv.num_r_bins)}, SHAPE_FINAL gives the U-Net the grid {grid}")
+    return form, conv
+
+
+def _refuse_out_of_scope(model, debug, geometry=None):
+    """Raises for what a generator file does not hold, by name; returns ``_hgcal_form``'s (form, converter), None off HGCal."""
     cfg = model.config
     if debug:
         raise NotImplementedError("export_generator: a debug trajectory request is not part of a generator file (cd_generator_run "
                                   "returns showers only)")
-    if cfg.get("HGCAL", False) or getattr(model, "hgcal", False):
-        raise NotImplementedError("export_generator: HGCal configs are not provided: their geometry maps would have to be in the file")
-    if cfg.get("DATASET_NUM", 2) not in (2, 3):
+    geom = _hgcal_form(model, geometry)
+    if geom is not None:
+        pass  # (its own checks are _hgcal_form's)
+    elif cfg.get("DATASET_NUM", 2) not in (2, 3):
         raise NotImplementedError(f"export_generator: Dataset {cfg.get('DATASET_NUM')} is not provided (DATASET_NUM 2 / 3 only): the "
                                   "irregular geometry would have to be in the file")
-    if getattr(model, "do_embed", False) or getattr(model, "NN_embed", None) is not None:
+    elif getattr(model, "do_embed", False) or getattr(model, "NN_embed", None) is not None:
         raise NotImplementedError("export_generator: a model with an in-model geometry embedding (do_embed) is not provided: its "
                                   "maps would have to be in the file")
     if cfg.get("SHOWERMAP") not in ("layer-logit-norm", "logit-norm"):
@@ -165,14 +230,18 @@ def _refuse_out_of_scope(model, debug):
     missing = [k for k in ("EMAX", "EMIN", "logE", "MAXDEP", "ECUT") if k not in cfg]
     if missing:
         raise ValueError(f"export_generator: the config lacks {missing}: the inverse pre-processing record needs them")
+    return geom
 
 
-def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Optional[str] = None, debug: bool = False) -> bytes:
+def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Optional[str] = None, debug: bool = False,
+                     geometry=None) -> bytes:
     """The generator file of ``model`` (a ``CaloDiffusion`` or ``LayerDiffusion`` as constructed from its config) for
-    ``model.generate(loader, sample_steps, sample_offset=sample_offset)``; also written to ``path`` when given."""
+    ``model.generate(loader, sample_steps, sample_offset=sample_offset)``; also written to ``path`` when given.  ``geometry``: the
+    ``hgcal.HGCalConverter`` of a pre-embedded HGCal model, what ``generate(geometry=)`` takes (frozen); an HGCal model with the
+    converter inside writes ``model.NN_embed`` and takes none.  Runs without a GPU and without the library."""
     from .layerdiffusion import LayerDiffusion
     from .postprocess import DATASET_PARAMS
-    _refuse_out_of_scope(model, debug)
+    geom = _refuse_out_of_scope(model, debug, geometry)
     cfg = model.config
     sample_steps, sample_offset = int(sample_steps), int(sample_offset or 0)
     two_stage = isinstance(model, LayerDiffusion)
@@ -181,7 +250,11 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
     coords = opts.pop("coords")
     data_shape = [int(v) for v in model._data_shape]
     D, H, W = (int(v) for v in cfg["SHAPE_FINAL"][2:])
-    if data_shape != [1, D, H, W]:
+    if geom is not None and geom[0] == 1:
+        cells = int(geom[1].decoder.mat.shape[1])
+        if data_shape != [1, D, cells]:
+            raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (1, L, N) cell-space shower")
+    elif data_shape != [1, D, H, W]:
         raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (1, D, H, W) grid")
     layer_map = "layer" in cfg["SHOWERMAP"]
 
@@ -198,14 +271,31 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
                  (TAG_UNET_SAMPLER, _sampler_section(net))]
 
     c = DATASET_PARAMS[cfg["DATASET_NUM"]]
-    rev = struct.pack("<6i8f2d", D, H, W, int(layer_map), int(bool(cfg["logE"])), int(cfg["DATASET_NUM"]),
-                      c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"],
-                      float(cfg["MAXDEP"]), float(cfg["ECUT"]), float(cfg["EMAX"]), float(cfg["EMIN"]))
+    if geom is None:
+        rev = struct.pack("<6i8f2d", D, H, W, int(layer_map), int(bool(cfg["logE"])), int(cfg["DATASET_NUM"]),
+                          c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"],
+                          float(cfg["MAXDEP"]), float(cfg["ECUT"]), float(cfg["EMAX"]), float(cfg["EMIN"]))
+    energy_cols = 1
+    if geom is not None:
+        # ReverseNormHGCal: np.array(emin) + (np.array(emax) - np.array(emin)) * e over the (B, cols) conditioning values
+        energy_cols = int(unet.cond_size) - (D + 1 if layer_map else 0)
+        if not 1 <= energy_cols <= 8:
+            raise NotImplementedError(f"export_generator: {energy_cols} incident-energy columns (1 to 8 are provided)")
+        emax = np.broadcast_to(np.atleast_1d(np.asarray(cfg["EMAX"], dtype=np.float64)), (energy_cols,))
+        emin = np.broadcast_to(np.atleast_1d(np.asarray(cfg["EMIN"], dtype=np.float64)), (energy_cols,))
+        rev = struct.pack("<6i8f2d", D, H, W, int(layer_map), int(bool(cfg["logE"])), int(cfg["DATASET_NUM"]),
+                          c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"],
+                          float(cfg["MAXDEP"]), float(cfg["ECUT"]), float(emax[0]), float(emin[0]))
+        rev = _pad(rev, 80) + struct.pack("<2i2f", energy_cols, 0, STAGED_ALPHA, STAGED_LAYER_EPS)
+        rev += emax.astype("<f8").tobytes() + emin.astype("<f8").tobytes()
     name = str(cfg.get("CHECKPOINT_NAME", "")).encode()[:63]
-    meta = struct.pack("<12iQ2i", 4, *data_shape, unet.cond_size, 1, int(two_stage), int(layer_map), sample_steps,
+    shape4 = data_shape + [0] * (4 - len(data_shape))
+    meta = struct.pack("<12iQ2i", len(data_shape), *shape4, unet.cond_size, energy_cols, int(two_stage), int(layer_map), sample_steps,
                        int(model.layer_steps) if two_stage else 0, sample_offset, int(model.noise_seed), D + 1 if layer_map else 0, 0)
     meta += name.ljust(64, b"\0")
-    sections = [(TAG_META, meta), (TAG_REVNORM, _pad(rev, 80))] + sections
+    sections = [(TAG_META, meta), (TAG_REVNORM, _pad(rev, 80 if geom is None else 16))] + sections
+    if geom is not None:
+        sections.append((TAG_GEOM, _geom_section(geom[1], geom[0])))
 
     # header, section table, 64-byte aligned sections; the checksum covers everything behind the header
     off = HEADER_BYTES + SECTION_ENTRY_BYTES * len(sections)
@@ -216,7 +306,7 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
         payload += _pad(body, ALIGN)
     rest = _pad(table, ALIGN) + payload
     total = HEADER_BYTES + len(rest)
-    blob = _pad(MAGIC + struct.pack("<IIQQ", FORMAT_VERSION, len(sections), total, fnv1a64(rest)), HEADER_BYTES) + rest
+    blob = _pad(MAGIC + struct.pack("<IIQQ", FORMAT_VERSION if geom is None else FORMAT_VERSION_GEOM, len(sections), total, fnv1a64(rest)), HEADER_BYTES) + rest
     if path is not None:
         with open(path, "wb") as fh:
             fh.write(blob)
@@ -265,10 +355,18 @@ class Generator:
             self._ws = {int(batch): ws}
         return ws
 
-    def run(self, E, layers=None, seed: int = 1234, offset: int = 0, shard=None, normalised: bool = True, workspace=None):
-        """(showers (B, voxels), layers_out (B, 1 + D) or None, next_offset): one cd_generator_run call.  ``E`` (B,) or (B, 1)
-        device tensor of conditioning values (``normalised``) or physical energies; ``shard`` = (first_row, global_batch)."""
-        E = engine._dev32(E, "E").reshape(-1)
+    def run(self, E, layers=None, seed: int = 1234, offset: int = 0, shard=None, normalised: bool = True, workspace=None,
+            sparse_decoding: bool = False, sparse_per_batch: bool = False, decode_seed: int = 1234, decode_offset: int = 0):
+        """(showers (B, voxels), layers_out (B, 1 + D) or None, next_offset): one cd_generator_run_ex call.  ``E`` (B, energy
+        columns) device tensor ((B,) for one column) of conditioning values (``normalised``) or physical energies; ``shard`` =
+        (first_row, global_batch).  An HGCal file (format version 2) returns a fourth value, the next decode offset:
+        ``sparse_decoding`` / ``sparse_per_batch`` are ``generate()``'s, drawn from the decoder's own stream at (``decode_seed``,
+        ``decode_offset``) -- ``Decoder.noise_seed`` / ``noise_offset`` -- and chained over batches like ``offset``."""
+        cols = self.info["energy_columns"]
+        E = engine._dev32(E, "E")
+        if E.numel() % cols or (E.dim() > 1 and E.shape[-1] != cols):
+            raise ValueError(f"E must have shape (batch, {cols}), not {tuple(E.shape)}")
+        E = E.reshape(-1, cols)
         B = E.shape[0]
         if layers is not None:
             layers = engine._dev32(layers, "layers")
@@ -278,8 +376,14 @@ class Generator:
         ws = self.workspace(B) if workspace is None else workspace
         showers = torch.empty((B, self.info["voxels"]), dtype=torch.float32, device=E.device)
         lout = torch.empty((B, self.info["layers"] + 1), dtype=torch.float32, device=E.device) if self.info["takes_layers"] else None
-        nxt = C.c_uint64(0)
-        engine._check(self.lib.cd_generator_run(self.handle, B, E.data_ptr(), int(bool(normalised)), engine._ptr(layers), int(seed),
-                                                int(offset), first, gb, showers.data_ptr(), engine._ptr(lout), C.byref(nxt),
-                                                ws.data_ptr(), ws.numel(), engine._stream()))
+        nxt, dnxt = C.c_uint64(0), C.c_uint64(0)
+        args = engine.CdGeneratorRun(
+            struct_size=C.sizeof(engine.CdGeneratorRun), batch=B, energy=E.data_ptr(), energy_is_normalised=int(bool(normalised)),
+            sparse_mode=(2 if sparse_per_batch else 1) if sparse_decoding else 0, layers=engine._ptr(layers), seed=int(seed),
+            offset=int(offset), first_row=first, global_batch=gb, showers=showers.data_ptr(), layers_out=engine._ptr(lout),
+            next_offset=C.pointer(nxt), decode_seed=int(decode_seed), decode_offset=int(decode_offset),
+            next_decode_offset=C.pointer(dnxt), workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=engine._stream())
+        engine._check(self.lib.cd_generator_run_ex(self.handle, C.byref(args)))
+        if self.info["format_version"] >= FORMAT_VERSION_GEOM:
+            return showers, lout, int(nxt.value), int(dnxt.value)
         return showers, lout, int(nxt.value)

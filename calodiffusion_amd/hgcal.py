@@ -34,6 +34,28 @@ def _to_dev32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(device="cuda", dtype=torch.float32).contiguous()
 
 
+def map_entries(mat, mask=None):
+    """The sparse entries of a dense map (L, rows, cols), host or device tensor: per-layer CSR (row_ptr (L * rows + 1,) int32,
+    col_idx, val) over the pattern ``mask != 0`` -- or ``mat != 0`` without one -- columns ascending within a row: the arrays
+    ``cd_geom_create_ex`` packs on the device, formed on the host a layer at a time (the generator file's exporter; needs no GPU)."""
+    mat = torch.as_tensor(mat).detach()
+    L, rows, _ = (int(v) for v in mat.shape)
+    if mask is not None and tuple(torch.as_tensor(mask).shape) != tuple(mat.shape):
+        raise ValueError(f"geometry map: mask {tuple(torch.as_tensor(mask).shape)} must have the map's shape {tuple(mat.shape)}")
+    counts, cols, vals = np.zeros(L * rows + 1, dtype=np.int64), [], []
+    for l in range(L):
+        m = mat[l].to("cpu", torch.float32)
+        pat = (m != 0) if mask is None else (torch.as_tensor(mask)[l].to("cpu") != 0)
+        r, c = torch.nonzero(pat, as_tuple=True)  # row-major: rows ascending, columns ascending within a row
+        counts[1 + l * rows: 1 + (l + 1) * rows] = np.bincount(r.numpy(), minlength=rows)
+        cols.append(c.numpy().astype(np.int32))
+        vals.append(m[r, c].numpy())
+    row_ptr = np.cumsum(counts)
+    if row_ptr[-1] >= 2 ** 31:
+        raise ValueError("geometry map: 2^31 or more entries")
+    return row_ptr.astype(np.int32), np.concatenate(cols), np.concatenate(vals).astype(np.float32)
+
+
 class _PackedMap:
     """Owner of one CdGeomMap handle.  ``mask``: the pattern of a trainable map (``dense`` then holds the values, read at the
     masked entries only; see ``refresh``); without one the pattern is ``dense != 0``."""
@@ -52,6 +74,27 @@ class _PackedMap:
         engine._check(self._lib.cd_geom_create_ex(dense.data_ptr(), engine._ptr(pattern), self.layers, self.rows, self.cols, flags,
                                                   C.byref(handle), engine._stream()))
         self.handle = handle
+
+    @classmethod
+    def from_entries(cls, row_ptr, col_idx, val, layers: int, rows: int, cols: int, want_columns: bool = False,
+                     want_transposed: bool = True):
+        """The same handle from the map's sparse entries (``map_entries``), without the dense tensor: ``cd_geom_create_csr``."""
+        self = cls.__new__(cls)
+        self.layers, self.rows, self.cols = int(layers), int(rows), int(cols)
+        self._lib = engine.load_library()
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        col_idx, val = np.ascontiguousarray(col_idx, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float32)
+        if row_ptr.shape != (self.layers * self.rows + 1,) or col_idx.shape != val.shape or col_idx.ndim != 1:
+            raise ValueError(f"geometry map: row_ptr must hold layers * rows + 1 = {self.layers * self.rows + 1} entries and col_idx / "
+                             "val one per entry")
+        if col_idx.size < max(int(row_ptr[-1]), 0):
+            raise ValueError(f"geometry map: row_ptr ends at {int(row_ptr[-1])}, {col_idx.size} entries given")
+        flags = (_GEOM_TRANSPOSED if want_transposed else 0) | (_GEOM_COLUMNS if want_columns else 0)
+        handle = C.c_void_p()
+        engine._check(self._lib.cd_geom_create_csr(row_ptr.ctypes.data, col_idx.ctypes.data, val.ctypes.data, self.layers, self.rows,
+                                                   self.cols, flags, C.byref(handle), engine._stream()))
+        self.handle = handle
+        return self
 
     def __del__(self):
         if getattr(self, "handle", None):

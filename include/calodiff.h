@@ -335,6 +335,17 @@ int cd_geom_destroy(CdGeomMap* map);
 #define CD_GEOM_TRANSPOSED 2
 int cd_geom_create_ex(const float* dense_dev, const float* mask_dev /* nullable */, int layers, int rows, int cols, int flags,
                       CdGeomMap** out, void* stream);
+/* The same map from its sparse entries, without the dense tensor (HGCal's decoders are 56 MB to 2.4 GB dense for 10^5 - 10^6
+ * entries): per-layer CSR in HOST arrays, row_ptr (layers * rows + 1; line l * rows + i holds row i of layer l), col_idx and val
+ * (row_ptr[layers * rows] entries each).  The pattern is taken as given: entries whose value is 0 are kept (a trainable map's mask
+ * has them).  flags as above; CD_GEOM_COLUMNS builds the column view from the entries > 1e-6.  Every array of the handle equals
+ * what cd_geom_create_ex builds from the dense tensor holding these entries (with that pattern as mask_dev if it has zeros), so
+ * every consumer is bitwise unchanged.  Checked on the host before anything is uploaded or launched, CD_EINVAL with a message
+ * otherwise: row_ptr[0] == 0, row_ptr non-decreasing, columns strictly ascending within a row and < cols, values finite.  The views
+ * by column are built on the device from the entries (integer atomics count and place them, then every column is sorted by row:
+ * the result does not depend on thread scheduling); peak memory is O(entries + layers * (rows + cols)).  Synchronises `stream`. */
+int cd_geom_create_csr(const int32_t* row_ptr, const int32_t* col_idx, const float* val, int layers, int rows, int cols, int flags,
+                       CdGeomMap** out, void* stream);
 /* Gathers the packed values again from a dense DEVICE tensor of the map's shape (the live `mat` of a trainable map: call it
  * whenever the parameter changed).  One launch; the pattern and every view stay; the column view, if any, keeps its old values. */
 int cd_geom_refresh(CdGeomMap* map, const float* dense_dev, void* stream);
@@ -606,7 +617,7 @@ int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights
 /* ---- generator: incident energies in, physical showers out, without Python -------------------------------------------
  * A generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file") holds everything
  * Diffusion.generate / LayerDiffusion.generate (calodiffusion/models/diffusion.py:118-197, layerdiffusion.py:171-235) need for one
- * regular-grid model (Dataset 2 / 3, '[layer-]logit-norm'): the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's
+ * model (Dataset 2 / 3 on the regular grid, or HGCal with its geometry maps in the file; '[layer-]logit-norm'): the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's
  * layer model, each stage's compiled sampler (CdStep table or step program) and the inverse pre-processing record.
  * cd_generator_run is the launch sequence of that Python path -- start tensor from the Philox stream, (layer stage,) conditioning
  * row, U-Net sampler, cd_reverse_norm -- with the same stream offsets, so its showers are the ones generate() returns for the same
@@ -618,18 +629,21 @@ int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights
  * message, whatever its bytes.  It allocates the plan (cd_plan_create's device memory) and ONE device block that lives as long as
  * the handle: the layer model's weights (about 3 MB for 45 layers) and its step table or program, each rounded up to 256 bytes;
  * a model without a layer stage has no block.  A staging block of the U-Net's fp32 tensors (the sum of their sizes, each rounded
- * up to 256 bytes) is freed before create returns.  The call synchronises `stream`. */
+ * up to 256 bytes) is freed before create returns.  An HGCal file (format version 2) also gets its geometry maps, built from the
+ * file's sparse entries by cd_geom_create_csr -- the decoder with its column view (pre-embedded), or encoder and decoder with their
+ * transposed views, bound by cd_plan_set_geom (converter inside the model): device memory in proportion to the entries, never the
+ * dense (layers, rows, cols) tensor.  The call synchronises `stream`. */
 typedef struct CdGenerator CdGenerator;
 int cd_generator_create(const void* blob, size_t bytes, CdGenerator** out, void* stream);
 int cd_generator_destroy(CdGenerator* gen);
 /* The file's checksum for code that writes or verifies one: 64-bit FNV-1a of `bytes` bytes of HOST memory (everything behind the
  * 64-byte header).  Host code; touches no device. */
 int cd_generator_checksum(const void* data, size_t bytes, uint64_t* out);
-/* info[8] (host) = {voxels per shower, layers D, energy columns, has layer stage, takes layer energies, sample steps, layer steps
- * (0 without a layer stage), format version}. */
+/* info[8] (host) = {voxels per shower (HGCal: layers x cells), layers D, energy columns, has layer stage, takes layer energies,
+ * sample steps, layer steps (0 without a layer stage), format version}. */
 int cd_generator_info(const CdGenerator* gen, int32_t* info);
 int cd_generator_workspace_bytes(CdGenerator* gen, int batch, size_t* bytes);
-/* energy (batch): the conditioning values e (energy_is_normalised != 0, what a loader of the Python path yields) or physical
+/* energy (batch, energy columns): the conditioning values e (energy_is_normalised != 0, what a loader of the Python path yields) or physical
  * incident energies in the unit of the config's EMIN / EMAX, mapped in the call as cd_preprocess maps them.  Either way the
  * energies cd_reverse_norm scales by are emin * (emax / emin)^e (logE; emin + (emax - emin) e otherwise) formed from e on the
  * device, the power correctly rounded to fp32 (numpy's float32 power, which the Python path takes on the host, may differ from it
@@ -648,6 +662,39 @@ int cd_generator_workspace_bytes(CdGenerator* gen, int batch, size_t* bytes);
 int cd_generator_run(CdGenerator* gen, int batch, const float* energy, int energy_is_normalised, const float* layers /* nullable */,
                      uint64_t seed, uint64_t offset, int first_row, int global_batch, float* showers, float* layers_out /* nullable */,
                      uint64_t* next_offset /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same run for every generator file, HGCal's (format version 2) included; cd_generator_run is this call with sparse_mode 0.
+ * An HGCal file carries its geometry maps, and the run ends as ReverseNormHGCal does: cd_reverse_norm_staged stage 1, for a
+ * pre-embedded model (form 0) the decode onto the cells -- cd_geom_apply with the converter's norm, or with sparse_mode != 0
+ * cd_geom_decode_sparse on the decoder's own Philox stream -- and stage 2; a model with the converter inside (form 1) samples the
+ * cells themselves.  energy is (batch, energy columns of cd_generator_info), showers (batch, layers * cells).  Physical energies
+ * (energy_is_normalised == 0) map per column as cd_preprocess_hgcal maps them; stage 2 scales by
+ * (float)(emin[0] + (emax[0] - emin[0]) * (double)e[0]).
+ * sparse_mode: 0 plain decode, 1 sampled per shower, 2 sampled per batch (one selection serves the batch); != 0 needs a file
+ * whose decoder has a column view (form 0), CD_EINVAL otherwise.  decode_seed / decode_offset: the position in the decoder's
+ * stream (Decoder.noise_seed / noise_offset); *next_decode_offset (HOST, nullable) = decode_offset + (batch, or 1 per batch)
+ * * layers * cells * grid bins, so chained calls draw what one decode of the concatenated batches draws.
+ * (Tag and typedef are declared apart because the struct holds pointers, as CdHlfDesc.) */
+struct CdGeneratorRun {
+  uint32_t struct_size;         /* = sizeof(CdGeneratorRun) */
+  int32_t batch;
+  const float* energy;          /* DEVICE (batch, energy columns) */
+  int32_t energy_is_normalised;
+  int32_t sparse_mode;
+  const float* layers;          /* DEVICE (batch, 1 + layers), nullable: as cd_generator_run */
+  uint64_t seed, offset;
+  int32_t first_row, global_batch;
+  float* showers;               /* DEVICE (batch, voxels) */
+  float* layers_out;            /* DEVICE (batch, 1 + layers), nullable */
+  uint64_t* next_offset;        /* HOST, nullable */
+  uint64_t decode_seed, decode_offset;
+  uint64_t* next_decode_offset; /* HOST, nullable */
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+typedef struct CdGeneratorRun CdGeneratorRun;
+int cd_generator_run_ex(CdGenerator* gen, const CdGeneratorRun* args);
 
 /* ---- shower observables: the CaloChallenge high-level features -------------------------------------------------------
  * HighLevelFeatures.CalculateFeatures of the reference (calodiffusion/utils/HighLevelFeatures.py:48-89) over the voxel positions

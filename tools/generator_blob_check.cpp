@@ -36,5 +36,13 @@ int main(int argc, char** argv) {
   if (blob.meta.has_layer_stage)
     std::printf("  layer model: %zu tensors, sampler %s, %d steps\n", blob.layer.weights.size(),
                 blob.layer_sampler.kind ? "program" : "table", blob.layer_sampler.n_steps);
+  if (blob.geom.form >= 0) {
+    const cdgen::Geom& g = blob.geom;
+    std::printf("  geometry: form %d (%s), bins (%d, %d, %d), %d cells a layer, embed_mean %g, embed_std %g, %d energy columns\n", g.form,
+                g.form ? "in-model" : "pre-embedded", g.layers, g.alpha, g.r, g.cells, g.embed_mean, g.embed_std, blob.rev.energy_cols);
+    if (g.form == 1)
+      std::printf("  encoder: %d x %d a layer, %d entries%s\n", g.enc.rows, g.enc.cols, g.enc.nnz, g.enc.is_mask ? " (a mask's pattern)" : "");
+    std::printf("  decoder: %d x %d a layer, %d entries%s\n", g.dec.rows, g.dec.cols, g.dec.nnz, g.dec.is_mask ? " (a mask's pattern)" : "");
+  }
   return 0;
 }
