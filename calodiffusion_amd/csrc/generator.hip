@@ -1,8 +1,8 @@
 // cd_generator_*: "incident energies in, physical showers out" from a generator file (generator_blob.h), without Python.
 // The run is the launch sequence of Diffusion.generate / LayerDiffusion.generate, issued through the library's own entry points
 // (cd_randn, cd_layer_sample / cd_layer_sampler_run, cd_ddim_sample / cd_sampler_run, cd_reverse_norm; for an HGCal file
-// cd_reverse_norm_staged around cd_geom_apply / cd_geom_decode_sparse, ReverseNormHGCal's tail) with the Philox offsets the Python
-// path hands them; the kernels of its own are the conditioning row and the sampled decode's input scaling.
+// cd_reverse_norm_staged around cd_geom_apply / cd_geom_decode_sparse, ReverseNormHGCal's tail; for a Dataset-0/1 file
+// cd_reverse_norm_ds1 over the file's radial map) with the Philox offsets the Python path hands them; the kernels of its own are the conditioning row and the sampled decode's input scaling.
 #include "arena.h"
 #include "energy_map.h"
 #include "generator_blob.h"
@@ -116,11 +116,17 @@ struct CdGenerator {
   cdgen::RevNorm rev;
   uint32_t version = 0;
   int64_t voxels = 0;  // of a shower as the run returns it
-  int64_t per = 0;     // of the sampler's state: the grid, or the cells of an in-model HGCal file
+  int64_t per = 0;     // of the sampler's state: the grid, the cells of an in-model HGCal file, the flat shower of an in-model Dataset-0/1 file
   // HGCal (format version 2): form -1 none, 0 pre-embedded (dec with its column view), 1 in-model (enc, dec bound to the plan)
   int form = -1, cells = 0;
   float embed_mean = 0.f, embed_std = 1.f;
   CdGeomMap *enc = nullptr, *dec = nullptr;
+  // Dataset 0 / 1 (format version 3): rform -1 none, 0 on the converted grid (r_dec = the un-conversion matrices, the run's last
+  // step reads them), 1 in-model (r_enc, r_dec bound to the plan); both in the one block r_block
+  int rform = -1;
+  CdRadialMap* rmap = nullptr;
+  char* r_block = nullptr;
+  const float *r_enc = nullptr, *r_dec = nullptr;
   CdPlan* plan = nullptr;
   CdLayerMlpDesc ldesc{};
   Stage unet, layer;
@@ -135,6 +141,8 @@ struct CdGenerator {
     if (plan) (void)cd_plan_destroy(plan);  // (before the maps it reads)
     if (enc) (void)cd_geom_destroy(enc);
     if (dec) (void)cd_geom_destroy(dec);
+    if (rmap) (void)cd_radial_destroy(rmap);
+    if (r_block) (void)hipFree(r_block);
     if (block) (void)hipFree(block);
   }
 };
@@ -245,6 +253,33 @@ CdGeomMap* load_geom_map(const cdgen::GeomMap& m, int layers, int flags, hipStre
   return out;
 }
 
+// The RADL section onto the device: the layout through cd_radial_create (which checks it again), the matrices into one block.  The
+// file's arrays may be unaligned, so they are copied out first.
+void load_radial(CdGenerator* g, const cdgen::Radial& r, hipStream_t s) {
+  const size_t L = (size_t)r.layers, wt = (size_t)r.wtotal;
+  std::vector<int32_t> bound(L + 1), alpha(L), rin(L);
+  memcpy(bound.data(), r.bound, bound.size() * sizeof(int32_t));
+  memcpy(alpha.data(), r.alpha, alpha.size() * sizeof(int32_t));
+  memcpy(rin.data(), r.rin, rin.size() * sizeof(int32_t));
+  call(cd_radial_create(r.layers, bound.data(), alpha.data(), rin.data(), r.alpha_out, r.r_out, &g->rmap, s));
+  const size_t one = aligned(wt * sizeof(float));
+  std::vector<float> host((size_t)r.n_mats * wt);
+  if (r.form == 1) memcpy(host.data(), r.enc, wt * sizeof(float));
+  memcpy(host.data() + (size_t)(r.n_mats - 1) * wt, r.dec, wt * sizeof(float));
+  CD_HIP(hipMalloc((void**)&g->r_block, (size_t)r.n_mats * one));
+  for (int k = 0; k < r.n_mats; ++k)
+    CD_HIP(hipMemcpyAsync(g->r_block + (size_t)k * one, host.data() + (size_t)k * wt, wt * sizeof(float), hipMemcpyHostToDevice, s));
+  CD_HIP(hipStreamSynchronize(s));  // the host copy may go
+  g->rform = r.form;
+  g->r_dec = (const float*)(g->r_block + (size_t)(r.n_mats - 1) * one);
+  g->voxels = r.voxels;
+  if (r.form == 1) {
+    g->r_enc = (const float*)g->r_block;
+    g->per = r.voxels;
+    call(cd_plan_set_radial(g->plan, g->rmap, g->r_enc, g->r_dec, 0, s));
+  }
+}
+
 // the caller's workspace, dealt in one fixed order by the dry run and by every call
 struct RunBuffers {
   float *start, *x, *cond, *e_norm, *e_phys, *lstart, *lout, *lnoise;
@@ -318,6 +353,7 @@ int cd_generator_create(const void* blob, size_t bytes, CdGenerator** out, void*
         call(cd_plan_set_geom(g->plan, g->enc, g->dec, 0, s));
       }
     }
+    if (view.radial.form >= 0) load_radial(g.get(), view.radial, s);
     if (view.meta.has_layer_stage) {
       g->layer.take(view.layer_sampler);
       load_layer(g.get(), view.layer, s);
@@ -344,6 +380,16 @@ int cd_generator_info(const CdGenerator* gen, int32_t* info) {
     const int32_t v[8] = {(int32_t)gen->voxels, gen->rev.dims[0], m.energy_cols, m.has_layer_stage, m.takes_layers, m.sample_steps,
                           m.has_layer_stage ? m.layer_steps : 0, (int32_t)gen->version};
     memcpy(info, v, sizeof(v));
+  });
+}
+
+int cd_generator_geometry(const CdGenerator* gen, int32_t* geom) {
+  return guarded([&] {
+    CD_REQUIRE(gen && geom, "null argument");
+    const cdgen::Meta& m = gen->meta;
+    const int32_t v[8] = {gen->form >= 0 ? 1 : gen->rform >= 0 ? 2 : 0, gen->form >= 0 ? gen->form : gen->rform, m.data_ndim,
+                          m.data_shape[0], m.data_shape[1], m.data_shape[2], m.data_shape[3], 0};
+    memcpy(geom, v, sizeof(v));
   });
 }
 
@@ -375,7 +421,7 @@ int cd_generator_run_ex(CdGenerator* gen, const CdGeneratorRun* args) {
     CD_REQUIRE(args->sparse_mode >= 0 && args->sparse_mode <= 2, "cd_generator_run_ex: sparse_mode is 0 (plain decode), 1 (per shower) or 2 (per batch)");
     CD_REQUIRE(args->sparse_mode == 0 || (gen->form == 0 && gen->dec && gen->dec->col_ptr),
                "cd_generator_run_ex: sparse_mode != 0 needs a file whose decoder has a column view (a pre-embedded HGCal model's): this "
-               "file has no decode step");
+               "file has no sampled decode step");
     const bool given_layers = m.takes_layers && !m.has_layer_stage;
     CD_REQUIRE(!given_layers || layers, "cd_generator_run: this model conditions on layer energies and has no layer stage: `layers` "
                                         "(batch, 1 + layers) is required");
@@ -445,7 +491,12 @@ int cd_generator_run_ex(CdGenerator* gen, const CdGeneratorRun* args) {
     off += m.has_layer_stage ? B * per * (uint64_t)m.sample_steps : gb * per * (uint64_t)st.h.noise_tensors_drawn;
 
     uint64_t decode_next = args->decode_offset;
-    if (gen->form < 0) {
+    if (gen->rform >= 0) {
+      // ReverseNormCaloChall for Dataset 0 / 1: the flat form with the layer energies (in-model), the grid form through the
+      // un-conversion matrices
+      call(cd_reverse_norm_ds1(gen->rmap, gen->rform == 0 ? gen->r_dec : nullptr, b.x, b.e_phys, r.layer_map ? layer_e : nullptr, showers,
+                               batch, r.consts64, r.max_deposit, r.ecut, s));
+    } else if (gen->form < 0) {
       call(cd_reverse_norm(b.x, b.e_phys, r.layer_map ? layer_e : nullptr, showers, batch, r.dims, r.consts, r.max_deposit, r.ecut, s));
     } else {
       // ReverseNormHGCal: stage 1 on the sampler's output (the start tensor's block is free again), the decode of a pre-embedded

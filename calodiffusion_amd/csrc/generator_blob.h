@@ -1,5 +1,6 @@
 // Reader of the generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file"), format
-// versions 1 (regular grids) and 2 (HGCal: a GEOM section with the geometry maps by their sparse entries).
+// versions 1 (regular grids), 2 (HGCal: a GEOM section with the geometry maps by their sparse entries) and 3 (Dataset 0 / 1: a
+// RADL section with the irregular layout as cd_radial_create takes it and the matrices in cd_radial_enc / cd_radial_dec layout).
 // Pure C++17, no HIP: cd_generator_create (generator.hip) and tools/generator_blob_check.cpp share it.
 //
 // parse() validates everything before anything is dereferenced: magic, version, total length, checksum, every section's
@@ -22,19 +23,23 @@ namespace cdgen {
 constexpr char kMagic[8] = {'C', 'D', 'G', 'E', 'N', 'B', 'L', 'B'};
 constexpr uint32_t kVersion = 1;      // regular-grid files
 constexpr uint32_t kVersionGeom = 2;  // HGCal files: a GEOM section, per-column EMAX / EMIN in RNRM
+constexpr uint32_t kVersionRadial = 3;  // Dataset-0/1 files: a RADL section, the float64 constants of cd_reverse_norm_ds1 in RNRM
 constexpr uint64_t kHeaderBytes = 64, kSectionEntryBytes = 24, kAlign = 64;
 constexpr uint64_t kStepBytes = 16, kOpBytes = 40;  // sizeof(CdStep), sizeof(CdSamplerOp): generator.hip asserts both
 constexpr uint64_t kWeightRecordBytes = 112, kWeightNameBytes = 96;
 constexpr uint64_t kNetHeaderBytes = 32, kSamplerHeaderBytes = 64, kMetaBytes = 128, kRevNormBytes = 80;
 constexpr uint64_t kRevNormGeomBytes = 96, kGeomHeaderBytes = 64, kGeomMapHeaderBytes = 64;  // version 2
 constexpr int32_t kMaxEnergyCols = 8;                                                         // cd_preprocess_hgcal's limit
+constexpr uint64_t kRevNormRadialBytes = 128, kRadialHeaderBytes = 64;                        // version 3
+// cd_radial_create's on-chip limits (include/calodiff.h, "Dataset-1 radial maps")
+constexpr int32_t kRadialMaxLayers = 64, kRadialMaxWeightFloats = 8192, kRadialMaxRowFloats = 6144;
 
 constexpr uint32_t fourcc(char a, char b, char c, char d) {
   return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
 }
 constexpr uint32_t kTagMeta = fourcc('M', 'E', 'T', 'A'), kTagUnet = fourcc('U', 'N', 'E', 'T'), kTagLayer = fourcc('L', 'A', 'Y', 'R'),
                    kTagUnetSampler = fourcc('U', 'S', 'M', 'P'), kTagLayerSampler = fourcc('L', 'S', 'M', 'P'),
-                   kTagRevNorm = fourcc('R', 'N', 'R', 'M'), kTagGeom = fourcc('G', 'E', 'O', 'M');
+                   kTagRevNorm = fourcc('R', 'N', 'R', 'M'), kTagGeom = fourcc('G', 'E', 'O', 'M'), kTagRadial = fourcc('R', 'A', 'D', 'L');
 
 inline uint64_t fnv1a64(const unsigned char* p, uint64_t n) {
   uint64_t h = 0xcbf29ce484222325ull;
@@ -90,6 +95,8 @@ struct RevNorm {
   int32_t energy_cols = 1;
   float alpha = 0, layer_eps = 0;  // cd_reverse_norm_staged's
   double emax_col[kMaxEnergyCols] = {0}, emin_col[kMaxEnergyCols] = {0};
+  // version 3 (Dataset 0 / 1): cd_reverse_norm_ds1's constants, float64 as postprocess.DATASET1_PARAMS holds them
+  double consts64[6] = {0, 0, 0, 0, 0, 0};
 };
 
 // one map of the GEOM section: per-layer CSR over layers * rows lines, little-endian arrays (views, possibly unaligned)
@@ -107,6 +114,17 @@ struct Geom {
   GeomMap enc, dec;
 };
 
+// the RADL section: cd_radial_create's arguments and the matrices, little-endian arrays (views, possibly unaligned)
+struct Radial {
+  int32_t form = -1;  // -1: no RADL section; 0: on the converted grid (the un-conversion matrices); 1: in-model (encoder, decoder)
+  int32_t layers = 0, alpha_out = 0, r_out = 0, voxels = 0, n_mats = 0, wtotal = 0;
+  const unsigned char* bound = nullptr;  // layers + 1 int32
+  const unsigned char* alpha = nullptr;  // layers int32
+  const unsigned char* rin = nullptr;    // layers int32
+  const unsigned char* enc = nullptr;    // form 1: wtotal fp32 in cd_radial_enc's layout
+  const unsigned char* dec = nullptr;    // wtotal fp32 in cd_radial_dec's layout (form 0: GeomConverter.pinv_mats)
+};
+
 struct Blob {
   uint32_t version = 0;
   uint64_t total_bytes = 0, checksum = 0;
@@ -114,6 +132,7 @@ struct Blob {
   Meta meta;
   RevNorm rev;
   Geom geom;
+  Radial radial;
   Net unet, layer;
   Sampler unet_sampler, layer_sampler;
 };
@@ -210,6 +229,57 @@ inline bool parse_geom(const unsigned char* sec, uint64_t size, Geom* g, std::st
   return true;
 }
 
+// RADL: header {form, L, A, R, V, n_mats, wtotal}, then bound[L + 1], alpha[L], rin[L] (int32) and n_mats matrices of wtotal fp32
+// -- the encoder then the decoder (form 1), or the un-conversion matrices (form 0) --, every piece on a 64-byte boundary.  Counts
+// against the section first, then every rule cd_radial_create has, then the values: nothing is uploaded from a file that fails.
+inline bool parse_radial(const unsigned char* sec, uint64_t size, Radial* g, std::string* err) {
+  Cursor c{sec, size, 0};
+  const unsigned char* h;
+  if (!c.take(kRadialHeaderBytes, &h)) return *err = "RADL: section shorter than its header", false;
+  int32_t* f[7] = {&g->form, &g->layers, &g->alpha_out, &g->r_out, &g->voxels, &g->n_mats, &g->wtotal};
+  for (int i = 0; i < 7; ++i) *f[i] = rd<int32_t>(h + 4 * i);
+  if (g->form != 0 && g->form != 1) return g->form = -1, *err = "RADL: unknown form (0: on the converted grid, 1: in-model)", false;
+  if (g->n_mats != g->form + 1) return *err = "RADL: form 0 holds one set of matrices (the un-conversion), form 1 two (encoder, decoder)", false;
+  const int32_t L = g->layers, A = g->alpha_out, R = g->r_out;
+  if (L < 1 || L > kRadialMaxLayers) return *err = "RADL: 1 to " + std::to_string(kRadialMaxLayers) + " layers (cd_radial_create's limit)", false;
+  if (A < 1 || R < 1 || A > kRadialMaxRowFloats || R > kRadialMaxRowFloats || (int64_t)L * A * R > kRadialMaxRowFloats)
+    return *err = "RADL: layers * alpha_out * r_out must be 1 to " + std::to_string(kRadialMaxRowFloats) + " (cd_radial_create's limit)", false;
+  if (g->voxels < 1 || g->voxels > kRadialMaxRowFloats)
+    return *err = "RADL: 1 to " + std::to_string(kRadialMaxRowFloats) + " voxels (cd_radial_create's limit)", false;
+  if (g->wtotal < 1 || g->wtotal > kRadialMaxWeightFloats)
+    return *err = "RADL: the matrices hold 1 to " + std::to_string(kRadialMaxWeightFloats) + " floats (cd_radial_create's limit)", false;
+  if (!c.take_array((uint64_t)L + 1, 4, &g->bound)) return *err = "RADL: bound overflows the section", false;
+  c.align(kAlign);
+  if (!c.take_array((uint64_t)L, 4, &g->alpha)) return *err = "RADL: alpha overflows the section", false;
+  c.align(kAlign);
+  if (!c.take_array((uint64_t)L, 4, &g->rin)) return *err = "RADL: rin overflows the section", false;
+  c.align(kAlign);
+  int64_t sum_rin = 0;
+  if (rd<int32_t>(g->bound) != 0) return *err = "RADL: bound[0] is not 0", false;
+  for (int i = 0; i < L; ++i) {
+    const int32_t lo = rd<int32_t>(g->bound + 4 * i), hi = rd<int32_t>(g->bound + 4 * (i + 1));
+    const int32_t a = rd<int32_t>(g->alpha + 4 * i), n = rd<int32_t>(g->rin + 4 * i);
+    const std::string lay = "RADL: layer " + std::to_string(i);
+    if (hi <= lo) return *err = lay + ": bound is not strictly increasing", false;
+    if (a != 1 && a != A) return *err = lay + ": alpha is " + std::to_string(a) + ", a layer has 1 or alpha_out angular bins", false;
+    if (n < 1 || n > kRadialMaxRowFloats) return *err = lay + ": radial bin count out of range", false;
+    if ((int64_t)hi - lo != (int64_t)a * n) return *err = lay + ": its span is not alpha * rin voxels", false;
+    sum_rin += n;
+  }
+  if (rd<int32_t>(g->bound + 4 * L) != g->voxels) return *err = "RADL: the voxel count is not bound[layers]", false;
+  if ((int64_t)R * sum_rin != (int64_t)g->wtotal) return *err = "RADL: the matrices' size is not r_out * sum of rin", false;
+  for (int k = 0; k < g->n_mats; ++k) {
+    const bool is_enc = g->form == 1 && k == 0;
+    const unsigned char** m = is_enc ? &g->enc : &g->dec;
+    const std::string what = is_enc ? "RADL encoder" : g->form == 1 ? "RADL decoder" : "RADL un-conversion";
+    if (!c.take_array((uint64_t)g->wtotal, 4, m)) return *err = what + ": " + std::to_string(g->wtotal) + " values overflow the section", false;
+    c.align(kAlign);
+    for (int32_t i = 0; i < g->wtotal; ++i)
+      if (!std::isfinite(rd<float>(*m + 4 * (uint64_t)i))) return *err = what + ": value " + std::to_string(i) + " is not finite", false;
+  }
+  return true;
+}
+
 inline bool parse_net(const unsigned char* sec, uint64_t size, const char* what, bool with_coords, Net* net, std::string* err) {
   Cursor c{sec, size, 0};
   const unsigned char* h;
@@ -292,10 +362,10 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   if (bytes < kHeaderBytes) return *err = "generator file: shorter than its 64-byte header", false;
   if (memcmp(p, kMagic, 8) != 0) return *err = "generator file: wrong magic (not a generator file)", false;
   out->version = rd<uint32_t>(p + 8);
-  if (out->version != kVersion && out->version != kVersionGeom)
+  if (out->version != kVersion && out->version != kVersionGeom && out->version != kVersionRadial)
     return *err = "generator file: format version " + std::to_string(out->version) + ", this reader knows versions " + std::to_string(kVersion) +
-                  " and " + std::to_string(kVersionGeom), false;
-  const bool v2 = out->version == kVersionGeom;
+                  ", " + std::to_string(kVersionGeom) + " and " + std::to_string(kVersionRadial), false;
+  const bool v2 = out->version == kVersionGeom, v3 = out->version == kVersionRadial;
   const uint32_t n_sections = rd<uint32_t>(p + 12);
   out->total_bytes = rd<uint64_t>(p + 16);
   out->checksum = rd<uint64_t>(p + 24);
@@ -325,9 +395,12 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   const Section* sus = find_section(*out, kTagUnetSampler);
   const Section* sg = find_section(*out, kTagGeom);
   if (v2 && !sg) return *err = "generator file: format version 2 must have a GEOM section (a version-1 payload under a version-2 header?)", false;
-  if (!v2 && sg) return *err = "generator file: a GEOM section in a format version 1 file", false;
+  if (!v2 && sg) return *err = "generator file: a GEOM section in a format version " + std::to_string(out->version) + " file", false;
+  const Section* sd = find_section(*out, kTagRadial);
+  if (v3 && !sd) return *err = "generator file: format version 3 must have a RADL section (another version's payload under a version-3 header?)", false;
+  if (!v3 && sd) return *err = "generator file: a RADL section in a format version " + std::to_string(out->version) + " file", false;
   if (!sm || !sr || !su || !sus) return *err = "generator file: a required section (META, RNRM, UNET, USMP) is missing", false;
-  if (sr->bytes < (v2 ? kRevNormGeomBytes : kRevNormBytes)) return *err = "RNRM: section shorter than its record", false;
+  if (sr->bytes < (v2 ? kRevNormGeomBytes : v3 ? kRevNormRadialBytes : kRevNormBytes)) return *err = "RNRM: section shorter than its record", false;
   if (sm->bytes < kMetaBytes) return *err = "META: section shorter than its record", false;
 
   Meta& m = out->meta;
@@ -371,6 +444,15 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
     r.energy_cols = 1;
     r.emax_col[0] = r.emax; r.emin_col[0] = r.emin;
   }
+  if (v3) {
+    for (int i = 0; i < 6; ++i) {
+      r.consts64[i] = rd<double>(q + kRevNormBytes + 8 * i);
+      if (!std::isfinite(r.consts64[i])) return *err = "RNRM: a constant of the Dataset-0/1 map is not finite", false;
+    }
+    if (r.consts64[1] == 0 || r.consts64[3] == 0 || r.consts64[5] == 0) return *err = "RNRM: a scale of the Dataset-0/1 map is 0", false;
+    if (!std::isfinite(r.ecut) || r.ecut < 0) return *err = "RNRM: ECUT must be finite and not negative", false;
+    if (!parse_radial(p + sd->off, sd->bytes, &out->radial, err)) return false;
+  }
 
   // the records against each other
   uint64_t vox = 1;
@@ -381,14 +463,20 @@ inline bool parse(const void* blob, size_t bytes, Blob* out, std::string* err) {
   if (vox > (1ull << 28)) return *err = "RNRM: more than 2^28 voxels", false;
   const Geom& g = out->geom;
   if (v2 && (g.layers != r.dims[0] || g.alpha != r.dims[1] || g.r != r.dims[2])) return *err = "GEOM: its bins are not the RNRM grid", false;
+  const Radial& rad = out->radial;
+  if (v3 && (rad.layers != r.dims[0] || rad.alpha_out != r.dims[1] || rad.r_out != r.dims[2])) return *err = "RADL: its grid is not the RNRM grid", false;
+  if (v3 && rad.form == 0 && r.layer_map)
+    return *err = "RNRM: a 'layer' map on the converted Dataset-0/1 grid is not provided (cd_reverse_norm_ds1's grid form takes no layer energies)", false;
   if (v2 && g.form == 1) {
     if (m.data_ndim != 3 || m.data_shape[0] != 1 || m.data_shape[1] != g.layers || m.data_shape[2] != g.cells || m.data_shape[3] != 0)
       return *err = "META: the data shape of an in-model file is not (1, L, N) of its GEOM section", false;
-    if (m.has_layer_stage) return *err = "META: a layer stage over an in-model embedding is not provided", false;
+  } else if (v3 && rad.form == 1) {
+    if (m.data_ndim != 1 || m.data_shape[0] != rad.voxels || m.data_shape[1] != 0 || m.data_shape[2] != 0 || m.data_shape[3] != 0)
+      return *err = "META: the data shape of an in-model Dataset-0/1 file is not (V,) of its RADL section", false;
   } else if (m.data_ndim != 4 || m.data_shape[0] != 1 || m.data_shape[1] != r.dims[0] || m.data_shape[2] != r.dims[1] || m.data_shape[3] != r.dims[2]) {
     return *err = "META: the data shape is not (1, D, H, W) of the RNRM grid", false;
   }
-  if (!v2 && m.energy_cols != 1) return *err = "META: one incident-energy column is the only form of format version 1", false;
+  if (!v2 && m.energy_cols != 1) return *err = "META: one incident-energy column is the only form of format versions 1 and 3", false;
   if (m.sample_steps < 1 || m.sample_steps > (1 << 20) || m.sample_offset < 0 || m.layer_steps < 0 || m.layer_steps > (1 << 20))
     return *err = "META: step counts out of range", false;
   if ((m.takes_layers != 0) != (r.layer_map != 0)) return *err = "META: takes_layers disagrees with the shower map", false;

@@ -161,6 +161,7 @@ _SIGNATURES = {
     "cd_generator_destroy": (C.c_int, [_P]),
     "cd_generator_checksum": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "cd_generator_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "cd_generator_geometry": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "cd_generator_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_generator_run": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64),
                                    _P, C.c_size_t, _P]),

@@ -9,7 +9,10 @@ tools/cd_generate_example.c the same from C.
 
 Scope: DATASET_NUM 2 / 3 (format version 1) and HGCal (format version 2, whose ``GEOM`` section carries the geometry maps by
 their sparse entries: the decoder of a pre-embedded model's ``geometry=`` converter, or both maps of a model with the converter
-inside) with a ``[layer-]logit-norm`` map, any width the plan takes, any sampler that compiles to a CdStep table or to a step
+inside) and Dataset 0 / 1 (format version 3, whose ``RADL`` section carries the irregular layout as ``cd_radial_create`` takes it and
+the matrices in ``cd_radial_enc`` / ``cd_radial_dec`` layout: encoder and decoder of a model with SHOWER_EMBED 'orig-NN', or the
+un-conversion matrices of the ``geometry=`` converter of a model on the converted grid) with a ``[layer-]logit-norm`` map, any
+width the plan takes, any sampler that compiles to a CdStep table or to a step
 program that does not depend on the batch.  Everything else is refused at export, by name.
 """
 from __future__ import annotations
@@ -17,7 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -27,11 +30,13 @@ from . import engine
 MAGIC = b"CDGENBLB"
 FORMAT_VERSION = 1       # regular-grid files: written as they always were, byte for byte
 FORMAT_VERSION_GEOM = 2  # HGCal files: a GEOM section, energy columns, per-column EMAX / EMIN in RNRM
+FORMAT_VERSION_RADIAL = 3  # Dataset-0/1 files: a RADL section, the float64 constants of cd_reverse_norm_ds1 in RNRM
 STAGED_ALPHA = STAGED_LAYER_EPS = 1e-8  # ReverseNormHGCal's reverse_logit alpha and layer threshold (postprocess.py)
 HEADER_BYTES, SECTION_ENTRY_BYTES, ALIGN = 64, 24, 64
 WEIGHT_RECORD_BYTES, WEIGHT_NAME_BYTES = 112, 96
 TAG_META, TAG_UNET, TAG_LAYER, TAG_UNET_SAMPLER, TAG_LAYER_SAMPLER, TAG_REVNORM = b"META", b"UNET", b"LAYR", b"USMP", b"LSMP", b"RNRM"
 TAG_GEOM = b"GEOM"
+TAG_RADIAL = b"RADL"
 
 
 def fnv1a64(data: bytes) -> int:
@@ -210,27 +215,91 @@ def _hgcal_form(model, geometry):
     return form, conv
 
 
+class _Radial(NamedTuple):
+    """What a Dataset-0/1 file carries of its geometry (``_radial_form``)."""
+    form: int    # 0 on the converted grid, 1 in-model
+    gc: object   # the geom1.GeomConverter: the layout
+    mats: list   # form 1: [encoder, decoder]; form 0: [un-conversion], each the flat fp32 concatenation over the layers
+
+
+def _radial_section(gc, form: int, mats) -> bytes:
+    """RADL: {form, L, alpha_out, r_out, V, n_mats, wtotal}, then bound[L + 1], alpha[L], rin[L] (int32) and the matrices (fp32, each
+    the concatenation cd_radial_enc / cd_radial_dec take), every piece 64-byte aligned."""
+    bound, alpha, rin = gc.descriptor()
+    L, A, R = int(gc.num_layers), int(gc.alpha_out), int(gc.dim_r_out)
+    wtotal = R * sum(rin)
+    mats = [np.ascontiguousarray(m, dtype="<f4").reshape(-1) for m in mats]
+    assert len(mats) == form + 1 and all(m.size == wtotal for m in mats)
+    head = struct.pack("<7i", form, L, A, R, bound[-1], len(mats), wtotal)
+    ints = b"".join(_pad(np.asarray(v, dtype="<i4").tobytes(), 64) for v in (bound, alpha, rin))
+    return _pad(head, 64) + ints + b"".join(_pad(m.tobytes(), 64) for m in mats)
+
+
+def _radial_form(model, geometry):
+    """The ``_Radial`` record of a Dataset-0/1 model, or the refusal by name.  Form 1: SHOWER_EMBED 'orig-NN', the
+    converter inside the model -- its trained encoder and decoder go into the file.  Form 0: a model on the converted grid with the
+    ``geometry=`` converter ``generate(geometry=)`` takes -- its fixed un-conversion matrices (``GeomConverter.pinv_mats``)."""
+    from .geom1 import GeomConverter, NNConverter
+    from .postprocess import refuse_uncovered_ds1
+    cfg = model.config
+    dnum, embed = cfg.get("DATASET_NUM"), cfg.get("SHOWER_EMBED", "")
+    if getattr(model, "do_embed", False):
+        if not isinstance(model.NN_embed, NNConverter) or "orig" not in embed:
+            raise NotImplementedError(f"export_generator: a Dataset-{dnum} model with an in-model embedding (do_embed) other than a "
+                                      "geom1.NNConverter over the flat shower (SHOWER_EMBED 'orig-NN') is not provided")
+        if geometry is not None:
+            raise ValueError(f"export_generator: this Dataset-{dnum} model has its converter inside (do_embed, SHOWER_EMBED 'orig-NN'): "
+                             "the file takes model.NN_embed, geometry= must not be given")
+        pad, final = cfg.get("SHAPE_PAD") or cfg["SHAPE_FINAL"], [int(v) for v in cfg["SHAPE_FINAL"]]
+        if len(pad) < 3 or int(pad[2]) != final[2]:
+            raise NotImplementedError(f"export_generator: Dataset {dnum} with SHAPE_PAD {list(pad)} is not provided: a generator file "
+                                      f"serves CaloDiffusion and LayerDiffusion of one config, and the two-stage model exists for "
+                                      f"SHAPE_PAD = SHAPE_FINAL = {final} only (with 'orig-NN' the state is SHAPE_ORIG either way)")
+        conv = model.NN_embed
+        mats = [torch.cat([lay.weight.detach().reshape(-1) for lay in part]).to("cpu", torch.float32).numpy() for part in (conv.encs, conv.decs)]
+        form, gc = 1, conv.gc
+    else:
+        if "orig" in embed:
+            raise NotImplementedError(f"export_generator: a Dataset-{dnum} model on the flat shower without an in-model converter "
+                                      f"(SHOWER_EMBED {embed!r}) is not provided")
+        if geometry is None:
+            raise NotImplementedError(f"export_generator: Dataset {dnum} on the converted grid needs its irregular geometry in the "
+                                      "file: pass geometry=<geom1.GeomConverter or NNConverter>, what generate(geometry=) takes")
+        if not isinstance(geometry, (GeomConverter, NNConverter)):
+            raise TypeError("export_generator(geometry=) on a Dataset-0/1 config takes a geom1.GeomConverter or NNConverter")
+        refuse_uncovered_ds1("export_generator", cfg.get("SHOWERMAP", ""), False)  # a 'layer' map on the grid: no layerE there
+        form, gc = 0, geometry.gc if isinstance(geometry, NNConverter) else geometry
+        mats = [torch.cat([m.reshape(-1) for m in gc.pinv_mats]).to("cpu", torch.float32).numpy()]
+    grid = tuple(int(v) for v in cfg["SHAPE_FINAL"][2:])
+    have = (int(gc.num_layers), int(gc.alpha_out), int(gc.dim_r_out))
+    if have != grid:
+        raise ValueError(f"export_generator: the converter maps onto (layers, alpha_out, dim_r_out) = {have}, SHAPE_FINAL gives the "
+                         f"U-Net the grid {grid}")
+    return _Radial(form, gc, mats)
+
+
 def _refuse_out_of_scope(model, debug, geometry=None):
-    """Raises for what a generator file does not hold, by name; returns ``_hgcal_form``'s (form, converter), None off HGCal."""
+    """Raises for what a generator file does not hold, by name; returns (``_hgcal_form``'s (form, converter) or None,
+    ``_radial_form``'s record or None): at most one of the two is set."""
     cfg = model.config
     if debug:
         raise NotImplementedError("export_generator: a debug trajectory request is not part of a generator file (cd_generator_run "
                                   "returns showers only)")
-    geom = _hgcal_form(model, geometry)
-    if geom is not None:
-        pass  # (its own checks are _hgcal_form's)
-    elif cfg.get("DATASET_NUM", 2) not in (2, 3):
-        raise NotImplementedError(f"export_generator: Dataset {cfg.get('DATASET_NUM')} is not provided (DATASET_NUM 2 / 3 only): the "
-                                  "irregular geometry would have to be in the file")
-    elif getattr(model, "do_embed", False) or getattr(model, "NN_embed", None) is not None:
-        raise NotImplementedError("export_generator: a model with an in-model geometry embedding (do_embed) is not provided: its "
-                                  "maps would have to be in the file")
+    hgcal = cfg.get("HGCAL", False) or getattr(model, "hgcal", False)
+    radial = _radial_form(model, geometry) if not hgcal and cfg.get("DATASET_NUM", 2) in (0, 1) else None
+    geom = _hgcal_form(model, geometry) if radial is None else None
+    if geom is None and radial is None:  # a regular grid (the two forms above have their own checks)
+        if cfg.get("DATASET_NUM", 2) not in (2, 3):
+            raise NotImplementedError(f"export_generator: Dataset {cfg.get('DATASET_NUM')} is not provided (DATASET_NUM 0 to 3 and HGCal)")
+        if getattr(model, "do_embed", False) or getattr(model, "NN_embed", None) is not None:
+            raise NotImplementedError("export_generator: a model with an in-model geometry embedding (do_embed) is not provided: its "
+                                      "maps would have to be in the file")
     if cfg.get("SHOWERMAP") not in ("layer-logit-norm", "logit-norm"):
         raise NotImplementedError(f"export_generator: SHOWERMAP {cfg.get('SHOWERMAP')!r} is not provided ([layer-]logit-norm only)")
     missing = [k for k in ("EMAX", "EMIN", "logE", "MAXDEP", "ECUT") if k not in cfg]
     if missing:
         raise ValueError(f"export_generator: the config lacks {missing}: the inverse pre-processing record needs them")
-    return geom
+    return geom, radial
 
 
 def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Optional[str] = None, debug: bool = False,
@@ -238,13 +307,17 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
     """The generator file of ``model`` (a ``CaloDiffusion`` or ``LayerDiffusion`` as constructed from its config) for
     ``model.generate(loader, sample_steps, sample_offset=sample_offset)``; also written to ``path`` when given.  ``geometry``: the
     ``hgcal.HGCalConverter`` of a pre-embedded HGCal model, what ``generate(geometry=)`` takes (frozen); an HGCal model with the
-    converter inside writes ``model.NN_embed`` and takes none.  Runs without a GPU and without the library."""
+    converter inside writes ``model.NN_embed`` and takes none.  Dataset 0 / 1: a model with SHOWER_EMBED 'orig-NN' writes
+    ``model.NN_embed`` and takes none; a model on the converted grid takes the ``geom1.GeomConverter`` / ``NNConverter`` of
+    ``generate(geometry=)``.  Runs without a GPU and without the library."""
     from .layerdiffusion import LayerDiffusion
-    from .postprocess import DATASET_PARAMS
-    geom = _refuse_out_of_scope(model, debug, geometry)
+    from .postprocess import DATASET1_PARAMS, DATASET_PARAMS
+    geom, radial = _refuse_out_of_scope(model, debug, geometry)
     cfg = model.config
     sample_steps, sample_offset = int(sample_steps), int(sample_offset or 0)
     two_stage = isinstance(model, LayerDiffusion)
+    if two_stage:
+        model._layer_dim()  # the ValueError that names SHAPE_PAD[2] + 1 != SHAPE_FINAL[2] + 1
     unet = model.base_model if two_stage else model.model
     opts = dict(unet._engine_opts)
     coords = opts.pop("coords")
@@ -254,6 +327,9 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
         cells = int(geom[1].decoder.mat.shape[1])
         if data_shape != [1, D, cells]:
             raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (1, L, N) cell-space shower")
+    elif radial is not None and radial.form == 1:
+        if data_shape != [int(radial.gc.layer_boundaries[-1])]:
+            raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (V,) flat shower of the converter")
     elif data_shape != [1, D, H, W]:
         raise NotImplementedError(f"export_generator: the sampler state {data_shape} is not the (1, D, H, W) grid")
     layer_map = "layer" in cfg["SHOWERMAP"]
@@ -270,11 +346,16 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
     sections += [(TAG_UNET, _net_section(engine.unet_desc(unet, **opts), unet.state_dict(), (r, z, phi))),
                  (TAG_UNET_SAMPLER, _sampler_section(net))]
 
-    c = DATASET_PARAMS[cfg["DATASET_NUM"]]
+    if radial is not None:  # ReverseNormCaloChall's choice: the '+ 10' constants in the original flat shape (utils.py:474-477)
+        c = DATASET1_PARAMS[cfg["DATASET_NUM"] + (10 if radial.form == 1 else 0)]
+    else:
+        c = DATASET_PARAMS[cfg["DATASET_NUM"]]
     if geom is None:
         rev = struct.pack("<6i8f2d", D, H, W, int(layer_map), int(bool(cfg["logE"])), int(cfg["DATASET_NUM"]),
                           c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"],
                           float(cfg["MAXDEP"]), float(cfg["ECUT"]), float(cfg["EMAX"]), float(cfg["EMIN"]))
+    if radial is not None:  # cd_reverse_norm_ds1 takes the constants as float64
+        rev = _pad(rev, 80) + struct.pack("<6d", *(float(c[k]) for k in ("logit_mean", "logit_std", "totalE_mean", "totalE_std", "layers_mean", "layers_std")))
     energy_cols = 1
     if geom is not None:
         # ReverseNormHGCal: np.array(emin) + (np.array(emax) - np.array(emin)) * e over the (B, cols) conditioning values
@@ -293,9 +374,12 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
     meta = struct.pack("<12iQ2i", len(data_shape), *shape4, unet.cond_size, energy_cols, int(two_stage), int(layer_map), sample_steps,
                        int(model.layer_steps) if two_stage else 0, sample_offset, int(model.noise_seed), D + 1 if layer_map else 0, 0)
     meta += name.ljust(64, b"\0")
-    sections = [(TAG_META, meta), (TAG_REVNORM, _pad(rev, 80 if geom is None else 16))] + sections
+    sections = [(TAG_META, meta), (TAG_REVNORM, _pad(rev, 16 if geom is not None else 128 if radial is not None else 80))] + sections
     if geom is not None:
         sections.append((TAG_GEOM, _geom_section(geom[1], geom[0])))
+    if radial is not None:
+        sections.append((TAG_RADIAL, _radial_section(radial.gc, radial.form, radial.mats)))
+    version = FORMAT_VERSION_GEOM if geom is not None else FORMAT_VERSION_RADIAL if radial is not None else FORMAT_VERSION
 
     # header, section table, 64-byte aligned sections; the checksum covers everything behind the header
     off = HEADER_BYTES + SECTION_ENTRY_BYTES * len(sections)
@@ -306,7 +390,7 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
         payload += _pad(body, ALIGN)
     rest = _pad(table, ALIGN) + payload
     total = HEADER_BYTES + len(rest)
-    blob = _pad(MAGIC + struct.pack("<IIQQ", FORMAT_VERSION if geom is None else FORMAT_VERSION_GEOM, len(sections), total, fnv1a64(rest)), HEADER_BYTES) + rest
+    blob = _pad(MAGIC + struct.pack("<IIQQ", version, len(sections), total, fnv1a64(rest)), HEADER_BYTES) + rest
     if path is not None:
         with open(path, "wb") as fh:
             fh.write(blob)
@@ -331,6 +415,11 @@ class Generator:
         info = (C.c_int32 * 8)()
         engine._check(self.lib.cd_generator_info(self.handle, info))
         self.info = dict(zip(self.INFO_KEYS, (int(v) for v in info)))
+        geo = (C.c_int32 * 8)()
+        engine._check(self.lib.cd_generator_geometry(self.handle, geo))
+        # 'geometry': None (a regular grid), 'hgcal' or 'radial' (Dataset 0 / 1); 'form': 0 converted at the end of the run, 1 the
+        # converter inside the model; 'state_shape': the sampler's per-sample state
+        self.geometry = dict(geometry=(None, "hgcal", "radial")[geo[0]], form=int(geo[1]), state_shape=tuple(int(v) for v in geo[3:3 + geo[2]]))
         self._ws = {}
 
     def __del__(self):
@@ -359,7 +448,7 @@ class Generator:
             sparse_decoding: bool = False, sparse_per_batch: bool = False, decode_seed: int = 1234, decode_offset: int = 0):
         """(showers (B, voxels), layers_out (B, 1 + D) or None, next_offset): one cd_generator_run_ex call.  ``E`` (B, energy
         columns) device tensor ((B,) for one column) of conditioning values (``normalised``) or physical energies; ``shard`` =
-        (first_row, global_batch).  An HGCal file (format version 2) returns a fourth value, the next decode offset:
+        (first_row, global_batch).  An HGCal file (format version 2, and no other) returns a fourth value, the next decode offset:
         ``sparse_decoding`` / ``sparse_per_batch`` are ``generate()``'s, drawn from the decoder's own stream at (``decode_seed``,
         ``decode_offset``) -- ``Decoder.noise_seed`` / ``noise_offset`` -- and chained over batches like ``offset``."""
         cols = self.info["energy_columns"]
@@ -384,6 +473,6 @@ class Generator:
             next_offset=C.pointer(nxt), decode_seed=int(decode_seed), decode_offset=int(decode_offset),
             next_decode_offset=C.pointer(dnxt), workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=engine._stream())
         engine._check(self.lib.cd_generator_run_ex(self.handle, C.byref(args)))
-        if self.info["format_version"] >= FORMAT_VERSION_GEOM:
+        if self.info["format_version"] == FORMAT_VERSION_GEOM:
             return showers, lout, int(nxt.value), int(dnxt.value)
         return showers, lout, int(nxt.value)

@@ -22,16 +22,26 @@ from .resnet import ResNet
 class LayerDiffusion(CaloDiffusion):
     def __init__(self, config, n_steps=400, loss_type="l2"):
         from .configs import load_config
-        embed = load_config(config).get("SHOWER_EMBED", "")
-        if load_config(config).get("HGCAL", False) and "pre-embed" not in embed:
+        cfg = load_config(config)
+        embed = cfg.get("SHOWER_EMBED", "")
+        if not cfg.get("HGCAL", False) and "NN" in embed and "orig" in embed and "pre-embed" not in embed:
+            pad, final = cfg.get("SHAPE_PAD") or cfg["SHAPE_FINAL"], [int(v) for v in cfg["SHAPE_FINAL"]]
+            if len(pad) < 3 or int(pad[2]) != final[2]:
+                raise NotImplementedError(f"LayerDiffusion over an in-model geometry embedding (SHOWER_EMBED 'orig-NN') with SHAPE_PAD "
+                                          f"{list(pad)}: the layer stage draws SHAPE_PAD[2] + 1 columns for a layer model of "
+                                          f"SHAPE_FINAL[2] + 1 = {final[2] + 1} inputs (the reference fails in a matmul there), so the "
+                                          f"two-stage model is provided for SHAPE_PAD = SHAPE_FINAL = {final} only (with 'orig-NN' the "
+                                          "U-Net state is SHAPE_ORIG either way); use CaloDiffusion for this form of the config")
+        try:
+            super().__init__(config, n_steps, loss_type)
+        except ImportError as err:
+            if not (cfg.get("HGCAL", False) and "pre-embed" not in embed and cfg.get("NN_EMBED") is None):
+                raise
+            # the converter is built from BIN_FILE as CaloDiffusion builds it; where the geometry file's package is missing, the
+            # two-stage model over it does not exist here: say how to get one
             raise NotImplementedError("LayerDiffusion over HGCal's in-model geometry embedding (HGCalConverter inside forward): the "
-                                      "two-stage sampling and its layer-energy conditioning are not wired to the cell-space state; "
-                                      "use CaloDiffusion for such a config, or its pre-embedded ('...-pre-embed') form")
-        if "NN" in embed and "orig" in embed and "pre-embed" not in embed:
-            raise NotImplementedError("LayerDiffusion over an in-model geometry embedding (SHOWER_EMBED 'orig-NN'): the two-stage "
-                                      "sampling and its layer-energy conditioning are not wired to the flat Dataset-1 state yet; "
-                                      "use CaloDiffusion for such a config")
-        super().__init__(config, n_steps, loss_type)
+                                      f"converter could not be built from BIN_FILE ({err}); pass a built hgcal.HGCalConverter in "
+                                      "config['NN_EMBED']") from err
         self.layer_loss = False
         sampler_algo = self.config.get("LAYER_SAMPLER", "DDim")
         self.layer_sampler = utils.load_attr("sampler", sampler_algo)(self.config)
@@ -58,7 +68,31 @@ class LayerDiffusion(CaloDiffusion):
         self.model = self.layer_model if is_layer else self.base_model
 
     def engine(self):
-        return self.model.engine()
+        """The layer model's engine in the layer state (no geometry embedding is bound to it: the state is the (B, D+1) layer
+        energies); else the U-Net's, with the in-model embedding bound as ``CaloDiffusion.engine`` binds it."""
+        if self.layer_loss:
+            return self.model.engine()
+        return super().engine()
+
+    def _params(self):
+        """In the layer state the layer model's parameters alone take gradients: the embedding is not part of that graph."""
+        if self.layer_loss:
+            return list(self.layer_model.parameters())
+        return super()._params()
+
+    def _layer_dim(self):
+        """Columns of the layer stage's start tensor as the reference draws it, SHAPE_PAD[2] + 1 (layerdiffusion.py:116), checked
+        against the layer model's input SHAPE_FINAL[2] + 1: where they differ the reference dies in the layer model's first matmul.
+        (The shipped Dataset-1 configs, SHAPE_PAD [-1, 1, 368] / [-1, 1, 533], are refused at construction for this reason; this
+        check holds for every other config and for a ``shape_pad`` set after construction.)"""
+        want, have = int(self.config["SHAPE_FINAL"][2]) + 1, int(self.shape_pad[2]) + 1
+        if have != want:
+            final = [int(v) for v in self.config["SHAPE_FINAL"]]
+            raise ValueError(f"LayerDiffusion: SHAPE_PAD[2] + 1 != SHAPE_FINAL[2] + 1 ({have} != {want}): the layer stage would draw "
+                             f"{have} columns for a layer model of {want} inputs (the reference fails in a matmul there); two-stage "
+                             f"sampling needs SHAPE_PAD = SHAPE_FINAL = {final} in the config (with SHOWER_EMBED 'orig-NN' the U-Net "
+                             "state is SHAPE_ORIG either way)")
+        return have
 
     def cond_tensor(self, E, layers):
         if self.layer_loss:  # layer_forward conditions on the incident energy only (layerdiffusion.py:109-112)
@@ -146,10 +180,11 @@ class LayerDiffusion(CaloDiffusion):
     def sample_layers(self, energy, layers=None, debug=False, sample_offset=None, start: Optional[torch.Tensor] = None):
         """layerdiffusion.py:114-132: the (B, D+1) layer energies, one launch for the whole trajectory: DDim / DDPM / Euler
         without churn on cd_layer_sample, every step-program sampler of sample.py on cd_layer_sampler_run."""
+        dim = self._layer_dim()
         self.set_layer_state(is_layer=True)
         try:
             if start is None:
-                start = self.noise_generation((energy.shape[0], self.shape_pad[2] + 1)).to(torch.float32)
+                start = self.noise_generation((energy.shape[0], dim)).to(torch.float32)
             x, _, _ = self.layer_sampler(self, start, energy, layers, self.layer_steps, sample_offset, debug)
             if getattr(self.layer_sampler, "ran_program", False):
                 # a step program (cd_layer_sampler_run) drew its noise tensors one global (B, dim) tensor apart behind the start
@@ -165,6 +200,7 @@ class LayerDiffusion(CaloDiffusion):
                layer_start: Optional[torch.Tensor] = None) -> dict:
         """layerdiffusion.py:134-169; returns {'x', ['xs', 'x0s'], ['layers']}.  ``start`` / ``layer_start`` (parity hooks)
         replace the internally drawn noise of the shower / layer stage."""
+        self._layer_dim()  # (raises before a start tensor is drawn)
         shape = [energy.shape[0]] + list(copy.copy(self._data_shape))
         if start is None:
             start = self.noise_generation(shape).to(torch.float32)
@@ -183,6 +219,7 @@ class LayerDiffusion(CaloDiffusion):
         """layerdiffusion.py:171-235: no layer energies are taken from the loader, the layer model generates them.  ``geometry``:
         as for ``Diffusion.generate``."""
         self._physical_form(reverse_norm, geometry)  # raise before sampling if this config has no inverse pre-processing here
+        self._layer_dim()
         generated, energies, layers = [], [], []
         for E, _, _d in data_loader:
             E = E.to(device=self.device)

@@ -617,7 +617,8 @@ int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights
 /* ---- generator: incident energies in, physical showers out, without Python -------------------------------------------
  * A generator file (calodiffusion_amd/generator.py: export_generator; format: DESIGN.md "Generator file") holds everything
  * Diffusion.generate / LayerDiffusion.generate (calodiffusion/models/diffusion.py:118-197, layerdiffusion.py:171-235) need for one
- * model (Dataset 2 / 3 on the regular grid, or HGCal with its geometry maps in the file; '[layer-]logit-norm'): the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's
+ * model (Dataset 2 / 3 on the regular grid, HGCal with its geometry maps in the file, or Dataset 0 / 1 with its irregular layout
+ * and matrices in the file; '[layer-]logit-norm'): the U-Net's descriptor, coordinate profiles and weights, LayerDiffusion's
  * layer model, each stage's compiled sampler (CdStep table or step program) and the inverse pre-processing record.
  * cd_generator_run is the launch sequence of that Python path -- start tensor from the Philox stream, (layer stage,) conditioning
  * row, U-Net sampler, cd_reverse_norm -- with the same stream offsets, so its showers are the ones generate() returns for the same
@@ -632,7 +633,11 @@ int cd_layer_denoise_vjp(const CdLayerMlpDesc* desc, const float* const* weights
  * up to 256 bytes) is freed before create returns.  An HGCal file (format version 2) also gets its geometry maps, built from the
  * file's sparse entries by cd_geom_create_csr -- the decoder with its column view (pre-embedded), or encoder and decoder with their
  * transposed views, bound by cd_plan_set_geom (converter inside the model): device memory in proportion to the entries, never the
- * dense (layers, rows, cols) tensor.  The call synchronises `stream`. */
+ * dense (layers, rows, cols) tensor.  A Dataset-0/1 file (format version 3) gets a CdRadialMap from the layout in its RADL section
+ * (cd_radial_create, after the reader has checked every rule of that call on the host) and its matrices in one more device block
+ * -- encoder and decoder, bound by cd_plan_set_radial with want_grads 0 (form 1: SHOWER_EMBED 'orig-NN', the sampler's state is
+ * the flat shower (batch, V)), or the un-conversion matrices alone (form 0: the state is the converted grid).  The call
+ * synchronises `stream`. */
 typedef struct CdGenerator CdGenerator;
 int cd_generator_create(const void* blob, size_t bytes, CdGenerator** out, void* stream);
 int cd_generator_destroy(CdGenerator* gen);
@@ -642,6 +647,12 @@ int cd_generator_checksum(const void* data, size_t bytes, uint64_t* out);
 /* info[8] (host) = {voxels per shower (HGCal: layers x cells), layers D, energy columns, has layer stage, takes layer energies,
  * sample steps, layer steps (0 without a layer stage), format version}. */
 int cd_generator_info(const CdGenerator* gen, int32_t* info);
+/* geom[8] (host) = {kind of the file's geometry section: 0 none (a regular grid), 1 HGCal maps (GEOM), 2 Dataset-0/1 radial maps
+ * (RADL); its form: 0 the model runs on the grid and the run converts at its end, 1 the converter is inside the model, -1 for
+ * kind 0; dimensions of the sampler's per-sample state; its shape, unused entries 0 -- (1, D, H, W) on a grid, (1, layers, cells)
+ * for HGCal form 1, (V) for Dataset-0/1 form 1; 0}.  A call of its own because cd_generator_info's eight entries are all taken and
+ * its array cannot grow without breaking callers that pass int32_t[8]: adding an entry point leaves CD_ABI_VERSION as it is. */
+int cd_generator_geometry(const CdGenerator* gen, int32_t* geom);
 int cd_generator_workspace_bytes(CdGenerator* gen, int batch, size_t* bytes);
 /* energy (batch, energy columns): the conditioning values e (energy_is_normalised != 0, what a loader of the Python path yields) or physical
  * incident energies in the unit of the config's EMIN / EMAX, mapped in the call as cd_preprocess maps them.  Either way the
@@ -674,6 +685,9 @@ int cd_generator_run(CdGenerator* gen, int batch, const float* energy, int energ
  * whose decoder has a column view (form 0), CD_EINVAL otherwise.  decode_seed / decode_offset: the position in the decoder's
  * stream (Decoder.noise_seed / noise_offset); *next_decode_offset (HOST, nullable) = decode_offset + (batch, or 1 per batch)
  * * layers * cells * grid bins, so chained calls draw what one decode of the concatenated batches draws.
+ * A Dataset-0/1 file (format version 3) ends in cd_reverse_norm_ds1 with the constants of its RNRM record: the flat form with the
+ * layer energies of a 'layer-' map (form 1), the grid form with the file's un-conversion matrices (form 0); one energy column,
+ * mapped as for the regular grids; showers (batch, V); sparse_mode != 0 is CD_EINVAL.
  * (Tag and typedef are declared apart because the struct holds pointers, as CdHlfDesc.) */
 struct CdGeneratorRun {
   uint32_t struct_size;         /* = sizeof(CdGeneratorRun) */

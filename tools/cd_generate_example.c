@@ -4,7 +4,8 @@
  *   cd_generate_example <generator file> <energies.f32> <showers.f32> <batch> [seed [offset [physical [sparse]]]]
  *
  * <generator file>: written by calodiffusion_amd.generator.export_generator.  <energies.f32>: raw little-endian fp32, one row of
- * incident-energy columns per shower (cd_generator_info's energy columns: 1 for the regular grids, 3 for HGCal) -- the
+ * incident-energy columns per shower (cd_generator_info's energy columns: 1 for the regular grids and Dataset 0 / 1, 3 for
+ * HGCal) -- the
  * conditioning values e of a loader, or with `physical` = 1 energies in the config's unit.  `sparse` (HGCal files whose decoder
  * has a column view): 0 plain decode, 1 sampled per shower, 2 sampled per batch, on the decoder's own stream (seed 1234, chained
  * from offset 0 as generate(sparse_decoding=True) walks it from Decoder.noise_offset = 0).
@@ -87,6 +88,14 @@ int main(int argc, char** argv) {
     fprintf(stderr, "the energies file holds no full row of %zu columns\n", cols);
     return 1;
   }
+  int32_t geo[8]; /* which geometry the file carries, and the sampler's state */
+  CD_OK_OR_DIE(cd_generator_geometry(gen, geo));
+  static const char* const kinds[3] = {"a regular grid", "HGCal maps", "Dataset-0/1 radial maps"};
+  printf("format version %d: %s", info[7], kinds[geo[0] >= 0 && geo[0] < 3 ? geo[0] : 0]);
+  if (geo[0] > 0) printf(", form %d (%s)", geo[1], geo[1] ? "the converter inside the model" : "converted at the end of the run");
+  printf(", state (");
+  for (int i = 0; i < geo[2] && i < 4; ++i) printf(i ? ", %d" : "%d", geo[3 + i]);
+  printf(")\n");
   if (info[4] && !info[3]) {
     fprintf(stderr, "this model takes layer energies from its caller: pass them to cd_generator_run (not part of this example)\n");
     return 1;

@@ -44,5 +44,16 @@ int main(int argc, char** argv) {
       std::printf("  encoder: %d x %d a layer, %d entries%s\n", g.enc.rows, g.enc.cols, g.enc.nnz, g.enc.is_mask ? " (a mask's pattern)" : "");
     std::printf("  decoder: %d x %d a layer, %d entries%s\n", g.dec.rows, g.dec.cols, g.dec.nnz, g.dec.is_mask ? " (a mask's pattern)" : "");
   }
+  if (blob.radial.form >= 0) {
+    const cdgen::Radial& g = blob.radial;
+    std::printf("  radial geometry: form %d (%s), grid (%d, %d, %d), %d voxels, %d matrix floats x %d\n", g.form,
+                g.form ? "in-model" : "on the converted grid", g.layers, g.alpha_out, g.r_out, g.voxels, g.wtotal, g.n_mats);
+    std::printf("  layers (alpha x radial bins):");
+    for (int i = 0; i < g.layers; ++i)
+      std::printf(" %d x %d", cdgen::detail::rd<int32_t>(g.alpha + 4 * i), cdgen::detail::rd<int32_t>(g.rin + 4 * i));
+    std::printf("\n  reverse norm: logit %.17g / %.17g, total E %.17g / %.17g, layers %.17g / %.17g, MAXDEP %g, ECUT %g\n", blob.rev.consts64[0],
+                blob.rev.consts64[1], blob.rev.consts64[2], blob.rev.consts64[3], blob.rev.consts64[4], blob.rev.consts64[5],
+                blob.rev.max_deposit, blob.rev.ecut);
+  }
   return 0;
 }
