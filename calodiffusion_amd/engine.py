@@ -1,4 +1,6 @@
-"""ctypes binding of ``lib/libcalodiff_hip.so`` (C ABI: ``include/calodiff.h``).
+"""The engines: the objects that own a plan of the HIP library and call it (``UnetEngine``, ``LayerMlpEngine``).  The ctypes
+binding they stand on is ``abi.py``, the primitive-op wrappers are ``ops.py``; both are re-imported here by name, so
+``engine.<name>`` keeps reaching everything it always did.
 
 PyTorch is used here for device memory, streams and parameter storage only.  There is no fallback of
 any kind: if the library is missing, or no gfx950 GPU is visible, every compute entry point raises.
@@ -7,295 +9,16 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CALODIFF_LIB") or os.path.join(_HERE, "lib", "libcalodiff_hip.so")  # override: A/B builds
-
-CD_MAX_SIZES = 8
-CD_ABI_VERSION = 3  # include/calodiff.h; load_library refuses a library that reports another one
-TIME_KINDS = {"log": 0, "sigma": 1, "raw": 2}
-OBJECTIVES = {"hybrid": 0, "noise_pred": 1, "mean_pred": 2}
-LOSS_TYPES = {"l2": 0, "l1": 1, "mse": 2, "huber": 3}  # CD_LOSS_* (Loss._loss, models/loss.py:97-116)
-
-
-class CdUnetDesc(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("grid", C.c_int32 * 3),
-        ("in_channels", C.c_int32),
-        ("n_sizes", C.c_int32),
-        ("layer_sizes", C.c_int32 * CD_MAX_SIZES),
-        ("groups", C.c_int32),
-        ("block_attn", C.c_int32),
-        ("mid_attn", C.c_int32),
-        ("compress_z", C.c_int32),
-        ("cond_size", C.c_int32),
-        ("cond_dim", C.c_int32),
-        ("rz_input", C.c_int32),
-        ("phi_input", C.c_int32),
-        ("time_embed_kind", C.c_int32),
-        ("objective", C.c_int32),
-        ("sigma_data", C.c_float),
-        ("time_sin", C.c_int32),
-        ("cond_sin", C.c_int32),
-    ]
-
-
-SOP_LINCOMB, SOP_DENOISE, SOP_RANDN, SOP_RECORD, SOP_LINDIV, SOP_DENOISE_PS = 0, 1, 2, 3, 4, 5
-
-
-class CdSamplerOp(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("dst", C.c_int32), ("nsrc", C.c_int32), ("src", C.c_int32 * 6), ("col", C.c_int32)]
-
-
-class CdLayerMlpDesc(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("dim_in", C.c_int32), ("hidden", C.c_int32), ("cond_emb", C.c_int32), ("cond_size", C.c_int32),
-                ("n_res", C.c_int32), ("time_embed_kind", C.c_int32), ("objective", C.c_int32), ("sigma_data", C.c_float)]
-
-
-class CdHlfDesc(C.Structure):
-    """Host tables of one binning geometry (cd_hlf_create copies them to the device)."""
-    _fields_ = [("struct_size", C.c_uint32), ("n_layers", C.c_int32), ("layer_offset", C.POINTER(C.c_int32)),
-                ("eta", C.POINTER(C.c_double)), ("phi", C.POINTER(C.c_double)), ("with_centres", C.POINTER(C.c_int32))]
-
-
-class CdGeneratorRun(C.Structure):
-    """The arguments of cd_generator_run_ex."""
-    _fields_ = [("struct_size", C.c_uint32), ("batch", C.c_int32), ("energy", C.c_void_p), ("energy_is_normalised", C.c_int32),
-                ("sparse_mode", C.c_int32), ("layers", C.c_void_p), ("seed", C.c_uint64), ("offset", C.c_uint64),
-                ("first_row", C.c_int32), ("global_batch", C.c_int32), ("showers", C.c_void_p), ("layers_out", C.c_void_p),
-                ("next_offset", C.POINTER(C.c_uint64)), ("decode_seed", C.c_uint64), ("decode_offset", C.c_uint64),
-                ("next_decode_offset", C.POINTER(C.c_uint64)), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("stream", C.c_void_p)]
-
-
-class CdClassifierDesc(C.Structure):
-    """The classifier test's DNN (calodiffusion_amd.classifier)."""
-    _fields_ = [("struct_size", C.c_uint32), ("input_dim", C.c_int32), ("hidden", C.c_int32), ("num_layer", C.c_int32),
-                ("negative_slope", C.c_float), ("dropout_p", C.c_float)]
-
-
-class CdStep(C.Structure):
-    _fields_ = [("sigma", C.c_float), ("sigma_prev_masked", C.c_float), ("ddim_sigma", C.c_float), ("denom", C.c_float)]
-
-
-# every symbol include/calodiff.h declares: (name, restype, argtypes)
-_P = C.c_void_p
-_SIGNATURES = {
-    "cd_last_error": (C.c_char_p, []),
-    "cd_abi_version": (C.c_int, []),
-    "cd_device_check": (C.c_int, [C.c_char_p, C.c_int]),
-    "cd_plan_create": (C.c_int, [C.POINTER(CdUnetDesc), C.POINTER(_P)]),
-    "cd_plan_destroy": (C.c_int, [_P]),
-    "cd_plan_num_weights": (C.c_int, [_P, C.POINTER(C.c_int)]),
-    "cd_plan_weight_name": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
-    "cd_plan_set_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),
-    "cd_plan_set_weights": (C.c_int, [_P, C.c_int, C.POINTER(_P), _P]),
-    "cd_plan_set_coords": (C.c_int, [_P, _P, _P, _P, _P]),
-    "cd_plan_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_unet_forward": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_denoise": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_denoise_safe": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_int), _P]),
-    "cd_ddim_sample": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(CdStep), C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P,
-                                 C.c_int, _P, C.c_size_t, _P]),
-    "cd_plan_sampler_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_sampler_run": (C.c_int, [_P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.POINTER(CdSamplerOp), C.c_int,
-                                 C.POINTER(C.c_int32), _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, C.c_int,
-                                 _P, C.c_size_t, _P]),
-    "cd_randn": (C.c_int, [_P, C.c_int64, C.c_uint64, C.c_uint64, _P]),
-    "cd_plan_grad_layout": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-    "cd_plan_train_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_plan_status": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
-    "cd_layer_forward": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P]),
-    "cd_layer_denoise": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P]),
-    "cd_layer_sample": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
-    "cd_layer_sampler_run": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, _P, C.c_int,
-                                       _P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
-    "cd_layer_train_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_layer_train_step": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_layer_train_step_loss": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t,
-                                           _P]),
-    "cd_layer_loss": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
-    "cd_layer_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_layer_denoise_vjp": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_reverse_norm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float, _P]),
-    "cd_reverse_norm_staged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                         C.c_float, C.c_float, C.c_int, _P]),
-    "cd_preprocess": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                C.c_float, C.c_int, C.c_float, _P]),
-    "cd_preprocess_hgcal": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.POINTER(C.c_double), C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double),
-                                      C.POINTER(C.c_double), C.c_float, _P]),
-    "cd_geom_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
-    "cd_geom_create_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
-    "cd_geom_create_csr": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P]),
-    "cd_geom_refresh": (C.c_int, [_P, _P, _P]),
-    "cd_geom_destroy": (C.c_int, [_P]),
-    "cd_geom_apply_vjp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
-    "cd_geom_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
-    "cd_geom_sparse_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_geom_decode_sparse": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.c_uint64, _P, _P]),
-    "cd_radial_create": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.POINTER(_P), _P]),
-    "cd_radial_destroy": (C.c_int, [_P]),
-    "cd_radial_enc": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
-    "cd_radial_dec": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
-    "cd_radial_enc_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
-    "cd_radial_dec_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P]),
-    "cd_preprocess_ds1": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_float, C.c_float,
-                                    C.c_int, C.c_float, _P]),
-    "cd_reverse_norm_ds1": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_float, _P]),
-    "cd_plan_set_radial": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
-    "cd_plan_set_geom": (C.c_int, [_P, _P, _P, C.c_int, _P]),
-    "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                               C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
-    "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
-    "cd_plan_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_denoise_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_plan_bns_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_bns_theta_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_generator_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), _P]),
-    "cd_generator_destroy": (C.c_int, [_P]),
-    "cd_generator_checksum": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_uint64)]),
-    "cd_generator_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
-    "cd_generator_geometry": (C.c_int, [_P, C.POINTER(C.c_int32)]),
-    "cd_generator_workspace_bytes": (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_generator_run": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64),
-                                   _P, C.c_size_t, _P]),
-    "cd_generator_run_ex": (C.c_int, [_P, C.POINTER(CdGeneratorRun)]),
-    "cd_hlf_create": (C.c_int, [C.POINTER(CdHlfDesc), C.POINTER(_P), _P]),
-    "cd_hlf_destroy": (C.c_int, [_P]),
-    "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
-    "cd_fpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "cd_fpd_moments": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_kpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "cd_kpd_sums": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int, _P, _P, _P, C.c_size_t,
-                              _P]),
-    "cd_column_histograms_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
-    "cd_column_histograms": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
-    "cd_classifier_num_params": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_int64)]),
-    "cd_classifier_workspace_bytes": (C.c_int, [C.POINTER(CdClassifierDesc), C.c_int, C.POINTER(C.c_size_t)]),
-    "cd_classifier_forward": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P,
-                                        C.c_size_t, _P]),
-    "cd_classifier_train_step": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, _P, C.c_int64, _P, C.c_int, C.c_uint64,
-                                           C.c_uint64, _P, _P, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double, C.c_float, C.c_int, _P,
-                                           C.c_size_t, _P]),
-    "cd_classifier_train_epoch": (C.c_int, [C.POINTER(CdClassifierDesc), C.POINTER(C.c_void_p), _P, _P, C.c_int64, _P, C.c_int64, C.c_int,
-                                            C.c_uint64, C.c_uint64, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_float, _P, _P,
-                                            C.c_size_t, _P]),
-    "cd_classifier_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P]),
-    "cd_set_conv_precision": (C.c_int, [C.c_char_p]),
-    "cd_get_conv_precision": (C.c_char_p, []),
-    "cd_profile_begin": (C.c_int, []),
-    "cd_profile_end": (C.c_int, [C.c_char_p, C.c_int]),
-    "cd_loss_hybrid_l2": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "cd_loss_hybrid": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
-    "cd_op_to_channels_last": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P]),
-    "cd_op_to_ncdhw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P]),
-    "cd_op_cyl_conv": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P]),
-    "cd_op_zslide_conv": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                    _P, _P]),
-    "cd_op_cyl_conv_transpose": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
-                                           C.POINTER(C.c_int32), _P, _P]),
-    "cd_op_init_conv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, _P]),
-    "cd_op_init_pair_conv": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.c_int,
-                                       C.POINTER(C.c_int32), C.c_int, _P, _P]),
-    "cd_op_group_norm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
-    "cd_op_resnet_block": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(_P), _P, _P, C.c_int, C.c_int,
-                                     C.POINTER(C.c_int32), C.c_int, _P, C.c_size_t, _P]),
-    "cd_op_linear_attention": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, C.c_size_t, _P]),
-    "cd_op_conv_backward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, C.c_size_t, _P]),
-    "cd_op_conv_transpose_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
-                                                C.POINTER(C.c_int32), _P, C.c_size_t, _P]),
-    "cd_op_group_norm_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P,
-                                            C.c_size_t, _P]),
-    "cd_op_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
-    "cd_op_linear_act": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int,
-                                   _P]),
-    "cd_op_linear_act_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
-                                            C.c_size_t, _P]),
-}
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-
-_lib = None
-
-
-def load_library() -> C.CDLL:
-    """dlopen the HIP library and bind every declared symbol; fails loudly if it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: build it with `python -m calodiffusion_amd.build` (hipcc, --offload-arch=gfx950). "
-            "calodiffusion_amd has no CPU or PyTorch fallback.")
-    _check_built_from_these_sources()
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype, fn.argtypes = res, args
-    if lib.cd_abi_version() != CD_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} reports ABI version {lib.cd_abi_version()}, this binding is written against "
-                           f"{CD_ABI_VERSION} (include/calodiff.h): rebuild with `python -m calodiffusion_amd.build`")
-    _lib = lib
-    return lib
-
-
-def _check_built_from_these_sources():
-    """The library is git-ignored and travels between boxes as a built file: refuse one that was not built from the sources
-    next to it (a stale .so with an older argument list shifts every pointer argument).  build.py writes `<lib>.srchash`
-    after every link; CALODIFF_LIB (an explicit A/B build) and CD_SKIP_SRCHASH=1 bypass the check."""
-    if os.environ.get("CALODIFF_LIB") or os.environ.get("CD_SKIP_SRCHASH"):
-        return
-    from . import build
-    stamp = LIB_PATH + ".srchash"
-    have = open(stamp).read().strip() if os.path.exists(stamp) else None
-    want = build.source_hash()
-    if have != want:
-        raise RuntimeError(f"{LIB_PATH} was not built from the sources in {build.CSRC} (stamp {str(have)[:12]}, sources "
-                           f"{want[:12]}): run `python -m calodiffusion_amd.build`")
-
-
-def _check(code: int):
-    if code != 0:
-        msg = load_library().cd_last_error().decode(errors="replace")
-        exc = ValueError if code == -1 else RuntimeError
-        raise exc(f"calodiff[{code}]: {msg}")
-
-
-def require_gpu() -> str:
-    lib = load_library()
-    if not torch.cuda.is_available():
-        raise RuntimeError("calodiffusion_amd needs an MI355X (gfx950) GPU: torch.cuda.is_available() is False and "
-                           "there is no CPU fallback")
-    buf = C.create_string_buffer(256)
-    _check(lib.cd_device_check(buf, 256))
-    return buf.value.decode()
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev32(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA(ROCm) tensor: calodiffusion_amd computes on the GPU only")
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
-    return t
-
-
-def _i32x3(v: Sequence[int]):
-    return (C.c_int32 * 3)(*[int(a) for a in v])
+from .abi import (CD_ABI_VERSION, CD_MAX_SIZES, EXPORTED_SYMBOLS, LIB_PATH, LOSS_TYPES, OBJECTIVES, SOP_DENOISE, SOP_DENOISE_PS,
+                  SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD, TIME_KINDS, CdClassifierDesc, CdGeneratorRun, CdHlfDesc,
+                  CdLayerMlpDesc, CdSamplerOp, CdStep, CdUnetDesc, WorkspaceCache, _P, _SIGNATURES, _check,
+                  _check_built_from_these_sources, _dev32, _i32x3, _ptr, _stream, get_conv_precision, load_library, profile_begin,
+                  profile_end, randn, require_gpu, set_conv_precision)
+from .ops import Ops
 
 
 def _sigma_b(sigma, B: int) -> torch.Tensor:
@@ -331,6 +54,13 @@ def _program_io(start, program, n_steps: int, step_noise, debug: bool, what: str
         step_noise = _dev32(step_noise, "step_noise")
         assert step_noise.numel() == program.n_randn * start.numel(), f"step_noise: one {what} tensor per RANDN op executed"
     return xs, x0s, step_noise
+
+
+def _nbytes(sizing_fn, *args) -> int:
+    """What a ``cd_*_workspace_bytes(*args, size_t *out)`` entry point reports."""
+    n = C.c_size_t()
+    _check(sizing_fn(*args, C.byref(n)))
+    return n.value
 
 
 def unet_desc(unet, rz_input=False, phi_input=False, time_kind="raw", objective="hybrid", sigma_data=1.0, coords=None) -> CdUnetDesc:
@@ -383,9 +113,11 @@ class UnetEngine:
         self._weight_order = None  # [(state_dict name, tensor)] in the plan's order
         self._weight_ids = None
         self._held_weights = []
-        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._ws = WorkspaceCache()  # kinds "net", "sampler", "train", "vjp", "bns"; every key starts with _ws_key(batch)
+        self._grad_layout = None
+        self.range_fallbacks = 0
         self.embedding = None  # set_embedding: the NNConverter / HGCalConverter whose enc / dec run inside the denoise-based calls
-        self._rmap = self._gmaps = None
+        self._rmap = self._enc_flat = self._dec_flat = self._gmaps = self._embed_version = None
         self.state_shape = (1,) + self.grid  # per-sample state of those calls
         self.device = next(unet.parameters()).device
         if self.device.type != "cuda":
@@ -414,6 +146,18 @@ class UnetEngine:
         ps = list(self.unet.parameters())
         return tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps) + (tuple(id(p) for p in ps),)
 
+    def _plan_weights(self):
+        """[(state_dict name, numel)] of the plan's weight tensors, in the plan's order."""
+        n = C.c_int()
+        _check(self.lib.cd_plan_num_weights(self.plan, C.byref(n)))
+        buf = C.create_string_buffer(256)
+        numel = C.c_int64()
+        out = []
+        for i in range(n.value):
+            _check(self.lib.cd_plan_weight_name(self.plan, i, buf, 256, C.byref(numel)))
+            out.append((buf.value.decode(), numel.value))
+        return out
+
     # ------------------------------------------------------------------ flat-state embedding
     def set_embedding(self, nn_embed):
         """Bind a geometry embedding (None: unbind) to the plan: the state of denoise, the samplers, the loss, train_step and
@@ -423,7 +167,7 @@ class UnetEngine:
         whose values follow a trainable converter's parameters.  Either is refreshed whenever a weight changed (sync_weights)."""
         from .hgcal import HGCalConverter
         self._grad_layout = None
-        self._ws, self._tws, self._vws = {}, {}, {}
+        self._ws.clear()
         self._embed_version = None
         self._rmap = self._enc_flat = self._dec_flat = self._gmaps = None
         if nn_embed is None:
@@ -477,7 +221,7 @@ class UnetEngine:
                 _check(self.lib.cd_plan_set_geom(self.plan, enc.handle, dec.handle, int(ver[-1]), _stream()))
                 self._gmaps = (enc, dec)  # (kept alive here)
                 self._grad_layout = None  # (frozen maps have no gradient slots)
-                self._tws, self._vws = {}, {}
+                self._ws.drop("train", "vjp")
                 self._embed_version = ver
             return
         ps = [p for _, p in self._embed_params()]
@@ -506,18 +250,12 @@ class UnetEngine:
         ids = ver[-1]
         if self._weight_order is None or self._weight_ids != ids:
             sd = self.unet.state_dict(keep_vars=True)
-            n = C.c_int()
-            _check(self.lib.cd_plan_num_weights(self.plan, C.byref(n)))
-            buf = C.create_string_buffer(256)
-            numel = C.c_int64()
             order = []
-            for i in range(n.value):
-                _check(self.lib.cd_plan_weight_name(self.plan, i, buf, 256, C.byref(numel)))
-                name = buf.value.decode()
+            for name, numel in self._plan_weights():
                 if name not in sd:
                     raise RuntimeError(f"state_dict has no tensor named {name!r}")
-                if sd[name].numel() != numel.value:
-                    raise RuntimeError(f"{name}: {sd[name].numel()} elements, HIP plan expects {numel.value}")
+                if sd[name].numel() != numel:
+                    raise RuntimeError(f"{name}: {sd[name].numel()} elements, HIP plan expects {numel}")
                 order.append((name, sd[name]))
             missing = set(sd) - {name for name, _ in order}
             if missing:
@@ -530,7 +268,7 @@ class UnetEngine:
         self._weights_version = ver
 
     # launch-sequence switches the library reads per call (tests and A/B runs flip them inside one process): a workspace sized
-    # under one setting is not valid under another, so they are part of the cache key.  (The arithmetic mode is not: the
+    # under one setting is not valid under another, so they are part of every cache key.  (The arithmetic mode is not: the
     # library sizes for the largest of its three modes.)
     _WS_SWITCHES = ("CD_NO_DEEP_LEVEL", "CD_NO_PW_CLOSE", "CD_NO_FUSED_ATTN", "CD_NO_GNDEFER", "CD_ATTN_COMBINE_LAUNCH", "CD_PW_F32",
                     "CD_NO_ATTN_MOMENTS", "CD_ATTN_MOM_MIN", "CD_NO_DEEP_SIDE_CONV")
@@ -539,17 +277,8 @@ class UnetEngine:
         return (int(batch),) + tuple(os.environ.get(k) for k in self._WS_SWITCHES)
 
     def workspace(self, batch: int) -> torch.Tensor:
-        key = ("net",) + self._ws_key(batch)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_plan_workspace_bytes(self.plan, batch, C.byref(nbytes)))
-            # keep ONE network workspace and ONE sampler-program workspace (each ~1 GB at the headline batch: alternating
-            # denoise / sampler calls would otherwise reallocate every time, a ragged last batch would double the footprint)
-            self._ws = {k: v for k, v in self._ws.items() if k[0] != "net"}
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        return ws
+        return self._ws.get("net", self._ws_key(batch), self.device,
+                            lambda: _nbytes(self.lib.cd_plan_workspace_bytes, self.plan, batch))
 
     # ------------------------------------------------------------------ compute
     def unet_forward(self, x, cond, time):
@@ -591,7 +320,7 @@ class UnetEngine:
             _check(self.lib.cd_denoise_safe(self.plan, B, x.data_ptr(), sigma.data_ptr(), cond.data_ptr(), out.data_ptr(),
                                             ws.data_ptr(), ws.numel(), C.byref(fell), _stream()))
             if fell.value:
-                self.range_fallbacks = getattr(self, "range_fallbacks", 0) + 1
+                self.range_fallbacks += 1
         else:
             _check(self.lib.cd_denoise(self.plan, B, x.data_ptr(), sigma.data_ptr(), cond.data_ptr(), out.data_ptr(),
                                        ws.data_ptr(), ws.numel(), _stream()))
@@ -636,14 +365,9 @@ class UnetEngine:
             assert len(program.op_begin) == n_steps + 1
             op_begin = (C.c_int32 * (n_steps + 1))(*program.op_begin)
         self.sync_weights()
-        nbytes = C.c_size_t()
-        _check(self.lib.cd_plan_sampler_workspace_bytes(self.plan, B, program.n_bufs, n_steps, n_coef, C.byref(nbytes)))
-        key = ("sampler",) + self._ws_key(B)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes.value:
-            self._ws = {k: v for k, v in self._ws.items() if k[0] != "sampler"}  # (other batch sizes / switch settings: evicted)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
+        # (the size follows the program as well as the batch: kept while it is large enough)
+        ws = self._ws.get("sampler", self._ws_key(B), self.device,
+                          _nbytes(self.lib.cd_plan_sampler_workspace_bytes, self.plan, B, program.n_bufs, n_steps, n_coef))
         x_out = torch.empty_like(start)
         xs, x0s, step_noise = _program_io(start, program, n_steps, step_noise, debug, "(B,1,D,H,W)")
         _check(self.lib.cd_sampler_run(self.plan, B, start.data_ptr(), float(program.start_scale), cond.data_ptr(), program.n_bufs,
@@ -659,7 +383,7 @@ class UnetEngine:
         flags = C.c_int(0)
         _check(self.lib.cd_plan_status(self.plan, C.byref(flags), _stream()))
         if flags.value & 2:
-            self.range_fallbacks = getattr(self, "range_fallbacks", 0) + 1
+            self.range_fallbacks += 1
         if flags.value & 1:
             raise FloatingPointError("calodiff: an activation exceeded the fp16 range of the f16x2 convolution kernels "
                                      "(outputs contain inf/NaN); set CD_CONV_PRECISION=bf16x3 for the full fp32 range")
@@ -667,44 +391,41 @@ class UnetEngine:
     # ------------------------------------------------------------------ training
     def grad_layout(self):
         """{state_dict name: (offset, numel)} into the flat gradient buffer, and its total length."""
-        if getattr(self, "_grad_layout", None) is None:
-            n = C.c_int()
-            _check(self.lib.cd_plan_num_weights(self.plan, C.byref(n)))
-            buf = C.create_string_buffer(256)
-            numel, off, total = C.c_int64(), C.c_int64(), C.c_int64()
+        if self._grad_layout is None:
+            off, total = C.c_int64(), C.c_int64()
+            weights = self._plan_weights()
             lay = {}
-            for i in range(n.value):
-                _check(self.lib.cd_plan_weight_name(self.plan, i, buf, 256, C.byref(numel)))
+            for i, (name, numel) in enumerate(weights):
                 _check(self.lib.cd_plan_grad_layout(self.plan, i, C.byref(off), C.byref(total)))
-                lay[buf.value.decode()] = (off.value, numel.value)
+                lay[name] = (off.value, numel)
             # the embedding's two blocks follow the U-Net's (cd_plan_set_radial; cd_plan_set_geom when its maps train)
             if self.embedding is not None and (not self._embed_is_geom() or self.embedding_trains()):
                 sizes = ((self._rmap.wtotal,) * 2 if not self._embed_is_geom() else
                          (self.embedding.embeder.mat.numel(), self.embedding.decoder.mat.numel()))
                 for k, name in enumerate(("NN_embed.encs", "NN_embed.decs")):
-                    _check(self.lib.cd_plan_grad_layout(self.plan, n.value + k, C.byref(off), C.byref(total)))
+                    _check(self.lib.cd_plan_grad_layout(self.plan, len(weights) + k, C.byref(off), C.byref(total)))
                     lay[name] = (off.value, sizes[k])
             self._grad_layout = (lay, total.value)
         return self._grad_layout
 
     def train_workspace(self, batch: int) -> torch.Tensor:
-        ws = getattr(self, "_tws", {}).get(batch)
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_plan_train_workspace_bytes(self.plan, batch, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._tws = {batch: ws}
-        return ws
+        return self._ws.get("train", self._ws_key(batch), self.device,
+                            lambda: _nbytes(self.lib.cd_plan_train_workspace_bytes, self.plan, batch))
+
+    def _loss_io(self, data, noise, sigma, cond, name):
+        """The checked arguments of train_step and loss_hybrid, and the batch size."""
+        data, noise, cond = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(cond, "cond")
+        sigma = _dev32(sigma, "sigma").reshape(-1)
+        B = data.shape[0]
+        self._check_state(data, name, "data")
+        if noise.shape != data.shape or sigma.numel() != B:
+            raise ValueError(f"{name}: noise {tuple(noise.shape)} must have data's shape and sigma {tuple(sigma.shape)} B elements")
+        return data, noise, sigma, cond, B
 
     def train_step(self, data, noise, sigma, cond, loss_type="l2"):
         """hybrid_weight loss (LOSS_TYPE l2 / l1 / mse / huber) and the gradient of every parameter (flat fp32 buffer, see
         grad_layout)."""
-        data, noise, cond = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(cond, "cond")
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        B = data.shape[0]
-        self._check_state(data, "train_step", "data")
-        if noise.shape != data.shape or sigma.numel() != B:
-            raise ValueError(f"train_step: noise {tuple(noise.shape)} must have data's shape and sigma {tuple(sigma.shape)} B elements")
+        data, noise, sigma, cond, B = self._loss_io(data, noise, sigma, cond, "train_step")
         self.sync_weights()
         ws = self.train_workspace(B)
         _, total = self.grad_layout()
@@ -715,16 +436,10 @@ class UnetEngine:
         return loss, flat
 
     def vjp_workspace(self, batch: int, with_param_grads: bool) -> torch.Tensor:
-        """Workspace of cd_denoise_vjp (one kept: the last batch size and mode asked for)."""
-        key = (int(batch), bool(with_param_grads))
-        ws = getattr(self, "_vws", {}).get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_plan_vjp_workspace_bytes(self.plan, batch, int(bool(with_param_grads)), C.byref(nbytes)))
-            self._vws = {}  # (release the previous one before allocating the next)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._vws = {key: ws}
-        return ws
+        """Workspace of cd_denoise_vjp."""
+        mode = bool(with_param_grads)
+        return self._ws.get("vjp", self._ws_key(batch) + (mode,), self.device,
+                            lambda: _nbytes(self.lib.cd_plan_vjp_workspace_bytes, self.plan, batch, int(mode)))
 
     def denoise_vjp(self, x, sigma, cond, gy, param_grads: bool):
         """Vector-Jacobian product of denoise (cd_denoise_vjp): dx = dL/dx for gy = dL/dD, and with ``param_grads`` the
@@ -748,16 +463,9 @@ class UnetEngine:
         return dx, flat
 
     def bns_workspace(self, batch: int, n_steps: int) -> torch.Tensor:
-        """Workspace of cd_bns_theta_grad (one kept: the last shape asked for)."""
-        key = (int(batch), int(n_steps))
-        ws = getattr(self, "_bws", {}).get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_plan_bns_workspace_bytes(self.plan, batch, n_steps, C.byref(nbytes)))
-            self._bws = {}  # (release the previous one before allocating the next)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._bws = {key: ws}
-        return ws
+        """Workspace of cd_bns_theta_grad."""
+        return self._ws.get("bns", self._ws_key(batch) + (int(n_steps),), self.device,
+                            lambda: _nbytes(self.lib.cd_plan_bns_workspace_bytes, self.plan, batch, n_steps))
 
     def bns_theta_grad(self, data, cond, theta, sigma):
         """BespokeNonStationary training loss and its gradient with respect to theta (cd_bns_theta_grad): the chain
@@ -801,12 +509,7 @@ class UnetEngine:
         return out
 
     def loss_hybrid(self, data, noise, sigma, cond, loss_type="l2"):
-        data, noise, cond = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(cond, "cond")
-        sigma = _dev32(sigma, "sigma").reshape(-1)
-        B = data.shape[0]
-        self._check_state(data, "loss_hybrid", "data")
-        if noise.shape != data.shape or sigma.numel() != B:
-            raise ValueError(f"loss_hybrid: noise {tuple(noise.shape)} must have data's shape and sigma {tuple(sigma.shape)} B elements")
+        data, noise, sigma, cond, B = self._loss_io(data, noise, sigma, cond, "loss_hybrid")
         self.sync_weights()
         ws = self.workspace(B)
         out = torch.empty((), dtype=torch.float64, device=data.device)
@@ -829,6 +532,9 @@ class LayerMlpEngine:
         self.net = resnet
         self.desc = layer_mlp_desc(resnet, time_kind, objective, sigma_data)
         self.dim = resnet.dim_in
+        self.device = next(resnet.parameters()).device
+        self._ws = WorkspaceCache()  # kinds "train" and "vjp"
+        self._keep = []
 
     def _weights(self):
         ps = [_dev32(p.detach(), k) for k, p in self.net.state_dict().items()]
@@ -880,15 +586,9 @@ class LayerMlpEngine:
         return lay, off
 
     def train_workspace(self, batch: int) -> torch.Tensor:
-        """Workspace of cd_layer_train_step_loss / cd_layer_loss (one kept: the last batch size asked for)."""
-        ws = getattr(self, "_tws", {}).get(int(batch))
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_layer_train_workspace_bytes(C.byref(self.desc), batch, C.byref(nbytes)))
-            self._tws = {}
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=next(self.net.parameters()).device)
-            self._tws = {int(batch): ws}
-        return ws
+        """Workspace of cd_layer_train_step_loss / cd_layer_loss."""
+        return self._ws.get("train", (int(batch),), self.device,
+                            lambda: _nbytes(self.lib.cd_layer_train_workspace_bytes, C.byref(self.desc), batch))
 
     def _loss_io(self, data, noise, sigma, cond):
         data, cond, B = self._io(data, cond)
@@ -923,16 +623,10 @@ class LayerMlpEngine:
         return loss
 
     def vjp_workspace(self, batch: int, with_param_grads: bool) -> torch.Tensor:
-        """Workspace of cd_layer_denoise_vjp (one kept: the last batch size and mode asked for)."""
-        key = (int(batch), bool(with_param_grads))
-        ws = getattr(self, "_vws", {}).get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            _check(self.lib.cd_layer_vjp_workspace_bytes(C.byref(self.desc), batch, int(bool(with_param_grads)), C.byref(nbytes)))
-            self._vws = {}  # (release the previous one before allocating the next)
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=next(self.net.parameters()).device)
-            self._vws = {key: ws}
-        return ws
+        """Workspace of cd_layer_denoise_vjp."""
+        mode = bool(with_param_grads)
+        return self._ws.get("vjp", (int(batch), mode), self.device,
+                            lambda: _nbytes(self.lib.cd_layer_vjp_workspace_bytes, C.byref(self.desc), batch, int(mode)))
 
     def denoise_vjp(self, x, sigma, cond, gy, param_grads: bool):
         """Vector-Jacobian product of denoise (cd_layer_denoise_vjp): dx = dL/dx for gy = dL/dD, and with ``param_grads`` the
@@ -1009,224 +703,3 @@ class LayerMlpEngine:
         _check(self.lib.cd_layer_sample(C.byref(self.desc), w, n, B, start.data_ptr(), cond.data_ptr(), table.data_ptr(),
                                         n_steps, _ptr(step_noise), x_out.data_ptr(), _ptr(xs), _ptr(x0s), _stream()))
         return x_out, xs, x0s
-
-
-def set_conv_precision(mode: str):
-    """'f16x2' (default), 'bf16x3' or 'f32' arithmetic of the convolutions, process-wide (cd_set_conv_precision)."""
-    _check(load_library().cd_set_conv_precision(mode.encode()))
-
-
-def get_conv_precision() -> str:
-    return load_library().cd_get_conv_precision().decode()
-
-
-def profile_begin():
-    _check(load_library().cd_profile_begin())
-
-
-def profile_end() -> dict:
-    import json
-    buf = C.create_string_buffer(1 << 18)
-    _check(load_library().cd_profile_end(buf, 1 << 18))
-    return json.loads(buf.value.decode())
-
-
-def randn(shape, device, seed: int, offset: int = 0) -> torch.Tensor:
-    """Unit normals from the device Philox stream (element i is a function of (seed, offset + i) only)."""
-    lib = load_library()
-    require_gpu()
-    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-    _check(lib.cd_randn(out.data_ptr(), out.numel(), int(seed), int(offset), _stream()))
-    return out
-
-
-# ---------------------------------------------------------------------- primitive ops (parity tests)
-class Ops:
-    """Thin wrappers over the cd_op_* entry points.  Activations are channels-last (B, D, H, W, C)."""
-
-    def __init__(self):
-        self.lib = load_library()
-        require_gpu()
-        self._scratch = None
-
-    def scratch(self, batch, channels, voxels):
-        need = self.lib.cd_op_scratch_bytes(batch, channels, voxels)
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-        return self._scratch
-
-    def to_channels_last(self, x):
-        x = _dev32(x, "x")
-        B, Cc = x.shape[:2]
-        vox = int(np.prod(x.shape[2:]))
-        y = torch.empty((B,) + tuple(x.shape[2:]) + (Cc,), dtype=torch.float32, device=x.device)
-        _check(self.lib.cd_op_to_channels_last(x.data_ptr(), y.data_ptr(), B, Cc, vox, _stream()))
-        return y
-
-    def to_ncdhw(self, y):
-        y = _dev32(y, "y")
-        B, Cc = y.shape[0], y.shape[-1]
-        vox = int(np.prod(y.shape[1:-1]))
-        x = torch.empty((B, Cc) + tuple(y.shape[1:-1]), dtype=torch.float32, device=y.device)
-        _check(self.lib.cd_op_to_ncdhw(y.data_ptr(), x.data_ptr(), B, Cc, vox, _stream()))
-        return x
-
-    def cyl_conv(self, x_cl, w, bias, stride=(1, 1, 1), x1_cl=None):
-        x_cl, w = _dev32(x_cl, "x"), _dev32(w, "w")
-        B, D, H, W, c0 = x_cl.shape
-        c1 = 0 if x1_cl is None else x1_cl.shape[-1]
-        cout = w.shape[0]
-        k = tuple(w.shape[2:])
-        if k == (1, 1, 1):
-            od = (D, H, W)
-        else:
-            od = ((D + 2 - k[0]) // stride[0] + 1, (H + 2 - k[1]) // stride[1] + 1, (W + 2 - k[2]) // stride[2] + 1)
-        y = torch.empty((B,) + od + (cout,), dtype=torch.float32, device=x_cl.device)
-        sc = self.scratch(B, max(c0 + c1, cout), D * H * W)
-        _check(self.lib.cd_op_cyl_conv(x_cl.data_ptr(), c0, _ptr(x1_cl), c1, w.data_ptr(), _ptr(bias), y.data_ptr(), B, cout,
-                                       _i32x3((D, H, W)), _i32x3(k), _i32x3(stride), sc.data_ptr(), _stream()))
-        return y
-
-    def zslide_conv_chunked(self, x_cl, w, bias, chunks=0):
-        """3x3x3 conv through the z-slide kernel with every sample dealt in `chunks` chunks (0: the launcher's choice).  Returns
-        (y, stats): stats [B][cout][2] = the kernel's channel partials {sum, sum of squares} of y, added up in fp64."""
-        x_cl, w = _dev32(x_cl, "x"), _dev32(w, "w")
-        B, D, H, W, cin = x_cl.shape
-        cout = w.shape[0]
-        y = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x_cl.device)
-        cap = (D * H * W + 31) // 32
-        part = torch.zeros((B, cap, cout, 2), dtype=torch.float32, device=x_cl.device)
-        units = C.c_int()
-        sc = self.scratch(B, max(cin, cout), D * H * W)
-        _check(self.lib.cd_op_zslide_conv(x_cl.data_ptr(), cin, w.data_ptr(), _ptr(bias), y.data_ptr(), part.data_ptr(), C.byref(units),
-                                          B, cout, _i32x3((D, H, W)), int(chunks), sc.data_ptr(), _stream()))
-        u = units.value  # (the partials are packed [B][units][cout][2] at the front of the buffer)
-        return y, part.view(-1)[:B * u * cout * 2].view(B, u, cout, 2).double().sum(1)
-
-    def cyl_conv_transpose(self, x_cl, w, bias, kernel_z, stride_z, out_pad):
-        x_cl, w = _dev32(x_cl, "x"), _dev32(w, "w")
-        B, D, H, W, c = x_cl.shape
-        od = ((D - 1) * stride_z - 2 + kernel_z, 2 * H + out_pad[1], 2 * W + out_pad[2])
-        y = torch.empty((B,) + od + (c,), dtype=torch.float32, device=x_cl.device)
-        sc = self.scratch(B, c, int(np.prod(od)))
-        _check(self.lib.cd_op_cyl_conv_transpose(x_cl.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, c,
-                                                 _i32x3((D, H, W)), kernel_z, stride_z, _i32x3(out_pad), sc.data_ptr(),
-                                                 _stream()))
-        return y
-
-    def init_conv(self, x_ncdhw, w, bias):
-        x, w = _dev32(x_ncdhw, "x"), _dev32(w, "w")
-        B, cin, D, H, W = x.shape
-        cout = w.shape[0]
-        y = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device)
-        sc = self.scratch(B, cout, D * H * W)
-        _check(self.lib.cd_op_init_conv(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, cin, cout, _i32x3((D, H, W)),
-                                        sc.data_ptr(), _stream()))
-        return y
-
-    def init_pair_conv(self, x, w0, b0, w1, b1, profiles=None, scale=None, slabs=0, y=None, part=None):
-        """The init conv followed by a 32 -> 32 3x3x3 conv as the one composed 5x5x5 launch.  x: (B, D, H, W), the data channel;
-        w0 (32, cin, 3, 3, 3) with cin = 1 + coordinate channels; profiles = (r_w, z_d, phi_h, use_rz, use_phi) or None; scale:
-        (B,) per-sample multiplier of x or None.  y (B, D, H, W, 32) and part (>= B * D * 64 floats) may be the caller's own
-        (guard-band tests).  Returns (y, stats, units), stats as zslide_conv_chunked's."""
-        x, w0, w1 = _dev32(x, "x"), _dev32(w0, "w0"), _dev32(w1, "w1")
-        B, D, H, W = x.shape
-        cin = w0.shape[1]
-        if y is None:
-            y = torch.empty((B, D, H, W, 32), dtype=torch.float32, device=x.device)
-        if part is None:
-            part = torch.zeros((B * D * 64,), dtype=torch.float32, device=x.device)
-        r_w, z_d, phi_h, use_rz, use_phi = profiles if profiles is not None else (None, None, None, 0, 0)
-        units = C.c_int()
-        sc = self.scratch(B, 32, D * H * W)
-        _check(self.lib.cd_op_init_pair_conv(x.data_ptr(), w0.data_ptr(), _ptr(b0), w1.data_ptr(), _ptr(b1), cin, _ptr(r_w), _ptr(z_d),
-                                             _ptr(phi_h), int(use_rz), int(use_phi), _ptr(scale), y.data_ptr(), part.data_ptr(),
-                                             C.byref(units), B, _i32x3((D, H, W)), int(slabs), sc.data_ptr(), _stream()))
-        u = units.value
-        return y, part.view(-1)[:B * u * 64].view(B, u, 32, 2).double().sum(1), u
-
-    def group_norm(self, x_cl, gamma, beta, groups, silu=False, add_bc=None, residual=None):
-        x = _dev32(x_cl, "x")
-        B, Cc = x.shape[0], x.shape[-1]
-        vox = int(np.prod(x.shape[1:-1]))
-        y = torch.empty_like(x)
-        sc = self.scratch(B, Cc, vox)
-        _check(self.lib.cd_op_group_norm(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B, Cc, vox, groups,
-                                         int(silu), _ptr(add_bc), _ptr(residual), sc.data_ptr(), _stream()))
-        return y
-
-    def _bws(self, nbytes=1 << 30):
-        if getattr(self, "_bwd_ws", None) is None or self._bwd_ws.numel() < nbytes:
-            self._bwd_ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-        return self._bwd_ws
-
-    def conv_backward(self, x_cl, w, dy_cl, stride=(1, 1, 1), x1_cl=None, need_dx=True, bias=True):
-        """Gradients (dx, dw, db) of cyl_conv; channels-last activations, torch-layout weights."""
-        x, w, dy = _dev32(x_cl, "x"), _dev32(w, "w"), _dev32(dy_cl, "dy")
-        B, D, H, W, c0 = x.shape
-        c1 = 0 if x1_cl is None else x1_cl.shape[-1]
-        cout, k = w.shape[0], tuple(w.shape[2:])
-        dx = torch.empty((B, D, H, W, c0 + c1), dtype=torch.float32, device=x.device) if need_dx else None
-        dw = torch.empty_like(w)
-        db = torch.empty((cout,), dtype=torch.float32, device=x.device) if bias else None
-        ws = self._bws()
-        _check(self.lib.cd_op_conv_backward(x.data_ptr(), c0, _ptr(x1_cl), c1, w.data_ptr(), dy.data_ptr(), _ptr(dx), dw.data_ptr(),
-                                            _ptr(db), B, cout, _i32x3((D, H, W)), _i32x3(k), _i32x3(stride), ws.data_ptr(),
-                                            ws.numel(), _stream()))
-        return dx, dw, db
-
-    def conv_transpose_backward(self, x_cl, w, dy_cl, kernel_z, stride_z, out_pad):
-        x, w, dy = _dev32(x_cl, "x"), _dev32(w, "w"), _dev32(dy_cl, "dy")
-        B, D, H, W, c = x.shape
-        dx, dw = torch.empty_like(x), torch.empty_like(w)
-        db = torch.empty((c,), dtype=torch.float32, device=x.device)
-        ws = self._bws()
-        _check(self.lib.cd_op_conv_transpose_backward(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                                      db.data_ptr(), B, c, _i32x3((D, H, W)), kernel_z, stride_z, _i32x3(out_pad),
-                                                      ws.data_ptr(), ws.numel(), _stream()))
-        return dx, dw, db
-
-    def group_norm_backward(self, x_cl, gamma, beta, dy_cl, groups, silu=False, want_dadd=False):
-        x, dy = _dev32(x_cl, "x"), _dev32(dy_cl, "dy")
-        B, Cc = x.shape[0], x.shape[-1]
-        vox = int(np.prod(x.shape[1:-1]))
-        dx, dg, db = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta)
-        dadd = torch.empty((B, Cc), dtype=torch.float32, device=x.device) if want_dadd else None
-        ws = self._bws()
-        _check(self.lib.cd_op_group_norm_backward(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(), dx.data_ptr(),
-                                                  dg.data_ptr(), db.data_ptr(), _ptr(dadd), B, Cc, vox, groups, int(silu),
-                                                  ws.data_ptr(), ws.numel(), _stream()))
-        return dx, dg, db, dadd
-
-    _RES_KEYS = ("block1.proj.conv.weight", "block1.proj.conv.bias", "block1.norm.weight", "block1.norm.bias",
-                 "block2.proj.conv.weight", "block2.proj.conv.bias", "block2.norm.weight", "block2.norm.bias",
-                 "mlp.1.weight", "mlp.1.bias", "res_conv.conv.weight", "res_conv.conv.bias")
-
-    def resnet_block(self, x_cl, sd: Dict[str, torch.Tensor], cond=None, groups=8, x1_cl=None):
-        """ResnetBlock on channels-last input; ``sd`` uses the reference's key names (models.py:172-200)."""
-        x = _dev32(x_cl, "x")
-        B, D, H, W, c0 = x.shape
-        c1 = 0 if x1_cl is None else x1_cl.shape[-1]
-        cout = sd["block1.proj.conv.weight"].shape[0]
-        ptrs = (_P * 12)(*[(sd[k].data_ptr() if k in sd else None) for k in self._RES_KEYS])
-        y = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device)
-        nbytes = self.lib.cd_op_scratch_bytes(B, max(c0 + c1, cout), D * H * W) + 4 * B * D * H * W * cout * 4 * 4
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _check(self.lib.cd_op_resnet_block(x.data_ptr(), c0, _ptr(x1_cl), c1, ptrs, _ptr(cond), y.data_ptr(), B, cout,
-                                           _i32x3((D, H, W)), groups, ws.data_ptr(), ws.numel(), _stream()))
-        return y
-
-    _ATTN_KEYS = ("fn.norm.weight", "fn.norm.bias", "fn.fn.to_qkv.conv.weight", "fn.fn.to_out.0.conv.weight",
-                  "fn.fn.to_out.0.conv.bias", "fn.fn.to_out.1.weight", "fn.fn.to_out.1.bias")
-
-    def linear_attention(self, x_cl, sd: Dict[str, torch.Tensor]):
-        """Residual(PreNorm(LinearAttention)) on channels-last input (models.py:281-329)."""
-        x = _dev32(x_cl, "x")
-        B, D, H, W, c = x.shape
-        ptrs = (_P * 7)(*[sd[k].data_ptr() for k in self._ATTN_KEYS])
-        y = torch.empty_like(x)
-        nbytes = self.lib.cd_op_scratch_bytes(B, 96, D * H * W) + 4 * B * D * H * W * 96 * 4
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _check(self.lib.cd_op_linear_attention(x.data_ptr(), ptrs, y.data_ptr(), B, c, _i32x3((D, H, W)), ws.data_ptr(),
-                                               ws.numel(), _stream()))
-        return y

@@ -96,15 +96,11 @@ def fpd_index_lists(n_real, n_gen, batch_sizes, num_batches=20, seed=42):
 
 # ---- step 3: the moments (device) -----------------------------------------------------------------------------------------
 
-_workspaces = {}  # device index -> uint8 tensor, grown on demand
+_workspaces = engine.WorkspaceCache()  # kind: the device index; grown on demand
 
 
 def _workspace(device, nbytes):
-    ws = _workspaces.get(device.index)
-    if ws is None or ws.numel() < nbytes:
-        _workspaces.pop(device.index, None)
-        ws = _workspaces[device.index] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    return ws
+    return _workspaces.get(device.index, (), device, nbytes)
 
 
 def moments_workspace_bytes(d, sets, max_count):

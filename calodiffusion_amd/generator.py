@@ -420,7 +420,7 @@ class Generator:
         # 'geometry': None (a regular grid), 'hgcal' or 'radial' (Dataset 0 / 1); 'form': 0 converted at the end of the run, 1 the
         # converter inside the model; 'state_shape': the sampler's per-sample state
         self.geometry = dict(geometry=(None, "hgcal", "radial")[geo[0]], form=int(geo[1]), state_shape=tuple(int(v) for v in geo[3:3 + geo[2]]))
-        self._ws = {}
+        self._ws = engine.WorkspaceCache()
 
     def __del__(self):
         try:
@@ -437,12 +437,7 @@ class Generator:
 
     def workspace(self, batch: int) -> torch.Tensor:
         """One workspace kept: the last batch size asked for."""
-        ws = self._ws.get(int(batch))
-        if ws is None:
-            self._ws = {}
-            ws = torch.empty(self.workspace_bytes(batch), dtype=torch.uint8, device="cuda")
-            self._ws = {int(batch): ws}
-        return ws
+        return self._ws.get("run", (int(batch),), "cuda", lambda: self.workspace_bytes(batch))
 
     def run(self, E, layers=None, seed: int = 1234, offset: int = 0, shard=None, normalised: bool = True, workspace=None,
             sparse_decoding: bool = False, sparse_per_batch: bool = False, decode_seed: int = 1234, decode_offset: int = 0):

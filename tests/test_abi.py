@@ -1,5 +1,5 @@
-"""CPU: the three descriptions of the C ABI -- include/calodiff.h, the ctypes binding in calodiffusion_amd/engine.py and the
-stub INTEGRATION.md shows a reference maintainer -- must agree on struct layouts and argument lists.  (A binder following a
+"""CPU: the three descriptions of the C ABI -- include/calodiff.h, the ctypes binding in calodiffusion_amd/abi.py (reached here, as
+everywhere, through calodiffusion_amd.engine) and the stub INTEGRATION.md shows a reference maintainer -- must agree on struct layouts and argument lists.  (A binder following a
 stale INTEGRATION.md hands cd_plan_create a struct of the wrong size; round 2 shipped exactly that.)"""
 import ctypes as C
 import os
