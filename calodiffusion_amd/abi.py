@@ -63,6 +63,13 @@ class CdHlfDesc(C.Structure):
                 ("eta", C.POINTER(C.c_double)), ("phi", C.POINTER(C.c_double)), ("with_centres", C.POINTER(C.c_int32))]
 
 
+class CdShowerStatsDesc(C.Structure):
+    """Host tables of one shower geometry (cd_shower_stats_create copies them to the device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_layers", C.c_int32), ("n_cells", C.c_int32), ("n_rbins", C.c_int32),
+                ("n_abins", C.c_int32), ("r_bin", C.POINTER(C.c_int32)), ("a_bin", C.POINTER(C.c_int32)),
+                ("r_coord", C.POINTER(C.c_double)), ("angle", C.POINTER(C.c_double))]
+
+
 class CdGeneratorRun(C.Structure):
     """The arguments of cd_generator_run_ex."""
     _fields_ = [("struct_size", C.c_uint32), ("batch", C.c_int32), ("energy", C.c_void_p), ("energy_is_normalised", C.c_int32),
@@ -169,6 +176,10 @@ _SIGNATURES = {
     "cd_hlf_create": (C.c_int, [C.POINTER(CdHlfDesc), C.POINTER(_P), _P]),
     "cd_hlf_destroy": (C.c_int, [_P]),
     "cd_hlf_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "cd_shower_stats_create": (C.c_int, [C.POINTER(CdShowerStatsDesc), C.POINTER(_P), _P]),
+    "cd_shower_stats_destroy": (C.c_int, [_P]),
+    "cd_shower_stats_compute": (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    "cd_threshold_conserve": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_float, _P]),
     "cd_fpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "cd_fpd_moments": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_kpd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -102,8 +102,15 @@ class Diffusion(torch.nn.Module, ABC):
 
     def generate(self, data_loader, sample_steps: int, debug: bool = False, sample_offset: Optional[int] = 0,
                  sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False,
-                 reverse_norm: Optional[Callable] = None, geometry=None):
+                 reverse_norm: Optional[Callable] = None, geometry=None, emin: Optional[float] = None):
         """Sampling loop over a loader of (E, layers, data) batches (diffusion.py:118-197).
+
+        ``emin`` = a cell threshold in physical units: the energy-conserving cut the reference's inference.py:293-295 applies to
+        the physical showers (``utils.threshold_conserveE`` on the device), per row of the last axis of SHAPE_FINAL (HGCal: of
+        the returned cells).  None (default): no cut.  The cut needs the regular grid (flat or plot-shaped: layers x alpha x r
+        elements a shower) or HGCal's cells: it is refused, before sampling, for normalised-space showers and for the Dataset-0/1
+        device form, whose showers come back as the irregular SHAPE_ORIG voxels (the reference cuts those only after its
+        ``plot_reshape``); what a ``reverse_norm`` callable returns is checked when it returns.
 
         The inverse pre-processing (``utils.ReverseNorm``, diffusion.py:171-195) runs on the device for the regular-grid
         configs (``postprocess.ReverseNorm``: Dataset-2 / Dataset-3 shower maps; needs the EMAX / EMIN / logE / MAXDEP / ECUT
@@ -115,7 +122,7 @@ class Diffusion(torch.nn.Module, ABC):
         themselves and needs no ``geometry``.  ``geometry`` = a ``geom1.GeomConverter`` or ``NNConverter`` (typically
         ``model.NN_embed``): a Dataset-0/1 config ends in physical showers shaped SHAPE_ORIG (``cd_reverse_norm_ds1``).
         """
-        self._physical_form(reverse_norm, geometry)  # raises NOW, not after minutes of sampling, if there is no inverse pre-processing
+        self._check_cut(emin, self._physical_form(reverse_norm, geometry))  # both raise NOW, not after minutes of sampling
         generated, energies, layers = [], [], []
         for E, layers_, d_batch in data_loader:
             E = E.to(device=self.device)
@@ -127,7 +134,46 @@ class Diffusion(torch.nn.Module, ABC):
                 layers.append(layers_.detach().cpu().numpy())
         generated, energies = np.concatenate(generated), np.concatenate(energies)
         layers = np.concatenate(layers) if layers else None
-        return self._to_physical(generated, energies, layers, reverse_norm, debug, geometry, sparse_decoding, sparse_per_batch)
+        generated, energies = self._to_physical(generated, energies, layers, reverse_norm, debug, geometry, sparse_decoding, sparse_per_batch)
+        if emin is not None:
+            generated = self._energy_cut(generated, float(emin))
+        return generated, energies
+
+    def _check_cut(self, emin, form: str) -> None:
+        """generate(emin=) before the sampling loop: the cut is defined on physical showers of a regular grid or of HGCal cells."""
+        if emin is None:
+            return
+        if form == "none":
+            raise ValueError("generate(emin=) cuts physical showers; reverse_norm=False returns normalised-space showers")
+        if form == "device" and not self.hgcal and self.config.get("DATASET_NUM", 2) in (0, 1):
+            raise ValueError("generate(emin=) is not provided for Dataset 0 / 1: their showers come back as the irregular SHAPE_ORIG "
+                             "voxels, whose rows are not the r bins of a regular grid (the reference cuts them only after its "
+                             "plot_reshape); cut the converted showers with utils.threshold_conserveE")
+
+    def _energy_cut(self, generated: np.ndarray, emin: float, chunk: int = 16384) -> np.ndarray:
+        """inference.py:290-295 on physical showers: the rows of the last axis of SHAPE_FINAL (the plot shape of a grid) or of
+        HGCal's cells, cut and rescaled on the device, ``chunk`` showers at a time (as hlf.py uploads them: the set never has to
+        sit on the device); same shape back, float32, in the array itself where it is a writable contiguous float32 one."""
+        from .utils import threshold_conserveE
+        shape = tuple(generated.shape)
+        per_shower = int(np.prod(shape[1:])) if len(shape) > 1 else 0
+        if self.hgcal:
+            row = shape[-1] if len(shape) > 1 else 0
+        else:
+            row = int(self.config["SHAPE_FINAL"][-1])
+            grid = int(np.prod(self.config["SHAPE_FINAL"][-3:]))
+            if per_shower != grid:
+                raise ValueError(f"generate(emin=): the showers of shape {shape} are not the regular grid of SHAPE_FINAL ({grid} elements a "
+                                 f"shower, rows of {row}); the cut is defined on that grid (Dataset 0 / 1: after the geometry conversion)")
+        if not 1 <= row <= 4096:
+            raise ValueError(f"generate(emin=): a row is the last axis and holds 1 to 4096 cells, got showers of shape {shape}")
+        in_place = generated.dtype == np.float32 and generated.flags.c_contiguous and generated.flags.writeable
+        out = generated if in_place else np.empty(shape, dtype=np.float32)
+        flat_in, flat_out = generated.reshape(shape[0], per_shower), out.reshape(shape[0], per_shower)
+        for lo in range(0, shape[0], int(chunk)):
+            part = torch.from_numpy(np.array(flat_in[lo:lo + int(chunk)], dtype=np.float32, order="C")).to(self.device)
+            flat_out[lo:lo + part.shape[0]] = threshold_conserveE(part.reshape(-1, row), emin).cpu().numpy().reshape(part.shape)
+        return out
 
     def _physical_form(self, reverse_norm, geometry=None) -> str:
         """Which inverse pre-processing generate() will apply: 'callable', 'device', or 'none' (reverse_norm=False).  Raises for

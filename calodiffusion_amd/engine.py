@@ -15,7 +15,7 @@ import torch
 
 from .abi import (CD_ABI_VERSION, CD_MAX_SIZES, EXPORTED_SYMBOLS, LIB_PATH, LOSS_TYPES, OBJECTIVES, SOP_DENOISE, SOP_DENOISE_PS,
                   SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD, TIME_KINDS, CdClassifierDesc, CdGeneratorRun, CdHlfDesc,
-                  CdLayerMlpDesc, CdSamplerOp, CdStep, CdUnetDesc, WorkspaceCache, _P, _SIGNATURES, _check,
+                  CdLayerMlpDesc, CdSamplerOp, CdShowerStatsDesc, CdStep, CdUnetDesc, WorkspaceCache, _P, _SIGNATURES, _check,
                   _check_built_from_these_sources, _dev32, _i32x3, _ptr, _stream, get_conv_precision, load_library, profile_begin,
                   profile_end, randn, require_gpu, set_conv_precision)
 from .ops import Ops

@@ -215,10 +215,11 @@ class LayerDiffusion(CaloDiffusion):
         return out
 
     def generate(self, data_loader, sample_steps: int, debug: bool = False, sample_offset: Optional[int] = 0,
-                 sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False, reverse_norm=None, geometry=None):
-        """layerdiffusion.py:171-235: no layer energies are taken from the loader, the layer model generates them.  ``geometry``:
-        as for ``Diffusion.generate``."""
-        self._physical_form(reverse_norm, geometry)  # raise before sampling if this config has no inverse pre-processing here
+                 sparse_decoding: Optional[bool] = False, sparse_per_batch: Optional[bool] = False, reverse_norm=None, geometry=None,
+                 emin: Optional[float] = None):
+        """layerdiffusion.py:171-235: no layer energies are taken from the loader, the layer model generates them.  ``geometry``
+        and ``emin``: as for ``Diffusion.generate``."""
+        self._check_cut(emin, self._physical_form(reverse_norm, geometry))  # raise before sampling, not after it
         self._layer_dim()
         generated, energies, layers = [], [], []
         for E, _, _d in data_loader:
@@ -229,4 +230,7 @@ class LayerDiffusion(CaloDiffusion):
             layers.append(out["layers"].detach().cpu().numpy())
             energies.append(E.detach().cpu().numpy())
         generated, energies, layers = np.concatenate(generated), np.concatenate(energies), np.concatenate(layers)
-        return self._to_physical(generated, energies, layers, reverse_norm, False, geometry, sparse_decoding, sparse_per_batch)
+        generated, energies = self._to_physical(generated, energies, layers, reverse_norm, False, geometry, sparse_decoding, sparse_per_batch)
+        if emin is not None:
+            generated = self._energy_cut(generated, float(emin))
+        return generated, energies

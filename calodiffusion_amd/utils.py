@@ -77,6 +77,43 @@ def load_attr(type_: Literal["sampler", "loss"], algo_name: str):
         raise ValueError("%s '%s' is not supported: %s" % (type_, algo_name, e))
 
 
+def _conserve(who: str, generated: torch.Tensor, mask, emin: float) -> torch.Tensor:
+    from . import engine
+    lib = engine.load_library()
+    engine.require_gpu()
+    if not isinstance(generated, torch.Tensor) or not generated.is_cuda:
+        raise RuntimeError(f"{who}: generated must be a CUDA(ROCm) tensor: calodiffusion_amd computes on the GPU only")
+    if generated.dtype != torch.float32 or not generated.is_contiguous() or generated.dim() < 1:
+        raise ValueError(f"{who}: generated is changed in place and must be a contiguous float32 tensor, got {generated.dtype}, "
+                         f"contiguous {generated.is_contiguous()}")
+    row_len = int(generated.shape[-1])
+    if not 1 <= row_len <= 4096:
+        raise ValueError(f"{who}: a row is the last axis and holds 1 to 4096 cells, got {row_len}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != generated.device or mask.shape != generated.shape:
+            raise ValueError(f"{who}: mask must be a tensor of generated's shape on its device")
+        mask = (mask != 0).contiguous().view(torch.uint8)
+    with torch.cuda.device(generated.device):
+        engine._check(lib.cd_threshold_conserve(generated.data_ptr(), engine._ptr(mask), generated.numel() // row_len, row_len,
+                                                float(emin), engine._stream()))
+    return generated
+
+
+def apply_mask_conserveE(generated: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """``utils.apply_mask_conserveE`` of the reference (utils/utils.py:1021-1032) on a device tensor, in place
+    (``cd_threshold_conserve``): negatives become 0, the cells where ``mask`` is set become 0 and the others are rescaled so that
+    every ROW keeps its energy.  A row is the LAST axis, as in the reference: the name says layer energies, but on the (N, 1, L, A,
+    R) grid that is one (layer, alpha) row of R cells; for HGCal's (N, L, cells) it is the layer.  One deliberate difference: the
+    kept energy is summed directly in fp64, not formed as ``total - lost`` in float32, so a row with nothing kept is exactly 0."""
+    return _conserve("apply_mask_conserveE", generated, mask, 0.0)
+
+
+def threshold_conserveE(generated: torch.Tensor, emin: float) -> torch.Tensor:
+    """The ``--EMin`` cut of the reference's plot.py:99-101 and inference.py:293-295 on a device tensor, in place:
+    ``apply_mask_conserveE(generated, generated < emin)`` with the mask formed in the kernel (before negatives are clamped)."""
+    return _conserve("threshold_conserveE", generated, None, emin)
+
+
 def shard_batch(n: int, world_size: int, rank: int) -> slice:
     """Contiguous batch shard of rank `rank` (sampling needs no collective: showers are independent)."""
     base, rem = divmod(n, world_size)

@@ -746,6 +746,59 @@ int cd_hlf_destroy(CdHlf* hlf);
  * stream is not synchronised. */
 int cd_hlf_compute(const CdHlf* hlf, const float* showers, int batch, float threshold, double* out, int32_t* n_hits, void* stream);
 
+/* ---- shower statistics: what the plot program computes before it draws ------------------------------------------------
+ * The arithmetic of the reference's plot classes (calodiffusion/utils/plots.py): ELayer :567-576, SparsityLayer :684-692,
+ * AverageShowerWidth :461-518, AverageER :617-625, AverageEPhi :651-658, HistEtot :884-887, HistERatio :406-418, HistNhits
+ * :912-916, HistMaxE :1003-1010, HistMaxELayer :978-984, RadialEnergyHGCal :720-734, RCenterHGCal :748-779 and PhiCenterHGCal
+ * :810-839.  Each of them reshapes and sums the whole shower set again; here one pass over the showers leaves the raw sums
+ * they all derive from, and the divisions, masks and roots are the caller's, on (batch, layers) arrays.
+ *
+ * A shower is (n_layers, n_cells) fp32: a regular grid's (L, A x R) or HGCal's (L, max_ncell).  The geometry is four HOST
+ * tables of n_layers * n_cells entries, copied to the device by cd_shower_stats_create (the call allocates, and synchronises
+ * `stream`): r_bin in [-1, n_rbins) (-1: the cell is in no radial bin), a_bin in [-1, n_abins) or NULL with n_abins == 0,
+ * r_coord and angle (radians; the cosine and sine are tabulated here).  Cells beyond a layer's real cell count are ordinary
+ * cells.  Refused with CD_EINVAL, before anything touches the device: a struct_size other than sizeof(CdShowerStatsDesc),
+ * n_layers outside [1, 512], n_cells outside [1, 4096], n_rbins outside [1, 256], n_abins outside [0, 256], a null r_bin /
+ * r_coord / angle table, an a_bin table without n_abins or n_abins without a table, a bin index outside its range, a
+ * coordinate that is not finite.
+ * (Tag and typedef are declared apart because the struct holds pointers, as CdHlfDesc.) */
+struct CdShowerStatsDesc {
+  uint32_t struct_size;   /* = sizeof(CdShowerStatsDesc) */
+  int32_t n_layers;
+  int32_t n_cells;        /* cells per layer */
+  int32_t n_rbins;
+  int32_t n_abins;        /* 0 with a null a_bin */
+  const int32_t* r_bin;   /* [n_layers * n_cells] */
+  const int32_t* a_bin;   /* [n_layers * n_cells], nullable */
+  const double* r_coord;  /* [n_layers * n_cells] */
+  const double* angle;    /* [n_layers * n_cells] */
+};
+typedef struct CdShowerStatsDesc CdShowerStatsDesc;
+typedef struct CdShowerStats CdShowerStats;
+int cd_shower_stats_create(const CdShowerStatsDesc* desc, CdShowerStats** out, void* stream);
+int cd_shower_stats_destroy(CdShowerStats* stats);
+/* showers (batch, n_layers * n_cells) fp32 on the device.  Per shower and layer, with e the cell energies of the layer:
+ *   records (batch, n_layers, 6) fp64 = {sum e, max e, sum e r, sum e r^2, sum e cos(angle), sum e sin(angle)}
+ *   counts  (batch, n_layers, 2) int32 = {cells > hit_threshold, cells > sparsity_eps}    (fp32 against fp32, as NumPy
+ *                                        compares a float32 array with a Python float)
+ * and per shower, over all layers, r_profile (batch, n_rbins) and a_profile (batch, n_abins) fp64 = sum e of the cells of each
+ * bin; either may be NULL and is then not computed (a_profile must be NULL for a geometry without a_bin).
+ * Every shower element is read from memory once: a wave stages a layer of its showers in LDS while it takes the moment sums
+ * (lane j the cells j, j + 64, ... in ascending order, combined by a fixed tree), then the lane that owns a bin adds the bin's
+ * cells from LDS in ascending cell order, layer after layer.  Every sum is fp64, there are no atomics and no workspace, so the
+ * outputs of a shower are the same bits in any batch, at any position and in any call.  The grid is capped: any batch an int
+ * holds.  Nothing is allocated and the stream is not synchronised. */
+int cd_shower_stats_compute(const CdShowerStats* stats, const float* showers, int batch, float hit_threshold, float sparsity_eps,
+                            double* records, int32_t* counts, double* r_profile, double* a_profile, void* stream);
+/* utils.apply_mask_conserveE of the reference (calodiffusion/utils/utils.py:1021-1032), the --EMin cut of plot.py:99-101 and
+ * inference.py:293-295, in place on x (rows, row_len) fp32 on the device, a row being the LAST axis of the reference's array.
+ * Per row: negatives are clamped to 0; a cell is dropped where mask (rows, row_len) uint8 is non-zero, or with a NULL mask where
+ * the value before the clamp is < emin; T = the sum of the clamped row and K = the sum of its kept cells, both fp64; dropped
+ * cells become 0 and kept cells are multiplied by (T + 1e-10) / (K + 1e-10) rounded once to fp32.  K is summed directly where
+ * the reference forms T - lost in fp32, so a row with nothing kept is exactly zero.  emin is ignored with a mask.  16 lanes
+ * take a row; row_len in [1, 4096].  Nothing is allocated and the stream is not synchronised. */
+int cd_threshold_conserve(float* x, const uint8_t* mask, int64_t rows, int row_len, float emin, void* stream);
+
 /* ---- Frechet physics distance: bootstrap moments of the feature matrix ----------------------------------------------
  * What the reference's FDP hands to jetnet.evaluation.fpd (train/evaluate.py:66-79) is a feature matrix per shower set; the
  * distance bootstraps the mean and covariance of row samples drawn with replacement.  cd_fpd_moments computes them for `sets`
