@@ -160,6 +160,9 @@ _SIGNATURES = {
     "cd_adam_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int, _P]),
     "cd_train_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "cd_train_step_target": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "cd_ode_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, _P]),
+    "cd_ema_step": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_double, _P]),
     "cd_plan_vjp_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "cd_denoise_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "cd_plan_bns_workspace_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -206,6 +209,7 @@ _SIGNATURES = {
     "cd_loss_hybrid": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "cd_op_to_channels_last": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P]),
     "cd_op_to_ncdhw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P]),
+    "cd_op_axpy_sigma": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, _P]),
     "cd_op_cyl_conv": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P]),
     "cd_op_zslide_conv": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,

@@ -20,7 +20,7 @@ LIBDIR = os.path.join(HERE, "lib")
 TAG = os.environ.get("CD_BUILD_TAG", "")
 LIB = os.path.join(LIBDIR, f"libcalodiff_hip{'_' + TAG if TAG else ''}.so")
 SOURCES = ["kernels_conv_flat16.hip", "kernels_conv_flat.hip", "kernels_conv_tiled.hip", "kernels_conv_transpose.hip", "kernels_pointwise.hip", "kernels_init_conv.hip", "kernels_init_pair.hip", "kernels_conv.hip", "kernels_conv_zs.hip", "kernels_attn.hip", "kernels_conv_small.hip", "kernels_deep.hip", "kernels_deep_side.hip", "kernels_wgrad16.hip", "kernels_gn.hip", "kernels_attn_unfused.hip", "kernels_embed.hip", "kernels_head.hip", "kernels_sampler.hip", "kernels_loss.hip", "kernels_preprocess.hip", "kernels_mlp.hip", "kernels_mlp_train.hip", "kernels_wgrad.hip", "kernels_gn_bwd.hip", "kernels_conv_bwd.hip", "kernels_attn_bwd.hip", "kernels_head_bwd.hip", "kernels_init_bwd.hip", "kernels_embed_bwd.hip", "profiler.hip", "plan.hip",
-           "forward.hip", "conv_backward.hip", "sampler.hip", "train.hip", "bns.hip", "ops.hip", "layer.hip", "adam.hip", "kernels_geom.hip", "kernels_geom_embed.hip", "kernels_radial.hip", "kernels_widen.hip", "generator.hip", "kernels_hlf.hip", "kernels_shower_stats.hip", "kernels_fpd.hip", "kernels_kpd.hip", "kernels_classifier.hip", "classifier.hip"]
+           "forward.hip", "conv_backward.hip", "sampler.hip", "train.hip", "bns.hip", "ops.hip", "layer.hip", "adam.hip", "kernels_distill.hip", "kernels_geom.hip", "kernels_geom_embed.hip", "kernels_radial.hip", "kernels_widen.hip", "generator.hip", "kernels_hlf.hip", "kernels_shower_stats.hip", "kernels_fpd.hip", "kernels_kpd.hip", "kernels_classifier.hip", "classifier.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 FLAGS += os.environ.get("CD_EXTRA_HIPCC_FLAGS", "").split()  # e.g. -DCD_ZS_EXPERIMENTS (tools/zs_stamps.sh, tools/zs_power.sh)

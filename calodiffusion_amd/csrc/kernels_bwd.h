@@ -19,7 +19,7 @@ int head_bwd_blocks(int batch, int64_t vox);
 // objective: CD_OBJ_* (objective_residual / objective_weight, kernels_loss.h); noise is only read for noise_pred
 void launch_head_loss_bwd(const float* x0, const float* data, const float* noise, const float* scal, const float* h, const float* wh,
                           float* dh, float* part, float* dwh, float* dbh, int batch, int64_t vox, hipStream_t s, int loss_type = 0,
-                          int objective = 0);
+                          int objective = 0, int res_objective = -1 /* the objective's own */);
 // the head's backward from the caller's dL/dD (cd_denoise_vjp): dh always; dWh / dbh only when part != null
 void launch_head_vjp(const float* gy, const float* scal, const float* h, const float* wh, float* dh, float* part, float* dwh, float* dbh,
                      int batch, int64_t vox, int objective, hipStream_t s);

@@ -11,19 +11,21 @@ namespace cd {
 //   L = sum_b w_b sum_v (x0 - data)^2 / (mean(w) * B * per),  x0 = c_skip*x + c_out*F,  F = sum_c Wh[c]*h[v][c] + bh
 //   dF = 2 w_b (x0 - data) c_out[b] / (mean(w) B per);  dh[v][c] = dF*Wh[c];  dWh[c] = sum dF*h[v][c];  dbh = sum dF
 // part: [blocks][33] partial sums (32 weights + bias)
+// res_objective: the objective whose residual and weight the loss takes, the plan's own (== objective) in cd_train_step;
+// kResidualOnOutput with `data` the given target in cd_train_step_target (x0 - target, weight 1; the chain stays objective's)
 // ------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) head_loss_bwd_kernel(const float* __restrict__ x0, const float* __restrict__ data,
                                                             const float* __restrict__ noise,
                                                             const float* __restrict__ scal, const float* __restrict__ h,
                                                             const float* __restrict__ wh, float* __restrict__ dh,
                                                             float* __restrict__ part, int batch, int64_t vox, int loss_type,
-                                                            int objective) {
+                                                            int objective, int res_objective) {
   __shared__ float sW[32];
   __shared__ float sAcc[8][33];
   __shared__ float sNorm;
   const int tid = threadIdx.x, sub = tid & 7, grp = tid >> 3;
   if (tid < 32) sW[tid] = wh[tid];
-  if (tid == 0) sNorm = loss_grad_norm(scal, batch, vox, loss_type, objective);
+  if (tid == 0) sNorm = loss_grad_norm(scal, batch, vox, loss_type, res_objective);
   __syncthreads();
   const int64_t total = (int64_t)batch * vox;
   f32x4 aw = {0.f, 0.f, 0.f, 0.f};
@@ -33,7 +35,7 @@ __global__ void __launch_bounds__(256) head_loss_bwd_kernel(const float* __restr
     const float sg = scal[b * 4 + 3];
     // d pred / d F: c_out (hybrid), -sigma (noise_pred: out = x - sigma F and pred ~ out), 1 (mean_pred)
     const float chain = objective == 0 ? scal[b * 4 + 2] : (objective == 1 ? -sg : 1.0f);
-    const float dF = loss_grad_dF(sNorm, x0[i], data[i], objective == 1 ? noise[i] : 0.f, sg, chain, loss_type, objective);
+    const float dF = loss_grad_dF(sNorm, x0[i], data[i], res_objective == 1 ? noise[i] : 0.f, sg, chain, loss_type, res_objective);
     const f32x4 hv = *(const f32x4*)(h + (size_t)i * 32 + sub * 4);
     f32x4 o;
 #pragma unroll
@@ -93,10 +95,10 @@ int head_bwd_blocks(int batch, int64_t vox) {
 }
 void launch_head_loss_bwd(const float* x0, const float* data, const float* noise, const float* scal, const float* h, const float* wh,
                           float* dh, float* part, float* dwh, float* dbh, int batch, int64_t vox, hipStream_t s, int loss_type,
-                          int objective) {
+                          int objective, int res_objective) {
   const int nb = head_bwd_blocks(batch, vox);
   hipLaunchKernelGGL(head_loss_bwd_kernel, dim3(nb), dim3(256), 0, s, x0, data, noise, scal, h, wh, dh, part, batch, vox, loss_type,
-                     objective);
+                     objective, res_objective < 0 ? objective : res_objective);
   hipLaunchKernelGGL(head_grad_reduce_kernel, dim3(1), dim3(256), 0, s, part, nb, dwh, dbh);
   CD_HIP(hipGetLastError());
 }

@@ -28,6 +28,10 @@ __device__ __forceinline__ float objective_weight(int objective, int loss_type, 
   if (loss_type != 0 || objective == 1) return 1.0f;
   return objective == 0 ? 1.0f + 1.0f / (sg * sg) : 1.0f / (sg * sg);
 }
+// A given target (cd_train_step_target: consistency distillation): the residual is out - target and the weight 1 whatever the plan's
+// objective.  That is what objective 0 evaluates for every loss type but 'l2' when `data` holds the target, so the kernels take the
+// target where they take data and this value as the objective of the residual; d pred / d F stays the plan's own (c_out, -sigma, 1).
+constexpr int kResidualOnOutput = 0;
 // d loss / d x0 = norm * w_b * f'(d):  l2: 2 w d / (mean(w) N);  mse: 2 d / N;  l1: sign(d) / N;  huber: clamp(d, -1, 1) / N
 // (scal: (batch, 4), sigma in column 3; one thread of a workgroup evaluates the norm)
 __device__ __forceinline__ float loss_grad_norm(const float* scal, int batch, int64_t per, int loss_type, int objective) {

@@ -1,6 +1,7 @@
 // The cd_op_* primitives: single layers of the network (convolutions, GroupNorm, ResnetBlock, attention and their backward
 // passes) on caller-owned buffers, for the tests' layer-by-layer comparison with the reference.
 #include "plan_internal.h"
+#include "kernels_loss.h"
 
 namespace cd {
 
@@ -59,6 +60,13 @@ int cd_op_to_channels_last(const float* ncdhw, float* ndhwc, int batch, int chan
 }
 int cd_op_to_ncdhw(const float* ndhwc, float* ncdhw, int batch, int channels, int64_t voxels, void* stream) {
   return guarded([&] { launch_transpose_to_planar(ndhwc, ncdhw, batch, channels, voxels, (hipStream_t)stream); });
+}
+
+int cd_op_axpy_sigma(const float* data, const float* noise, const float* sigma, float* out, int batch, int64_t per, void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(data && noise && sigma && out && batch > 0 && batch <= 65535 && per > 0, "bad argument");
+    launch_axpy_sigma(data, noise, sigma, out, batch, per, (hipStream_t)stream);
+  });
 }
 
 int cd_op_cyl_conv(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias, float* y,

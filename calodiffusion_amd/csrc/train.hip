@@ -1,4 +1,4 @@
-// Training step and the denoise VJP (cd_train_step, cd_denoise_vjp): forward with a tape of saved activations, then the
+// Training step and the denoise VJP (cd_train_step, cd_train_step_target, cd_denoise_vjp): forward with a tape of saved activations, then the
 // backward pass.  Reference: TrainDiffusion.training_loop body (train/train_diffusion.py:52-63) =
 // Diffusion.compute_loss -> hybrid_weight.loss_function (loss.py:163-179) -> denoise -> CondUnet.forward, then
 // loss.backward().  torch autograd is replaced by the explicit chain below; gradients land in a flat buffer in the plan's
@@ -686,11 +686,16 @@ void finish_param_grads(CdPlan* p, Run& r, const TapedForward& f, float* g, cons
 }
 
 // loss + all parameter gradients.  Returns nothing; grads (flat) and loss_out are written on the stream.
+// target (cd_train_step_target; null in cd_train_step): the loss compares the denoiser's output with it instead of with what the
+// objective compares with -- residual out - target, weight 1 (kResidualOnOutput) -- in the same launches; the network's input
+// stays data + sigma * noise.
 void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, const float* sigma, const float* cond, double* loss_out,
-                     float* grads, hipStream_t s, int loss_type = 0) {
+                     float* grads, hipStream_t s, int loss_type = 0, const float* target = nullptr) {
   const CdUnetDesc& d = p->desc;
   const CdPlan::FlatEmbed* fe = p->flat();
   const int64_t vox = p->shapes[0].vox(), per = p->state_per();
+  const float* cmp = target ? target : data;
+  const int res_obj = target ? kResidualOnOutput : d.objective;
   Run r{&p->ws, s, B, d.groups};
   r.status = p->status_word;
   Grads G{p, grads};
@@ -704,8 +709,8 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
     if (!fe) { ha.x = f.xn; ha.scal = T.scal; ha.objective = d.objective; }
     launch_head(ha, s);
     if (fe) launch_embed_out(*fe, f.f_grid, f.xn, T.scal, d.objective, T.x0, nullptr, B, s);
-    launch_loss_partial(T.x0, data, noise, sigma, f.lpart, B, per, s, loss_type, d.objective);
-    launch_loss_final(f.lpart, sigma, loss_out, B, per, s, loss_type, d.objective);
+    launch_loss_partial(T.x0, cmp, noise, sigma, f.lpart, B, per, s, loss_type, res_obj);
+    launch_loss_final(f.lpart, sigma, loss_out, B, per, s, loss_type, res_obj);
   }
   BackwardState bs;
   begin_backward(p, r, bs);
@@ -714,8 +719,8 @@ void train_step_impl(CdPlan* p, int B, const float* data, const float* noise, co
     if (!r.dry()) launch_embed_cotangent(T.x0, data, noise, nullptr, T.scal, f.gf, B, per, loss_type, d.objective, s);
     embed_head_backward(p, r, f, G, bs, hpart);
   } else if (!r.dry()) {
-    launch_head_loss_bwd(T.x0, data, noise, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
-                         loss_type, d.objective);
+    launch_head_loss_bwd(T.x0, cmp, noise, T.scal, f.hf, p->raw(p->head_w), bs.g, hpart, G.at(p->head_w), G.at(p->head_b), B, per, s,
+                         loss_type, d.objective, res_obj);
   }
   float* g = body_backward(p, r, T, bs.g, G, bs.demb);
   // the embedding's encoder: its weight gradient (the input is data: no input gradient is wanted, the row program's goes to gf)
@@ -872,6 +877,22 @@ int cd_train_step(CdPlan* plan, int batch, const float* data, const float* noise
     dgrad_images(plan);
     plan->ws.reset((char*)workspace, workspace_bytes, false);
     train_step_impl(plan, batch, data, noise, sigma, cond, loss_out, grads, (hipStream_t)stream, loss_type);
+  });
+}
+
+int cd_train_step_target(CdPlan* plan, int batch, const float* data, const float* noise, const float* sigma, const float* cond,
+                         const float* target, int loss_type, double* loss_out, float* grads, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  return guarded([&] {
+    CD_REQUIRE(plan && data && noise && sigma && cond && target && loss_out && grads && workspace && batch > 0, "bad argument");
+    CD_REQUIRE(loss_type >= CD_LOSS_L1 && loss_type <= CD_LOSS_HUBER,
+               "loss_type must be one of CD_LOSS_L1 / MSE / HUBER: the weight of CD_LOSS_L2 has no meaning against a given target "
+               "(use CD_LOSS_MSE)");
+    CD_REQUIRE(!plan->flat(), "cd_train_step_target compares on the grid: a plan with a geometry embedding is not provided");
+    check_ready(plan, true);
+    dgrad_images(plan);
+    plan->ws.reset((char*)workspace, workspace_bytes, false);
+    train_step_impl(plan, batch, data, noise, sigma, cond, loss_out, grads, (hipStream_t)stream, loss_type, target);
   });
 }
 

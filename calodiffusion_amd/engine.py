@@ -435,6 +435,26 @@ class UnetEngine:
                                       LOSS_TYPES[loss_type], loss.data_ptr(), flat.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
         return loss, flat
 
+    def train_step_target(self, data, noise, sigma, cond, target, loss_type="mse"):
+        """train_step against a given target (cd_train_step_target: consistency distillation): the loss compares
+        denoise(data + sigma noise) with ``target`` (a constant of data's shape), residual out - target and weight 1 for every
+        objective; LOSS_TYPE mse / l1 / huber.  Returns (loss, flat gradient) as train_step does, from the same workspace."""
+        if loss_type == "l2":
+            raise ValueError("train_step_target: the weighted 'l2' loss has no meaning against a given target, use 'mse'")
+        data, noise, sigma, cond, B = self._loss_io(data, noise, sigma, cond, "train_step_target")
+        target = _dev32(target, "target")
+        if target.shape != data.shape:
+            raise ValueError(f"train_step_target: target {tuple(target.shape)} must have data's shape {tuple(data.shape)}")
+        self.sync_weights()
+        ws = self.train_workspace(B)
+        _, total = self.grad_layout()
+        flat = torch.empty(total, dtype=torch.float32, device=data.device)
+        loss = torch.empty((), dtype=torch.float64, device=data.device)
+        _check(self.lib.cd_train_step_target(self.plan, B, data.data_ptr(), noise.data_ptr(), sigma.data_ptr(), cond.data_ptr(),
+                                             target.data_ptr(), LOSS_TYPES[loss_type], loss.data_ptr(), flat.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream()))
+        return loss, flat
+
     def vjp_workspace(self, batch: int, with_param_grads: bool) -> torch.Tensor:
         """Workspace of cd_denoise_vjp."""
         mode = bool(with_param_grads)

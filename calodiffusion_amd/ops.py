@@ -1,5 +1,5 @@
-"""The primitive ops of the HIP library one at a time (``cd_op_*``): what the parity tests and the tools call.  No library code
-goes through here."""
+"""The primitive ops of the HIP library one at a time (``cd_op_*``): what the parity tests and the tools call; no library code
+goes through ``Ops``.  ``ode_step`` and ``ema_step`` wrap the two stateless calls of consistency distillation (``distill.py``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,6 +9,67 @@ import numpy as np
 import torch
 
 from .abi import WorkspaceCache, _P, _check, _dev32, _i32x3, _ptr, _stream, load_library, require_gpu
+
+
+def axpy_sigma(data, noise, sigma):
+    """data + sigma[b] * noise from the launch the training step forms its network input with (cd_op_axpy_sigma): the same bits."""
+    lib = load_library()
+    require_gpu()
+    data, noise, sigma = _dev32(data, "data"), _dev32(noise, "noise"), _dev32(sigma, "sigma").reshape(-1)
+    B = data.shape[0]
+    if noise.shape != data.shape or sigma.numel() != B or data.numel() == 0:
+        raise ValueError(f"axpy_sigma: noise {tuple(noise.shape)} must have data's shape {tuple(data.shape)} and sigma B elements")
+    out = torch.empty_like(data)
+    _check(lib.cd_op_axpy_sigma(data.data_ptr(), noise.data_ptr(), sigma.data_ptr(), out.data_ptr(), B, data.numel() // B, _stream()))
+    return out
+
+
+def ode_step(x_hi, d_hi, sigma_hi, sigma_lo, x_e=None, d_e=None, out=None):
+    """One probability-flow ODE step from sigma_hi to sigma_lo, a noise level per sample (cd_ode_step): the Euler x_lo from
+    (x_hi, D_hi), or with (x_e, D_e) -- the Euler x_lo and the denoiser's output there -- the Heun x_lo.  ``out`` may be ``x_e``
+    (in place); a fresh tensor otherwise.  The first axis is the batch, the rest of a sample is one row of any length."""
+    lib = load_library()
+    require_gpu()
+    if (x_e is None) != (d_e is None):
+        raise ValueError("ode_step: x_e and d_e come together (Heun) or not at all (Euler)")
+    xs = [x_hi, d_hi] + ([x_e, d_e] if x_e is not None else []) + ([out] if out is not None else [])
+    for v in xs:
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == x_hi.shape):
+            raise ValueError("ode_step: contiguous float32 device tensors of one shape")
+    B = x_hi.shape[0]
+    sigma_hi, sigma_lo = _dev32(sigma_hi, "sigma_hi").reshape(-1), _dev32(sigma_lo, "sigma_lo").reshape(-1)
+    if sigma_hi.numel() != B or sigma_lo.numel() != B or B == 0 or x_hi.numel() == 0:
+        raise ValueError(f"ode_step: one sigma_hi and one sigma_lo per sample of x_hi {tuple(x_hi.shape)}")
+    if out is None:
+        out = torch.empty_like(x_hi)
+    _check(lib.cd_ode_step(x_hi.data_ptr(), d_hi.data_ptr(), _ptr(x_e), _ptr(d_e), sigma_hi.data_ptr(), sigma_lo.data_ptr(),
+                           out.data_ptr(), B, x_hi.numel() // B, _stream()))
+    return out
+
+
+def ema_step(dst, src, mu: float):
+    """dst[i] <- mu dst[i] + (1 - mu) src[i] over two lists of tensors in ceil(n / 48) launches (cd_ema_step); mu in [0, 1).
+    The tensors of ``dst`` are written through raw pointers: their versions are bumped, as FusedAdam does."""
+    lib = load_library()
+    require_gpu()
+    dst, src = list(dst), list(src)
+    if not 0.0 <= float(mu) < 1.0:
+        raise ValueError(f"ema_step: mu must lie in [0, 1), not {mu}")
+    if len(dst) != len(src):
+        raise ValueError("ema_step: as many source tensors as destinations")
+    for d, s in zip(dst, src):
+        for v in (d, s):
+            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+                raise ValueError("ema_step: contiguous float32 device tensors")
+        if d.shape != s.shape:
+            raise ValueError(f"ema_step: destination {tuple(d.shape)} and source {tuple(s.shape)} differ in shape")
+    n = len(dst)
+    if n == 0:
+        return
+    arr = lambda xs: (C.c_void_p * n)(*[x.data_ptr() for x in xs])  # noqa: E731
+    numel = (C.c_int64 * n)(*[d.numel() for d in dst])
+    _check(lib.cd_ema_step(n, arr(dst), arr(src), numel, float(mu), _stream()))
+    torch.autograd.graph.increment_version(dst)
 
 
 class Ops:

@@ -237,6 +237,30 @@ int cd_train_step(CdPlan* plan, int batch, const float* data, const float* noise
                   int loss_type /* CD_LOSS_* */, double* loss_out, float* grads, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* ---- consistency distillation (Song et al. 2023, Algorithm 2; calodiffusion_amd/distill.py) -------------------------- */
+/* cd_train_step against a given target: the network's input is data + sigma * noise as in cd_train_step, the loss compares
+ * out = denoise(data + sigma noise, sigma, cond) with `target` (B,1,D,H,W; a constant, never differentiated):
+ *   r = out - target;  loss = mean r^2 (CD_LOSS_MSE), mean |r| (CD_LOSS_L1), mean smooth_l1(r) (CD_LOSS_HUBER);  weight 1
+ * whatever the plan's objective; d out / d F is the objective's own (c_out, -sigma, 1), as in cd_denoise_vjp.  CD_LOSS_L2 is
+ * refused (its weight has no meaning here: use CD_LOSS_MSE), and so is a plan with a geometry embedding.  The taped forward, the
+ * backward, `grads` and the workspace (cd_plan_train_workspace_bytes) are cd_train_step's; with target == data on a
+ * CD_OBJ_HYBRID plan the launches are cd_train_step's and loss and grads are the same bits. */
+int cd_train_step_target(CdPlan* plan, int batch, const float* data, const float* noise, const float* sigma, const float* cond,
+                         const float* target, int loss_type /* CD_LOSS_L1 / MSE / HUBER */, double* loss_out, float* grads,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* One step of the probability-flow ODE from sigma_hi[b] down to sigma_lo[b], a noise level per sample, over `batch` rows of `per`
+ * floats (any `per`: rows need not start on a 16-byte boundary); one pass, no plan and no workspace.  D_hi = denoise(x_hi, sigma_hi):
+ *   Euler (x_e == d_e == NULL):  d = (x_hi - D_hi) / sigma_hi;  x_lo = x_hi + (sigma_lo - sigma_hi) d
+ *   Heun  (x_e the Euler x_lo, D_e = denoise(x_e, sigma_lo)):  d2 = (x_e - D_e) / sigma_lo;
+ *                                                              x_lo = x_hi + (sigma_lo - sigma_hi) (0.5 (d + d2))
+ * Every product, difference and quotient is rounded to fp32 on its own.  x_lo may be x_e (in place). */
+int cd_ode_step(const float* x_hi, const float* d_hi, const float* x_e /* nullable */, const float* d_e /* nullable */,
+                const float* sigma_hi, const float* sigma_lo, float* x_lo, int batch, int64_t per, void* stream);
+/* EMA of the target network over n tensors in ceil(n / 48) launches: dst[i] <- mu dst[i] + (1 - mu) src[i], mu in [0, 1)
+ * (1 - mu formed in double, as cd_adam_step forms 1 - beta).  dst / src are HOST arrays of n DEVICE pointers, numel their lengths;
+ * src is only read.  mu = 0 copies. */
+int cd_ema_step(int n, float* const* dst, const float* const* src, const int64_t* numel, double mu, void* stream);
+
 /* ---- differentiable denoise ------------------------------------------------------------------------------------------ */
 /* Workspace of cd_denoise_vjp at this batch: with_param_grads 0 sizes the input-gradient-only call (grads == NULL), which needs
  * less; 1 sizes the call that also writes grads.  Same restrictions as cd_plan_train_workspace_bytes. */
@@ -970,6 +994,9 @@ int cd_profile_end(char* json, int cap);
 /* ---- primitives (parity tests of the individual kernels; activations CHANNELS-LAST (B, D, H, W, C)) ---- */
 int cd_op_to_channels_last(const float* ncdhw, float* ndhwc, int batch, int channels, int64_t voxels, void* stream);
 int cd_op_to_ncdhw(const float* ndhwc, float* ncdhw, int batch, int channels, int64_t voxels, void* stream);
+/* out = data + sigma[b] * noise over `batch` rows of `per` floats: the launch with which cd_train_step, cd_train_step_target and
+ * cd_loss_hybrid form the network's input, for a caller that needs those bits outside them (distill.py: the teacher's input). */
+int cd_op_axpy_sigma(const float* data, const float* noise, const float* sigma, float* out, int batch, int64_t per, void* stream);
 /* phi-periodic Conv3d (CylindricalConv, models.py:65-96; Downsample, :360-365). w: torch layout (Cout,Cin,kD,kH,kW).
  * kernel (kD,kH,kW) in {(3,3,3),(3,4,4),(1,1,1)}; padding 1 (z,r zero; phi circular) unless 1x1x1.
  * x0/x1: two channel-concatenated sources (c1 may be 0).  scratch: >= cd_op_scratch_bytes(). */
