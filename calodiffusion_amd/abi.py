@@ -10,6 +10,7 @@ import ctypes as C
 import os
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -309,8 +310,54 @@ def _dev32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
+_NP_DTYPES = {torch.float32: np.float32, torch.float64: np.float64}
+
+
+def _upload(a, dtype: torch.dtype, name: str, need_gpu: bool = False, keep_device: bool = False) -> torch.Tensor:
+    """A NumPy array, sequence or tensor (host or device) as a contiguous device tensor of ``dtype``; the values are not touched.
+    A tensor is converted by torch in the move; anything else is converted by NumPy on the host and then uploaded.
+    ``need_gpu``: without a GPU the refusal names the argument (else it is torch's own).  ``keep_device``: a CUDA tensor
+    stays on its device (else everything lands on the current one)."""
+    if need_gpu and not torch.cuda.is_available():
+        raise RuntimeError(f"{name}: calodiffusion_amd computes on the GPU only and torch.cuda.is_available() is False")
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+        if a.dtype == object:
+            raise TypeError(f"{name} must be a numeric array")
+        # ("CW": torch wraps writable arrays only; a copy is made only where one is needed)
+        a = torch.from_numpy(np.require(a, _NP_DTYPES[dtype], "CW"))
+    return a.detach().to(device=a.device if keep_device and a.is_cuda else "cuda", dtype=dtype).contiguous()
+
+
 def _i32x3(v: Sequence[int]):
     return (C.c_int32 * 3)(*[int(a) for a in v])
+
+
+def _nbytes(sizing_fn, *args) -> int:
+    """What a ``cd_*_workspace_bytes(*args, size_t *out)`` entry point reports."""
+    n = C.c_size_t()
+    _check(sizing_fn(*args, C.byref(n)))
+    return n.value
+
+
+class Handle:
+    """A ``void*`` of the library: ``handle`` is null until a ``cd_*_create`` call fills it (``C.byref(self.handle)``), and is what
+    the C calls take.  ``destroy`` (the ``cd_*_destroy`` of its kind) is called at most once and never for a null handle, so an
+    owner whose create call failed frees nothing.  After ``close()`` the handle is null again."""
+
+    def __init__(self, destroy):
+        self.handle, self._destroy = C.c_void_p(), destroy
+
+    def close(self):
+        handle, self.handle = self.handle, C.c_void_p()
+        if handle:
+            self._destroy(handle)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter teardown: the library may be gone before its last handle
+            pass
 
 
 class WorkspaceCache:

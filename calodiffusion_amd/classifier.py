@@ -30,7 +30,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import engine
+from .abi import CdClassifierDesc, CdHlfDesc, _check, _dev32, _nbytes, _ptr, _stream, load_library, require_gpu
 
 MAX_DIM, MAX_LAYERS, MAX_BATCH, MAX_ROWS_PER_CALL = 4096, 8, 256, 65536  # CD_CLS_* of include/calodiff.h
 LEAKY_SLOPE = 0.01  # torch.nn.LeakyReLU()'s default, what the reference builds (:197)
@@ -39,34 +39,27 @@ LEAKY_SLOPE = 0.01  # torch.nn.LeakyReLU()'s default, what the reference builds 
 # ---- the device entry points --------------------------------------------------------------------------------------------------
 
 def _desc(input_dim, hidden, num_layer, slope=LEAKY_SLOPE, dropout=0.0):
-    return engine.CdClassifierDesc(C.sizeof(engine.CdClassifierDesc), int(input_dim), int(hidden), int(num_layer), float(slope), float(dropout))
+    return CdClassifierDesc(C.sizeof(CdClassifierDesc), int(input_dim), int(hidden), int(num_layer), float(slope), float(dropout))
 
 
-def _f32(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
-    return t
-
-
-def _i32(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1):
-        raise ValueError(f"{name} must be a contiguous 1-d int32 CUDA tensor")
+def _strict(t, name, dtype=torch.float32, ndim=None):
+    """``t`` as it is, if it is a contiguous CUDA tensor of ``dtype`` (and of ``ndim`` dimensions, where given)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and ndim in (None, t.dim())):
+        raise ValueError(f"{name} must be a contiguous {'' if ndim is None else f'{ndim}-d '}{str(dtype)[len('torch.'):]} CUDA tensor")
     return t
 
 
 def _weight_table(params):
-    return (C.c_void_p * len(params))(*[_f32(p, "a parameter").data_ptr() for p in params])
+    return (C.c_void_p * len(params))(*[_strict(p, "a parameter").data_ptr() for p in params])
 
 
 def workspace_bytes(desc, max_rows_per_call):
-    n = C.c_size_t()
-    engine._check(engine.load_library().cd_classifier_workspace_bytes(C.byref(desc), int(max_rows_per_call), C.byref(n)))
-    return n.value
+    return _nbytes(load_library().cd_classifier_workspace_bytes, C.byref(desc), int(max_rows_per_call))
 
 
 def num_params(desc):
     n = C.c_int64()
-    engine._check(engine.load_library().cd_classifier_num_params(C.byref(desc), C.byref(n)))
+    _check(load_library().cd_classifier_num_params(C.byref(desc), C.byref(n)))
     return n.value
 
 
@@ -77,31 +70,31 @@ def _workspace(desc, rows, device):
 def forward_logits(desc, params, x, idx=None, count=None, max_rows_per_call=4096, workspace=None):
     """``cd_classifier_forward``: eval-mode logits (count,) float32 of the rows ``idx`` (device int32) of ``x`` (rows, d), or of its
     first ``count`` rows (default: all)."""
-    x = _f32(x, "x")
-    count = (x.shape[0] if count is None else int(count)) if idx is None else _i32(idx, "idx").numel()
+    x = _strict(x, "x")
+    count = (x.shape[0] if count is None else int(count)) if idx is None else _strict(idx, "idx", torch.int32, 1).numel()
     with torch.cuda.device(x.device):
         out = torch.empty((count,), dtype=torch.float32, device=x.device)
         rows = max(1, min(int(max_rows_per_call), max(count, 1)))
         ws = _workspace(desc, rows, x.device) if workspace is None else workspace
-        engine._check(engine.load_library().cd_classifier_forward(
+        _check(load_library().cd_classifier_forward(
             C.byref(desc), _weight_table(params), x.data_ptr(), x.shape[0], None if idx is None else idx.data_ptr(), count, out.data_ptr(),
-            rows, ws.data_ptr(), ws.numel(), engine._stream()))
+            rows, ws.data_ptr(), ws.numel(), _stream()))
     return out
 
 
 def train_step(desc, params, x, labels, batch_idx, seed, step, grads, adam=None, workspace=None):
     """``cd_classifier_train_step``: the flat gradient into ``grads`` and the loss as a (1,) float64 device tensor.  ``adam``:
     None, or ``(exp_avg, exp_avg_sq, lr, beta1, beta2, eps, adam_step)`` to apply the update."""
-    x, labels, grads = _f32(x, "x"), _f32(labels, "labels"), _f32(grads, "grads")
-    batch = _i32(batch_idx, "batch_idx").numel()
+    x, labels, grads = _strict(x, "x"), _strict(labels, "labels"), _strict(grads, "grads")
+    batch = _strict(batch_idx, "batch_idx", torch.int32, 1).numel()
     with torch.cuda.device(x.device):
         loss = torch.empty((1,), dtype=torch.float64, device=x.device)
         ws = _workspace(desc, max(batch, 1), x.device) if workspace is None else workspace
         m, v, lr, b1, b2, eps, k = adam if adam is not None else (None, None, 0.0, 0.9, 0.999, 1e-8, 1)
-        engine._check(engine.load_library().cd_classifier_train_step(
+        _check(load_library().cd_classifier_train_step(
             C.byref(desc), _weight_table(params), x.data_ptr(), labels.data_ptr(), x.shape[0], batch_idx.data_ptr(), batch, int(seed), int(step),
-            grads.data_ptr(), loss.data_ptr(), int(adam is not None), engine._ptr(m), engine._ptr(v), float(lr), float(b1), float(b2), float(eps),
-            int(k), ws.data_ptr(), ws.numel(), engine._stream()))
+            grads.data_ptr(), loss.data_ptr(), int(adam is not None), _ptr(m), _ptr(v), float(lr), float(b1), float(b2), float(eps),
+            int(k), ws.data_ptr(), ws.numel(), _stream()))
     return loss
 
 
@@ -109,52 +102,52 @@ def train_epoch(desc, params, x, labels, perm, batch_size, seed, first_step, gra
                 workspace=None):
     """``cd_classifier_train_epoch``: every batch of ``perm`` (device int32) as a training step with Adam, all enqueued on the
     current stream; the per-step losses as a float64 device tensor."""
-    x, labels, grads = _f32(x, "x"), _f32(labels, "labels"), _f32(grads, "grads")
-    n_train = _i32(perm, "perm").numel()
+    x, labels, grads = _strict(x, "x"), _strict(labels, "labels"), _strict(grads, "grads")
+    n_train = _strict(perm, "perm", torch.int32, 1).numel()
     steps = -(-n_train // int(batch_size)) if int(batch_size) > 0 else 0
     with torch.cuda.device(x.device):
         losses = torch.empty((max(steps, 1),), dtype=torch.float64, device=x.device)
         ws = _workspace(desc, max(1, min(int(batch_size), MAX_BATCH)), x.device) if workspace is None else workspace
-        engine._check(engine.load_library().cd_classifier_train_epoch(
+        _check(load_library().cd_classifier_train_epoch(
             C.byref(desc), _weight_table(params), x.data_ptr(), labels.data_ptr(), x.shape[0], perm.data_ptr(), n_train, int(batch_size),
-            int(seed), int(first_step), grads.data_ptr(), _f32(exp_avg, "exp_avg").data_ptr(), _f32(exp_avg_sq, "exp_avg_sq").data_ptr(),
-            float(lr), float(betas[0]), float(betas[1]), float(eps), losses.data_ptr(), ws.data_ptr(), ws.numel(), engine._stream()))
+            int(seed), int(first_step), grads.data_ptr(), _strict(exp_avg, "exp_avg").data_ptr(), _strict(exp_avg_sq, "exp_avg_sq").data_ptr(),
+            float(lr), float(betas[0]), float(betas[1]), float(eps), losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return losses[:steps]
 
 
 def dropout_mask(seed, step, layer, p, rows, n, device="cuda"):
     """``cd_classifier_dropout_mask``: the (rows, n) uint8 mask (1 = kept) the training kernels apply at (seed, step, layer)."""
-    engine.require_gpu()
+    require_gpu()
     mask = torch.empty((int(rows), int(n)), dtype=torch.uint8, device=device)
     with torch.cuda.device(mask.device):
-        engine._check(engine.load_library().cd_classifier_dropout_mask(int(seed), int(step), int(layer), float(p), int(rows), int(n),
-                                                                       mask.data_ptr(), engine._stream()))
+        _check(load_library().cd_classifier_dropout_mask(int(seed), int(step), int(layer), float(p), int(rows), int(n),
+                                                         mask.data_ptr(), _stream()))
     return mask
 
 
 def linear_act(x, w, bias, act=True, slope=LEAKY_SLOPE, dropout=0.0, seed=0, step=0, layer=0):
     """``cd_op_linear_act``: dropout(act(x w^T + bias)), the forward layer kernel on its own."""
-    x, w = _f32(x, "x"), _f32(w, "w")
+    x, w = _strict(x, "x"), _strict(w, "w")
     with torch.cuda.device(x.device):
         y = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
-        engine._check(engine.load_library().cd_op_linear_act(
-            x.data_ptr(), w.data_ptr(), None if bias is None else _f32(bias, "bias").data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], w.shape[0],
-            int(bool(act)), float(slope), float(dropout), int(seed), int(step), int(layer), engine._stream()))
+        _check(load_library().cd_op_linear_act(
+            x.data_ptr(), w.data_ptr(), None if bias is None else _strict(bias, "bias").data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], w.shape[0],
+            int(bool(act)), float(slope), float(dropout), int(seed), int(step), int(layer), _stream()))
     return y
 
 
 def linear_act_backward(x, w, y, dy, mask=None, keep_scale=1.0, act=True, slope=LEAKY_SLOPE, need_dx=True):
     """``cd_op_linear_act_backward``: (dx or None, dw, db) for an arbitrary ``dy``; ``mask``: (rows, n_out) uint8 or None."""
-    x, w, y, dy = _f32(x, "x"), _f32(w, "w"), _f32(y, "y"), _f32(dy, "dy")
+    x, w, y, dy = _strict(x, "x"), _strict(w, "w"), _strict(y, "y"), _strict(dy, "dy")
     if mask is not None and not (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == y.shape):
         raise ValueError("mask must be a contiguous uint8 CUDA tensor of y's shape")
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x) if need_dx else None
         dw, db = torch.empty_like(w), torch.empty((w.shape[0],), dtype=torch.float32, device=x.device)
         ws = torch.empty((max(y.numel(), 4),), dtype=torch.float32, device=x.device)
-        engine._check(engine.load_library().cd_op_linear_act_backward(
-            x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), engine._ptr(mask), float(keep_scale), int(bool(act)), float(slope),
-            engine._ptr(dx), dw.data_ptr(), db.data_ptr(), x.shape[0], x.shape[1], w.shape[0], ws.data_ptr(), ws.numel() * 4, engine._stream()))
+        _check(load_library().cd_op_linear_act_backward(
+            x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), _ptr(mask), float(keep_scale), int(bool(act)), float(slope),
+            _ptr(dx), dw.data_ptr(), db.data_ptr(), x.shape[0], x.shape[1], w.shape[0], ws.data_ptr(), ws.numel() * 4, _stream()))
     return dx, dw, db
 
 
@@ -197,7 +190,7 @@ class DNN(torch.nn.Module):
         params = self.device_params()
         if not all(p.is_cuda for p in params):
             raise RuntimeError("DNN.forward: move the module to the device first (model.cuda())")
-        x = engine._dev32(x.detach(), "x")
+        x = _dev32(x.detach(), "x")
         if x.shape[0] == 0:
             return torch.empty((0, 1), dtype=torch.float32, device=x.device)
         return forward_logits(self.desc(), params, x).reshape(-1, 1)
@@ -428,7 +421,7 @@ class ClassifierTest:
         return np.random.default_rng(self.seed + epoch).permutation(self.split[0])
 
     def fit(self, features, labels, fractions=(0.7, 0.1, 0.2)):
-        engine.require_gpu()
+        require_gpu()
         feats = features.detach().cpu().numpy() if isinstance(features, torch.Tensor) else np.asarray(features)
         y = (labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).reshape(-1).astype(np.float32)
         if feats.ndim != 2 or feats.shape[1] != self.input_dim or feats.shape[0] != y.size:
@@ -501,8 +494,8 @@ def hgcal_features(showers, incident_E, xmap, ymap):
     coordinate tables ``xmap[:, :C]`` and ``ymap[:, :C]``, through ``cd_hlf_compute`` (one pass, fp64 sums).  An empty layer has
     centre and width 0, as the reference's masked division gives."""
     from .hlf import _E, _EC_ETA, _EC_PHI, _W_ETA, _W_PHI
-    lib = engine.load_library()
-    engine.require_gpu()
+    lib = load_library()
+    require_gpu()
     if isinstance(showers, torch.Tensor):
         sh = showers.detach()
     else:
@@ -519,17 +512,17 @@ def hgcal_features(showers, incident_E, xmap, ymap):
     eta, phi = np.ascontiguousarray(xs[:, :Cc]).reshape(-1), np.ascontiguousarray(ys[:, :Cc]).reshape(-1)
     offsets = (C.c_int32 * (L + 1))(*[l * Cc for l in range(L + 1)])
     centres = (C.c_int32 * L)(*([1] * L))
-    desc = engine.CdHlfDesc(C.sizeof(engine.CdHlfDesc), L, offsets, eta.ctypes.data_as(C.POINTER(C.c_double)),
-                            phi.ctypes.data_as(C.POINTER(C.c_double)), centres)
-    sh = engine._dev32(sh.cuda(), "showers").reshape(N, L * Cc)
+    desc = CdHlfDesc(C.sizeof(CdHlfDesc), L, offsets, eta.ctypes.data_as(C.POINTER(C.c_double)),
+                     phi.ctypes.data_as(C.POINTER(C.c_double)), centres)
+    sh = _dev32(sh.cuda(), "showers").reshape(N, L * Cc)
     with torch.cuda.device(sh.device):
         handle = C.c_void_p()
-        engine._check(lib.cd_hlf_create(C.byref(desc), C.byref(handle), engine._stream()))
+        _check(lib.cd_hlf_create(C.byref(desc), C.byref(handle), _stream()))
         try:
             out = torch.empty((N, L, 8), dtype=torch.float64, device=sh.device)
             hits = torch.empty((N, L), dtype=torch.int32, device=sh.device)
             if N:
-                engine._check(lib.cd_hlf_compute(handle, sh.data_ptr(), N, 0.0, out.data_ptr(), hits.data_ptr(), engine._stream()))
+                _check(lib.cd_hlf_compute(handle, sh.data_ptr(), N, 0.0, out.data_ptr(), hits.data_ptr(), _stream()))
             rec = out.cpu().numpy()
         finally:
             lib.cd_hlf_destroy(handle)

@@ -15,9 +15,10 @@ import torch
 
 from .abi import (CD_ABI_VERSION, CD_MAX_SIZES, EXPORTED_SYMBOLS, LIB_PATH, LOSS_TYPES, OBJECTIVES, SOP_DENOISE, SOP_DENOISE_PS,
                   SOP_LINCOMB, SOP_LINDIV, SOP_RANDN, SOP_RECORD, TIME_KINDS, CdClassifierDesc, CdGeneratorRun, CdHlfDesc,
-                  CdLayerMlpDesc, CdSamplerOp, CdShowerStatsDesc, CdStep, CdUnetDesc, WorkspaceCache, _P, _SIGNATURES, _check,
-                  _check_built_from_these_sources, _dev32, _i32x3, _ptr, _stream, get_conv_precision, load_library, profile_begin,
-                  profile_end, randn, require_gpu, set_conv_precision)
+                  CdLayerMlpDesc, CdSamplerOp, CdShowerStatsDesc, CdStep, CdUnetDesc, Handle, WorkspaceCache, _P, _SIGNATURES, _check,
+                  _check_built_from_these_sources, _dev32, _i32x3, _nbytes, _ptr, _stream, get_conv_precision, load_library,
+                  profile_begin, profile_end, randn, require_gpu, set_conv_precision)
+from .hgcal import HGCalConverter
 from .ops import Ops
 
 
@@ -56,13 +57,6 @@ def _program_io(start, program, n_steps: int, step_noise, debug: bool, what: str
     return xs, x0s, step_noise
 
 
-def _nbytes(sizing_fn, *args) -> int:
-    """What a ``cd_*_workspace_bytes(*args, size_t *out)`` entry point reports."""
-    n = C.c_size_t()
-    _check(sizing_fn(*args, C.byref(n)))
-    return n.value
-
-
 def unet_desc(unet, rz_input=False, phi_input=False, time_kind="raw", objective="hybrid", sigma_data=1.0, coords=None) -> CdUnetDesc:
     """The CdUnetDesc of a CondUnet under its ``_engine_opts`` (``coords`` is not part of it).  Needs no GPU."""
     d = CdUnetDesc()
@@ -95,8 +89,9 @@ def layer_mlp_desc(resnet, time_kind="raw", objective="hybrid", sigma_data=1.0) 
     return d
 
 
-class UnetEngine:
-    """One HIP plan bound to one CondUnet parameter set on one device."""
+class UnetEngine(Handle):
+    """One HIP plan bound to one CondUnet parameter set on one device; the plan is freed with the engine (``abi.Handle``)."""
+    plan = property(lambda self: self.handle)
 
     def __init__(self, unet, rz_input=False, phi_input=False, time_kind="raw", objective="hybrid", sigma_data=1.0,
                  coords=None):
@@ -106,9 +101,8 @@ class UnetEngine:
         d = self.desc = unet_desc(unet, rz_input, phi_input, time_kind, objective, sigma_data)
         self.grid = tuple(unet.grid)
         self.voxels = int(np.prod(self.grid))
-        handle = _P()
-        _check(self.lib.cd_plan_create(C.byref(d), C.byref(handle)))
-        self.plan = handle
+        super().__init__(self.lib.cd_plan_destroy)
+        _check(self.lib.cd_plan_create(C.byref(d), C.byref(self.handle)))
         self._weights_version = None
         self._weight_order = None  # [(state_dict name, tensor)] in the plan's order
         self._weight_ids = None
@@ -132,14 +126,6 @@ class UnetEngine:
     def for_unet(cls, unet):
         opts = getattr(unet, "_engine_opts", {})
         return cls(unet, **opts)
-
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                self.lib.cd_plan_destroy(self.plan)
-                self.plan = None
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ weights
     def _version(self):
@@ -165,7 +151,6 @@ class UnetEngine:
         ``encs[i].weight`` / ``decs[i].weight`` are gathered into two device buffers the plan reads in place.  An
         ``hgcal.HGCalConverter`` (cd_plan_set_geom): state (B, 1, layers, cells); the plan reads the converter's two packed maps,
         whose values follow a trainable converter's parameters.  Either is refreshed whenever a weight changed (sync_weights)."""
-        from .hgcal import HGCalConverter
         self._grad_layout = None
         self._ws.clear()
         self._embed_version = None

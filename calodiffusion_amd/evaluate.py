@@ -60,7 +60,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import engine
+from .abi import WorkspaceCache, _check, _stream, _upload, load_library, require_gpu
 from .hlf import HighLevelFeatures
 
 MAX_FEATURES = 256  # CD_FPD_MAX_D
@@ -96,7 +96,7 @@ def fpd_index_lists(n_real, n_gen, batch_sizes, num_batches=20, seed=42):
 
 # ---- step 3: the moments (device) -----------------------------------------------------------------------------------------
 
-_workspaces = engine.WorkspaceCache()  # kind: the device index; grown on demand
+_workspaces = WorkspaceCache()  # kind: the device index; grown on demand
 
 
 def _workspace(device, nbytes):
@@ -104,9 +104,9 @@ def _workspace(device, nbytes):
 
 
 def moments_workspace_bytes(d, sets, max_count):
-    nbytes = engine.load_library().cd_fpd_workspace_bytes(int(d), int(sets), int(max_count))
+    nbytes = load_library().cd_fpd_workspace_bytes(int(d), int(sets), int(max_count))
     if nbytes == 0:
-        engine._check(-1)
+        _check(-1)
     return nbytes
 
 
@@ -114,7 +114,7 @@ def launch_moments(x, centre, idx, counts, mean, cov, status, workspace=None):
     """One ``cd_fpd_moments`` call on the current stream, nothing allocated (unless ``workspace`` is None), nothing
     synchronised.  x (rows, d) float64, centre (d,) float64, idx (sets, idx_stride) int32, mean (sets, d), cov (sets, d, d)
     float64 and status (1,) int32: contiguous tensors on one device; counts: a sequence of ``sets`` ints (host)."""
-    lib = engine.load_library()
+    lib = load_library()
     sets, d = idx.shape[0], x.shape[1]
     for t, dt, name in ((x, torch.float64, "x"), (centre, torch.float64, "centre"), (idx, torch.int32, "idx"), (mean, torch.float64, "mean"),
                         (cov, torch.float64, "cov"), (status, torch.int32, "status")):
@@ -126,22 +126,21 @@ def launch_moments(x, centre, idx, counts, mean, cov, status, workspace=None):
     with torch.cuda.device(x.device):
         if workspace is None:
             workspace = _workspace(x.device, moments_workspace_bytes(d, sets, max(c_counts)))
-        engine._check(lib.cd_fpd_moments(x.data_ptr(), x.shape[0], d, centre.data_ptr(), idx.data_ptr(), idx.shape[1], c_counts, sets,
-                                         mean.data_ptr(), cov.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                         engine._stream()))
+        _check(lib.cd_fpd_moments(x.data_ptr(), x.shape[0], d, centre.data_ptr(), idx.data_ptr(), idx.shape[1], c_counts, sets,
+                                  mean.data_ptr(), cov.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                  _stream()))
 
 
-def _device_f64(a, name):
-    """A float64 (rows, d) tensor on the device: a CUDA tensor is cast, anything else is uploaded."""
-    if isinstance(a, torch.Tensor) and a.is_cuda:
-        t = a.detach().to(torch.float64)
-    else:
-        engine.require_gpu()
-        host = a.detach().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-        t = torch.from_numpy(np.array(host, dtype=np.float64, order="C")).cuda()
+def _feature_rows(a, name):
+    """A float64 (rows, d) tensor on the device: a CUDA tensor is cast where it is, anything else is uploaded."""
+    if not (isinstance(a, torch.Tensor) and a.is_cuda):
+        require_gpu()
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a, dtype=np.float64)  # (an object array of numbers is taken, as NumPy converts it)
+    t = _upload(a, torch.float64, name, keep_device=True)
     if t.dim() != 2:
         raise ValueError(f"{name}: expected a (rows, features) array, got shape {tuple(t.shape)}")
-    return t.contiguous()
+    return t
 
 
 def _pack_lists(index_lists, who="bootstrap_moments", least="a covariance needs at least 2 rows"):
@@ -171,10 +170,10 @@ def bootstrap_moments(x, index_lists, centre=None):
     float64 NumPy arrays.  ``x``: (rows, d), NumPy or CUDA tensor, cast to float64; lists may differ in length (at least 2
     entries each, duplicates allowed); ``centre`` (d,): the shift applied before the sums (default: the column mean of x).
     Raises ``ValueError`` naming the set and position of a row index outside x."""
-    x = _device_f64(x, "x")
+    x = _feature_rows(x, "x")
     idx, counts = _pack_lists(index_lists)
     with torch.cuda.device(x.device):
-        centre = x.mean(dim=0) if centre is None else _device_f64(np.asarray(centre).reshape(1, -1), "centre").reshape(-1)
+        centre = x.mean(dim=0) if centre is None else _feature_rows(np.asarray(centre).reshape(1, -1), "centre").reshape(-1)
         idx_d = torch.from_numpy(idx).to(x.device)
         sets, d = idx.shape[0], x.shape[1]
         mean = torch.empty((sets, d), dtype=torch.float64, device=x.device)
@@ -235,7 +234,7 @@ def _normalise(X, Y):
 def fpd(real_features, gen_features, min_samples=20_000, max_samples=50_000, num_batches=20, num_points=10, normalise=True, seed=42):
     """The Frechet physics distance of two feature arrays (rows, d), extrapolated to infinite sample size: (value, error).
     NumPy arrays or CUDA tensors, cast to float64; see the module docstring for the definition."""
-    X, Y = _device_f64(real_features, "real_features"), _device_f64(gen_features, "gen_features")
+    X, Y = _feature_rows(real_features, "real_features"), _feature_rows(gen_features, "gen_features")
     if X.shape[1] != Y.shape[1]:
         raise ValueError(f"fpd: {X.shape[1]} real and {Y.shape[1]} generated features")
     if not 1 <= X.shape[1] <= MAX_FEATURES:
@@ -298,9 +297,9 @@ def kpd_index_lists(n_real, n_gen, num_batches=10, batch_size=5000, seed=42):
 
 
 def kpd_workspace_bytes(sets, max_count):
-    nbytes = engine.load_library().cd_kpd_workspace_bytes(int(sets), int(max_count))
+    nbytes = load_library().cd_kpd_workspace_bytes(int(sets), int(max_count))
     if nbytes == 0:
-        engine._check(-1)
+        _check(-1)
     return nbytes
 
 
@@ -308,7 +307,7 @@ def launch_kpd_sums(x, idx, counts, gamma, degree, sums, status, workspace=None)
     """One ``cd_kpd_sums`` call on the current stream, nothing allocated (unless ``workspace`` is None), nothing synchronised.
     x (rows, d) float64, idx (sets, idx_stride) int32, sums (sets / 2, 3) float64 and status (1,) int32: contiguous tensors on
     one device; counts: a sequence of ``sets`` ints (host); set 2 k lists the real and set 2 k + 1 the generated rows of batch k."""
-    lib = engine.load_library()
+    lib = load_library()
     sets, d = idx.shape[0], x.shape[1]
     for t, dt, name in ((x, torch.float64, "x"), (idx, torch.int32, "idx"), (sums, torch.float64, "sums"), (status, torch.int32, "status")):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
@@ -319,8 +318,8 @@ def launch_kpd_sums(x, idx, counts, gamma, degree, sums, status, workspace=None)
     with torch.cuda.device(x.device):
         if workspace is None:
             workspace = _workspace(x.device, kpd_workspace_bytes(sets, max(c_counts)))
-        engine._check(lib.cd_kpd_sums(x.data_ptr(), x.shape[0], d, idx.data_ptr(), idx.shape[1], c_counts, sets, float(gamma), int(degree),
-                                      sums.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(), engine._stream()))
+        _check(lib.cd_kpd_sums(x.data_ptr(), x.shape[0], d, idx.data_ptr(), idx.shape[1], c_counts, sets, float(gamma), int(degree),
+                               sums.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream()))
 
 
 def kernel_sums(x, index_lists, gamma=None, degree=KPD_DEGREE):
@@ -328,7 +327,7 @@ def kernel_sums(x, index_lists, gamma=None, degree=KPD_DEGREE):
     ``(gamma a.b + 1)^degree``: over the ordered pairs of different positions of X, of Y, and over all pairs of one position of
     X and one of Y -- a (pairs, 3) float64 NumPy array, computed on the device.  ``gamma`` defaults to 1 / d.  Lists may differ in
     length (at least 2 entries each, duplicates allowed).  Raises ``ValueError`` naming the set and position of a row index outside x."""
-    x = _device_f64(x, "x")
+    x = _feature_rows(x, "x")
     idx, counts = _pack_lists(index_lists, "kpd", "a kernel sum needs at least 2 rows")
     if len(counts) % 2:
         raise ValueError(f"kpd: {len(counts)} index lists, they come in pairs (real, generated)")
@@ -355,7 +354,7 @@ def median_and_error(mmds):
 
 
 def _feature_pair(who, real_features, gen_features):
-    X, Y = _device_f64(real_features, "real_features"), _device_f64(gen_features, "gen_features")
+    X, Y = _feature_rows(real_features, "real_features"), _feature_rows(gen_features, "gen_features")
     if X.shape[1] != Y.shape[1]:
         raise ValueError(f"{who}: {X.shape[1]} real and {Y.shape[1]} generated features")
     if not 1 <= X.shape[1] <= MAX_FEATURES:
@@ -399,16 +398,16 @@ MAX_HISTOGRAM_EDGES = 64  # CD_HIST_MAX_EDGES: a workgroup keeps the edges and c
 
 
 def histogram_workspace_bytes(row_count, d, nedges):
-    nbytes = engine.load_library().cd_column_histograms_workspace_bytes(int(row_count), int(d), int(nedges))
+    nbytes = load_library().cd_column_histograms_workspace_bytes(int(row_count), int(d), int(nedges))
     if nbytes == 0:
-        engine._check(-1)
+        _check(-1)
     return nbytes
 
 
 def launch_column_histograms(x, row_begin, row_count, edges, counts, workspace=None):
     """One ``cd_column_histograms`` call on the current stream over rows [row_begin, row_begin + row_count) of x (rows, d)
     float64; edges (d, nedges) float64; counts (d, nedges - 1) int32, read as uint32: contiguous tensors on one device."""
-    lib = engine.load_library()
+    lib = load_library()
     for t, dt, name in ((x, torch.float64, "x"), (edges, torch.float64, "edges"), (counts, torch.int32, "counts")):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
             raise ValueError(f"launch_column_histograms: {name} must be a contiguous {dt} CUDA tensor")
@@ -420,14 +419,14 @@ def launch_column_histograms(x, row_begin, row_count, edges, counts, workspace=N
     with torch.cuda.device(x.device):
         if workspace is None:
             workspace = _workspace(x.device, histogram_workspace_bytes(row_count, d, edges.shape[1]))
-        engine._check(lib.cd_column_histograms(x.data_ptr(), int(row_begin), int(row_count), d, edges.data_ptr(), edges.shape[1], counts.data_ptr(),
-                                               workspace.data_ptr(), workspace.numel(), engine._stream()))
+        _check(lib.cd_column_histograms(x.data_ptr(), int(row_begin), int(row_count), d, edges.data_ptr(), edges.shape[1], counts.data_ptr(),
+                                        workspace.data_ptr(), workspace.numel(), _stream()))
 
 
 def column_histograms(x, edges, row_ranges=None):
     """``np.histogram(x[lo : lo + n, j], bins=edges[j])[0]`` for every column j and every ``(lo, n)`` of ``row_ranges`` (default: all
     rows), on the device: a (ranges, d, nedges - 1) int64 NumPy array.  ``x``: (rows, d) NumPy or CUDA tensor; ``edges`` (d, nedges)."""
-    x = _device_f64(x, "x")
+    x = _feature_rows(x, "x")
     edges = np.ascontiguousarray(edges, dtype=np.float64)
     d = x.shape[1]
     if edges.ndim != 2 or edges.shape[0] != d or edges.shape[1] < 2:

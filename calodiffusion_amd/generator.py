@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import engine
+from .abi import LIB_PATH, CdGeneratorRun, Handle, WorkspaceCache, _check, _dev32, _nbytes, _ptr, _stream, load_library, require_gpu
 
 MAGIC = b"CDGENBLB"
 FORMAT_VERSION = 1       # regular-grid files: written as they always were, byte for byte
@@ -43,9 +44,9 @@ def fnv1a64(data: bytes) -> int:
     """64-bit FNV-1a, the file's checksum: the library's loop (cd_generator_checksum, host code) when it is built, else the same
     loop in Python (a few seconds for a 10 MB file)."""
     data = bytes(data)
-    if os.path.exists(engine.LIB_PATH):
+    if os.path.exists(LIB_PATH):
         out = C.c_uint64()
-        engine._check(engine.load_library().cd_generator_checksum(data, len(data), C.byref(out)))
+        _check(load_library().cd_generator_checksum(data, len(data), C.byref(out)))
         return int(out.value)
     return fnv1a64_py(data)
 
@@ -397,7 +398,7 @@ def export_generator(model, sample_steps: int, sample_offset: int = 0, path: Opt
     return blob
 
 
-class Generator:
+class Generator(Handle):
     """``cd_generator_*`` for Python users: ``Generator(blob)`` (bytes or a path), ``.info``, ``.run(E, ...)``.  Needs the GPU."""
 
     INFO_KEYS = ("voxels", "layers", "energy_columns", "has_layer_stage", "takes_layers", "sample_steps", "layer_steps", "format_version")
@@ -407,33 +408,22 @@ class Generator:
             with open(blob, "rb") as fh:
                 blob = fh.read()
         blob = bytes(blob)
-        self.lib = engine.load_library()
-        engine.require_gpu()
-        handle = C.c_void_p()
-        engine._check(self.lib.cd_generator_create(blob, len(blob), C.byref(handle), engine._stream()))
-        self.handle = handle
+        self.lib = load_library()
+        require_gpu()
+        super().__init__(self.lib.cd_generator_destroy)
+        _check(self.lib.cd_generator_create(blob, len(blob), C.byref(self.handle), _stream()))
         info = (C.c_int32 * 8)()
-        engine._check(self.lib.cd_generator_info(self.handle, info))
+        _check(self.lib.cd_generator_info(self.handle, info))
         self.info = dict(zip(self.INFO_KEYS, (int(v) for v in info)))
         geo = (C.c_int32 * 8)()
-        engine._check(self.lib.cd_generator_geometry(self.handle, geo))
+        _check(self.lib.cd_generator_geometry(self.handle, geo))
         # 'geometry': None (a regular grid), 'hgcal' or 'radial' (Dataset 0 / 1); 'form': 0 converted at the end of the run, 1 the
         # converter inside the model; 'state_shape': the sampler's per-sample state
         self.geometry = dict(geometry=(None, "hgcal", "radial")[geo[0]], form=int(geo[1]), state_shape=tuple(int(v) for v in geo[3:3 + geo[2]]))
-        self._ws = engine.WorkspaceCache()
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.cd_generator_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        self._ws = WorkspaceCache()
 
     def workspace_bytes(self, batch: int) -> int:
-        n = C.c_size_t()
-        engine._check(self.lib.cd_generator_workspace_bytes(self.handle, int(batch), C.byref(n)))
-        return n.value
+        return _nbytes(self.lib.cd_generator_workspace_bytes, self.handle, int(batch))
 
     def workspace(self, batch: int) -> torch.Tensor:
         """One workspace kept: the last batch size asked for."""
@@ -447,13 +437,13 @@ class Generator:
         ``sparse_decoding`` / ``sparse_per_batch`` are ``generate()``'s, drawn from the decoder's own stream at (``decode_seed``,
         ``decode_offset``) -- ``Decoder.noise_seed`` / ``noise_offset`` -- and chained over batches like ``offset``."""
         cols = self.info["energy_columns"]
-        E = engine._dev32(E, "E")
+        E = _dev32(E, "E")
         if E.numel() % cols or (E.dim() > 1 and E.shape[-1] != cols):
             raise ValueError(f"E must have shape (batch, {cols}), not {tuple(E.shape)}")
         E = E.reshape(-1, cols)
         B = E.shape[0]
         if layers is not None:
-            layers = engine._dev32(layers, "layers")
+            layers = _dev32(layers, "layers")
             if tuple(layers.shape) != (B, self.info["layers"] + 1):
                 raise ValueError(f"layers must have shape ({B}, {self.info['layers'] + 1}), not {tuple(layers.shape)}")
         first, gb = (0, B) if shard is None else (int(shard[0]), int(shard[1]))
@@ -461,13 +451,13 @@ class Generator:
         showers = torch.empty((B, self.info["voxels"]), dtype=torch.float32, device=E.device)
         lout = torch.empty((B, self.info["layers"] + 1), dtype=torch.float32, device=E.device) if self.info["takes_layers"] else None
         nxt, dnxt = C.c_uint64(0), C.c_uint64(0)
-        args = engine.CdGeneratorRun(
-            struct_size=C.sizeof(engine.CdGeneratorRun), batch=B, energy=E.data_ptr(), energy_is_normalised=int(bool(normalised)),
-            sparse_mode=(2 if sparse_per_batch else 1) if sparse_decoding else 0, layers=engine._ptr(layers), seed=int(seed),
-            offset=int(offset), first_row=first, global_batch=gb, showers=showers.data_ptr(), layers_out=engine._ptr(lout),
+        args = CdGeneratorRun(
+            struct_size=C.sizeof(CdGeneratorRun), batch=B, energy=E.data_ptr(), energy_is_normalised=int(bool(normalised)),
+            sparse_mode=(2 if sparse_per_batch else 1) if sparse_decoding else 0, layers=_ptr(layers), seed=int(seed),
+            offset=int(offset), first_row=first, global_batch=gb, showers=showers.data_ptr(), layers_out=_ptr(lout),
             next_offset=C.pointer(nxt), decode_seed=int(decode_seed), decode_offset=int(decode_offset),
-            next_decode_offset=C.pointer(dnxt), workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=engine._stream())
-        engine._check(self.lib.cd_generator_run_ex(self.handle, C.byref(args)))
+            next_decode_offset=C.pointer(dnxt), workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=_stream())
+        _check(self.lib.cd_generator_run_ex(self.handle, C.byref(args)))
         if self.info["format_version"] == FORMAT_VERSION_GEOM:
             return showers, lout, int(nxt.value), int(dnxt.value)
         return showers, lout, int(nxt.value)

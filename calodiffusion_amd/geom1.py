@@ -21,37 +21,25 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import engine
+from .abi import Handle, _check, _ptr, _stream, _upload, load_library, require_gpu
 
 # the on-chip limits of cd_radial_create (include/calodiff.h)
 MAX_LAYERS, MAX_WEIGHT_FLOATS, MAX_ROW_FLOATS = 64, 8192, 6144
 
 
-def _to_device(x, name):
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{name}: calodiffusion_amd computes on the GPU only and torch.cuda.is_available() is False")
-    return torch.as_tensor(x).detach().to(device="cuda", dtype=torch.float32).contiguous()
-
-
-class _RadialMap:
+class _RadialMap(Handle):
     """Owner of one CdRadialMap handle; the four launches on raw device tensors."""
 
     def __init__(self, bound, alpha, rin, alpha_out, r_out):
-        self._lib = engine.load_library()
-        engine.require_gpu()
+        self._lib = load_library()
+        require_gpu()
+        super().__init__(self._lib.cd_radial_destroy)
         L = len(alpha)
         self.L, self.A, self.R, self.V = L, int(alpha_out), int(r_out), int(bound[-1])
         self.wtotal = self.R * int(sum(rin))
         i32 = lambda v: (C.c_int32 * len(v))(*[int(a) for a in v])  # noqa: E731
-        handle = C.c_void_p()
-        engine._check(self._lib.cd_radial_create(L, i32(bound), i32(alpha), i32(rin), self.A, self.R, C.byref(handle),
-                                                 engine._stream()))
-        self.handle = handle
-
-    def __del__(self):
-        if getattr(self, "handle", None):
-            self._lib.cd_radial_destroy(self.handle)
-            self.handle = None
+        _check(self._lib.cd_radial_create(L, i32(bound), i32(alpha), i32(rin), self.A, self.R, C.byref(self.handle),
+                                          _stream()))
 
     def _flat(self, x, name):
         if x.dim() != 2 or x.shape[1] != self.V:
@@ -73,14 +61,14 @@ class _RadialMap:
         self._flat(x, "enc"), self._weights(w, "enc")
         y = torch.empty((x.shape[0], 1, self.L, self.A, self.R), dtype=torch.float32, device=x.device)
         if y.numel():
-            engine._check(self._lib.cd_radial_enc(self.handle, w.data_ptr(), x.data_ptr(), y.data_ptr(), x.shape[0], engine._stream()))
+            _check(self._lib.cd_radial_enc(self.handle, w.data_ptr(), x.data_ptr(), y.data_ptr(), x.shape[0], _stream()))
         return y
 
     def dec(self, d, g):
         self._grid(g, "dec"), self._weights(d, "dec")
         x = torch.empty((g.shape[0], self.V), dtype=torch.float32, device=g.device)
         if x.numel():
-            engine._check(self._lib.cd_radial_dec(self.handle, d.data_ptr(), g.data_ptr(), x.data_ptr(), g.shape[0], engine._stream()))
+            _check(self._lib.cd_radial_dec(self.handle, d.data_ptr(), g.data_ptr(), x.data_ptr(), g.shape[0], _stream()))
         return x
 
     def enc_vjp(self, w, x, gy, want_dw):
@@ -88,8 +76,8 @@ class _RadialMap:
         dx = torch.empty_like(x)
         dw = (torch.empty_like(w) if x.shape[0] else torch.zeros_like(w)) if want_dw else None
         if x.shape[0]:
-            engine._check(self._lib.cd_radial_enc_vjp(self.handle, w.data_ptr(), x.data_ptr(), gy.data_ptr(), dx.data_ptr(),
-                                                      engine._ptr(dw), x.shape[0], engine._stream()))
+            _check(self._lib.cd_radial_enc_vjp(self.handle, w.data_ptr(), x.data_ptr(), gy.data_ptr(), dx.data_ptr(),
+                                               _ptr(dw), x.shape[0], _stream()))
         return dx, dw
 
     def dec_vjp(self, d, g, gx, want_dd):
@@ -97,8 +85,8 @@ class _RadialMap:
         dg = torch.empty_like(g)
         dd = (torch.empty_like(d) if g.shape[0] else torch.zeros_like(d)) if want_dd else None
         if g.shape[0]:
-            engine._check(self._lib.cd_radial_dec_vjp(self.handle, d.data_ptr(), g.data_ptr(), gx.data_ptr(), dg.data_ptr(),
-                                                      engine._ptr(dd), g.shape[0], engine._stream()))
+            _check(self._lib.cd_radial_dec_vjp(self.handle, d.data_ptr(), g.data_ptr(), gx.data_ptr(), dg.data_ptr(),
+                                               _ptr(dd), g.shape[0], _stream()))
         return dg, dd
 
 
@@ -200,12 +188,12 @@ class GeomConverter:
     def convert_flat(self, x):
         """flat showers (N, V) -> (N, L, alpha_out, dim_r_out): ``convert(reshape(x))`` in one launch."""
         rm = self.radial_map()
-        return rm.enc(self._fixed_weights()[0], _to_device(x, "convert_flat"))[:, 0]
+        return rm.enc(self._fixed_weights()[0], _upload(x, torch.float32, "convert_flat", need_gpu=True))[:, 0]
 
     def unconvert_flat(self, d):
         """(N, L, alpha_out, dim_r_out) (or with the channel axis) -> flat showers (N, V): ``unreshape(unconvert(d))`` in one launch."""
         rm = self.radial_map()
-        return rm.dec(self._fixed_weights()[1], _to_device(d, "unconvert_flat"))
+        return rm.dec(self._fixed_weights()[1], _upload(d, torch.float32, "unconvert_flat", need_gpu=True))
 
     def convert(self, d):
         return self.convert_flat(self.unreshape([torch.as_tensor(lay, dtype=torch.float32) for lay in d]))

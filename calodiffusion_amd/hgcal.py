@@ -23,15 +23,11 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import engine
+from .abi import Handle, _check, _dev32, _nbytes, _ptr, _stream, _upload, load_library
 from .postprocess import HGCAL_EMBED_PARAMS
 
 EPS = 1e-6  # the threshold of HGCalConverter.init's masks and of generate_sparse_mat (HGCal_utils.py:371, 607)
 _GEOM_COLUMNS, _GEOM_TRANSPOSED = 1, 2  # CD_GEOM_* of include/calodiff.h
-
-
-def _to_dev32(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().to(device="cuda", dtype=torch.float32).contiguous()
 
 
 def map_entries(mat, mask=None):
@@ -56,24 +52,23 @@ def map_entries(mat, mask=None):
     return row_ptr.astype(np.int32), np.concatenate(cols), np.concatenate(vals).astype(np.float32)
 
 
-class _PackedMap:
+class _PackedMap(Handle):
     """Owner of one CdGeomMap handle.  ``mask``: the pattern of a trainable map (``dense`` then holds the values, read at the
     masked entries only; see ``refresh``); without one the pattern is ``dense != 0``."""
 
     def __init__(self, dense: torch.Tensor, want_columns: bool, mask=None):
-        dense = _to_dev32(dense)
+        dense = _upload(dense, torch.float32, "dense")
         self.layers, self.rows, self.cols = (int(s) for s in dense.shape)
-        self._lib = engine.load_library()
-        handle = C.c_void_p()
+        self._lib = load_library()
+        super().__init__(self._lib.cd_geom_destroy)
         pattern = None
         if mask is not None:
-            pattern = _to_dev32(torch.as_tensor(mask) != 0)
+            pattern = _upload(torch.as_tensor(mask) != 0, torch.float32, "mask")
             if pattern.shape != dense.shape:
                 raise ValueError(f"geometry map: mask {tuple(pattern.shape)} must have the map's shape {tuple(dense.shape)}")
         flags = _GEOM_TRANSPOSED | (_GEOM_COLUMNS if want_columns else 0)
-        engine._check(self._lib.cd_geom_create_ex(dense.data_ptr(), engine._ptr(pattern), self.layers, self.rows, self.cols, flags,
-                                                  C.byref(handle), engine._stream()))
-        self.handle = handle
+        _check(self._lib.cd_geom_create_ex(dense.data_ptr(), _ptr(pattern), self.layers, self.rows, self.cols, flags,
+                                           C.byref(self.handle), _stream()))
 
     @classmethod
     def from_entries(cls, row_ptr, col_idx, val, layers: int, rows: int, cols: int, want_columns: bool = False,
@@ -81,7 +76,8 @@ class _PackedMap:
         """The same handle from the map's sparse entries (``map_entries``), without the dense tensor: ``cd_geom_create_csr``."""
         self = cls.__new__(cls)
         self.layers, self.rows, self.cols = int(layers), int(rows), int(cols)
-        self._lib = engine.load_library()
+        self._lib = load_library()
+        Handle.__init__(self, self._lib.cd_geom_destroy)
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
         col_idx, val = np.ascontiguousarray(col_idx, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float32)
         if row_ptr.shape != (self.layers * self.rows + 1,) or col_idx.shape != val.shape or col_idx.ndim != 1:
@@ -90,39 +86,32 @@ class _PackedMap:
         if col_idx.size < max(int(row_ptr[-1]), 0):
             raise ValueError(f"geometry map: row_ptr ends at {int(row_ptr[-1])}, {col_idx.size} entries given")
         flags = (_GEOM_TRANSPOSED if want_transposed else 0) | (_GEOM_COLUMNS if want_columns else 0)
-        handle = C.c_void_p()
-        engine._check(self._lib.cd_geom_create_csr(row_ptr.ctypes.data, col_idx.ctypes.data, val.ctypes.data, self.layers, self.rows,
-                                                   self.cols, flags, C.byref(handle), engine._stream()))
-        self.handle = handle
+        _check(self._lib.cd_geom_create_csr(row_ptr.ctypes.data, col_idx.ctypes.data, val.ctypes.data, self.layers, self.rows,
+                                            self.cols, flags, C.byref(self.handle), _stream()))
         return self
-
-    def __del__(self):
-        if getattr(self, "handle", None):
-            self._lib.cd_geom_destroy(self.handle)
-            self.handle = None
 
     def refresh(self, dense: torch.Tensor):
         """the packed values again from ``dense`` (a trainable map's live parameter)"""
-        dense = _to_dev32(dense)
+        dense = _upload(dense, torch.float32, "dense")
         if tuple(dense.shape) != (self.layers, self.rows, self.cols):
             raise ValueError(f"geometry map: expected ({self.layers}, {self.rows}, {self.cols}), got {tuple(dense.shape)}")
-        engine._check(self._lib.cd_geom_refresh(self.handle, dense.data_ptr(), engine._stream()))
+        _check(self._lib.cd_geom_refresh(self.handle, dense.data_ptr(), _stream()))
         self._held = dense  # (a converted copy must outlive the launch)
 
     def apply(self, x: torch.Tensor, scale: float, shift: float, affine_first: bool) -> torch.Tensor:
         """x (..., L, cols) -> (..., L, rows)"""
-        x = engine._dev32(x, "x")
+        x = _dev32(x, "x")
         if x.dim() < 2 or tuple(x.shape[-2:]) != (self.layers, self.cols):
             raise ValueError(f"geometry map: expected (..., {self.layers}, {self.cols}), got {tuple(x.shape)}")
         y = torch.empty(x.shape[:-1] + (self.rows,), dtype=torch.float32, device=x.device)
         if y.numel():
-            engine._check(self._lib.cd_geom_apply(self.handle, x.data_ptr(), y.data_ptr(), x.numel() // (self.layers * self.cols),
-                                                  float(scale), float(shift), int(affine_first), engine._stream()))
+            _check(self._lib.cd_geom_apply(self.handle, x.data_ptr(), y.data_ptr(), x.numel() // (self.layers * self.cols),
+                                           float(scale), float(shift), int(affine_first), _stream()))
         return y
 
     def apply_vjp(self, x, gy, scale: float, shift: float, affine_first: bool, want_dx: bool, want_dm: bool):
         """The gradients of ``apply`` for the cotangent gy (..., L, rows): (dx like x or None, dm (L, rows, cols) dense or None)"""
-        x, gy = engine._dev32(x, "x"), engine._dev32(gy, "gy")
+        x, gy = _dev32(x, "x"), _dev32(gy, "gy")
         if tuple(x.shape[-2:]) != (self.layers, self.cols) or gy.shape != x.shape[:-1] + (self.rows,):
             raise ValueError(f"geometry map gradient: x {tuple(x.shape)} and gy {tuple(gy.shape)} do not fit "
                              f"({self.layers}, {self.rows}, {self.cols})")
@@ -132,29 +121,27 @@ class _PackedMap:
         if n == 0:
             return dx, (dm.zero_() if want_dm else None)
         if want_dx or want_dm:
-            engine._check(self._lib.cd_geom_apply_vjp(self.handle, x.data_ptr(), gy.data_ptr(), engine._ptr(dx), engine._ptr(dm), n,
-                                                      float(scale), float(shift), int(affine_first), engine._stream()))
+            _check(self._lib.cd_geom_apply_vjp(self.handle, x.data_ptr(), gy.data_ptr(), _ptr(dx), _ptr(dm), n,
+                                               float(scale), float(shift), int(affine_first), _stream()))
         return dx, dm
 
     def decode_sparse(self, x: torch.Tensor, per_batch: bool, rand, seed: int, offset: int) -> torch.Tensor:
         """x (B, C, L, cols) -> (B, C, L, rows)"""
-        x = engine._dev32(x, "x")
+        x = _dev32(x, "x")
         if x.dim() != 4 or tuple(x.shape[-2:]) != (self.layers, self.cols):
             raise ValueError(f"sparse decoding: expected (batch, channels, {self.layers}, {self.cols}), got {tuple(x.shape)}")
         B, ch = int(x.shape[0]), int(x.shape[1])
         if rand is not None:
-            rand = engine._dev32(rand, "rand")
+            rand = _dev32(rand, "rand")
             if tuple(rand.shape) != (1 if per_batch else B, self.layers, self.rows, self.cols):
                 raise ValueError(f"sparse decoding: rand must be ({1 if per_batch else B}, {self.layers}, {self.rows}, "
                                  f"{self.cols}), got {tuple(rand.shape)}")
         y = torch.empty((B, ch, self.layers, self.rows), dtype=torch.float32, device=x.device)
         if not y.numel():
             return y
-        need = C.c_size_t()
-        engine._check(self._lib.cd_geom_sparse_workspace_bytes(self.handle, B, C.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device=x.device)
-        engine._check(self._lib.cd_geom_decode_sparse(self.handle, x.data_ptr(), y.data_ptr(), B, ch, int(per_batch), engine._ptr(rand),
-                                                      int(seed), int(offset), ws.data_ptr(), engine._stream()))
+        ws = torch.empty(_nbytes(self._lib.cd_geom_sparse_workspace_bytes, self.handle, B), dtype=torch.uint8, device=x.device)
+        _check(self._lib.cd_geom_decode_sparse(self.handle, x.data_ptr(), y.data_ptr(), B, ch, int(per_batch), _ptr(rand),
+                                               int(seed), int(offset), ws.data_ptr(), _stream()))
         return y
 
 
@@ -231,7 +218,7 @@ class _Map(torch.nn.Module):
         pm = self.packed()
         mat = self.mat if self.trainable and self.mat.requires_grad else None
         if torch.is_grad_enabled() and (mat is not None or (isinstance(x, torch.Tensor) and x.requires_grad)):
-            return _Apply.apply(engine._dev32(x, "x"), mat, pm, scale, shift, affine_first)
+            return _Apply.apply(_dev32(x, "x"), mat, pm, scale, shift, affine_first)
         return pm.apply(x, scale, shift, affine_first)
 
 
@@ -280,7 +267,7 @@ class Decoder(_Map):
             return self._apply_map(x, std, mean, affine_first=True)
         pm = self._sampled_map()
         if std != 1.0 or mean != 0.0:  # (every shipped HGCal constant set has embed_mean 0, embed_std 1)
-            x = engine._dev32(x, "x") * std + mean
+            x = _dev32(x, "x") * std + mean
         if rand is None and seed is None and offset is None:
             seed, offset = self.noise_seed, self.noise_offset
             self.noise_offset += (1 if sparse_per_batch else int(x.shape[0])) * pm.layers * pm.rows * pm.cols

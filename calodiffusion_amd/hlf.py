@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import engine
+from .abi import CdHlfDesc, Handle, _check, _dev32, _stream, load_library, require_gpu
 from .xml_handler import XMLHandler
 
 # columns of a cd_hlf_compute record
@@ -44,7 +44,7 @@ class HighLevelFeatures:
         self.E_tot = None
         self.E_layers, self.EC_etas, self.EC_phis, self.width_etas, self.width_phis = {}, {}, {}, {}, {}
         self.var_etas, self.var_phis, self.n_hits, self.max_voxel = {}, {}, {}, {}
-        self._handles = {}  # device index -> CdHlf handle: the geometry's tables live on the device they are used on
+        self._handles = {}  # device index -> abi.Handle of a CdHlf: the geometry's tables live on the device they are used on
         self._lib = None
 
     # layers that get centres and widths: an INDEX that is also among the XML ids (HighLevelFeatures.py:78-79)
@@ -60,31 +60,25 @@ class HighLevelFeatures:
         """The handle of the current device, created on first use there."""
         device = torch.cuda.current_device() if torch.cuda.is_available() else -1
         if device not in self._handles:
-            lib = engine.load_library()
-            engine.require_gpu()
+            lib = load_library()
+            require_gpu()
             n = len(self.bin_edges) - 1
             offsets = (C.c_int32 * (n + 1))(*[int(b) for b in self.bin_edges])
             centres = (C.c_int32 * n)(*[int(l in self.layers_with_centres) for l in range(n)])
             eta = np.ascontiguousarray(np.concatenate(self.eta_all_layers), dtype=np.float64)
             phi = np.ascontiguousarray(np.concatenate(self.phi_all_layers), dtype=np.float64)
             as_f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None  # noqa: E731
-            desc = engine.CdHlfDesc(C.sizeof(engine.CdHlfDesc), n, offsets, as_f64(eta), as_f64(phi), centres)
-            handle = C.c_void_p()
-            engine._check(lib.cd_hlf_create(C.byref(desc), C.byref(handle), engine._stream()))
-            self._lib, self._handles[device] = lib, handle
-        return self._handles[device]
+            desc = CdHlfDesc(C.sizeof(CdHlfDesc), n, offsets, as_f64(eta), as_f64(phi), centres)
+            owner = Handle(lib.cd_hlf_destroy)
+            _check(lib.cd_hlf_create(C.byref(desc), C.byref(owner.handle), _stream()))
+            self._lib, self._handles[device] = lib, owner
+        return self._handles[device].handle
 
     def close(self):
-        """Frees the device tables (they are created again on the next call)."""
-        handles, self._handles = getattr(self, "_handles", {}), {}
-        for handle in handles.values():
-            self._lib.cd_hlf_destroy(handle)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter teardown: the library may be gone before the last instance
-            pass
+        """Frees the device tables (they are created again on the next call; an instance that goes frees them by itself)."""
+        handles, self._handles = self._handles, {}
+        for owner in handles.values():
+            owner.close()
 
     def _launch(self, showers: torch.Tensor, threshold: float, out=None, hits=None):
         """(B, V) fp32 device tensor -> (B, R, 8) fp64 and (B, R) int32 tensors on its device (allocated here unless passed in),
@@ -95,8 +89,8 @@ class HighLevelFeatures:
             if out is None:
                 out = torch.empty((B, R, 8), dtype=torch.float64, device=showers.device)
                 hits = torch.empty((B, R), dtype=torch.int32, device=showers.device)
-            engine._check(self._lib.cd_hlf_compute(handle, showers.data_ptr(), B, float(threshold), out.data_ptr(), hits.data_ptr(),
-                                                   engine._stream()))
+            _check(self._lib.cd_hlf_compute(handle, showers.data_ptr(), B, float(threshold), out.data_ptr(), hits.data_ptr(),
+                                            _stream()))
         return out, hits
 
     def CalculateFeatures(self, data, threshold=0.0, chunk=16384):
@@ -135,7 +129,7 @@ class HighLevelFeatures:
         hits = np.empty((N, R), dtype=np.int32)
         if N:
             if isinstance(data, torch.Tensor) and data.is_cuda:
-                o, h = self._launch(engine._dev32(data.detach(), "data"), threshold)
+                o, h = self._launch(_dev32(data.detach(), "data"), threshold)
                 rec[:], hits[:] = o.cpu().numpy(), h.cpu().numpy()
             else:
                 self._device_handle()  # (raises here without a GPU, before any upload)

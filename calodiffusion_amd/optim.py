@@ -7,7 +7,7 @@ import ctypes as C
 
 import torch
 
-from . import engine
+from .abi import _check, _stream, load_library
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -15,7 +15,7 @@ class FusedAdam(torch.optim.Optimizer):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("FusedAdam: invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._lib = engine.load_library()
+        self._lib = load_library()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -45,10 +45,10 @@ class FusedAdam(torch.optim.Optimizer):
             arr = lambda xs: (C.c_void_p * n)(*[x.data_ptr() for x in xs])  # noqa: E731
             numel = (C.c_int64 * n)(*[p.numel() for p in ps])
             b1, b2 = group["betas"]
-            engine._check(self._lib.cd_adam_step(n, arr(ps), arr([p.grad for p in ps]), arr([self.state[p]["exp_avg"] for p in ps]),
-                                                 arr([self.state[p]["exp_avg_sq"] for p in ps]), numel, float(group["lr"]), float(b1),
-                                                 float(b2), float(group["eps"]), float(group["weight_decay"]), steps.pop(),
-                                                 engine._stream()))
+            _check(self._lib.cd_adam_step(n, arr(ps), arr([p.grad for p in ps]), arr([self.state[p]["exp_avg"] for p in ps]),
+                                          arr([self.state[p]["exp_avg_sq"] for p in ps]), numel, float(group["lr"]), float(b1),
+                                          float(b2), float(group["eps"]), float(group["weight_decay"]), steps.pop(),
+                                          _stream()))
             # cd_adam_step writes through raw pointers: tell torch (and UnetEngine.sync_weights, which keys its re-pack of the
             # plan's weight arena on the parameters' versions) that the tensors changed
             torch.autograd.graph.increment_version(ps)

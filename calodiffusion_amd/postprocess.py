@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import engine
+from .abi import _check, _ptr, _stream, load_library
 
 # normalisation constants of the reference (calodiffusion/utils/consts.py:82-116): data, not code
 DATASET_PARAMS = {
@@ -96,9 +96,9 @@ def _reverse_ds1(v, energy, layerE, gc, grid_form, c, max_deposit, ecut):
     out = torch.empty((B, rm.V), dtype=torch.float32, device="cuda")
     w = gc._fixed_weights()[1] if grid_form else None
     consts = (C.c_double * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(engine.load_library().cd_reverse_norm_ds1(rm.handle, engine._ptr(w), v.data_ptr(), energy.data_ptr(),
-                                                            engine._ptr(layerE), out.data_ptr(), B, consts, float(max_deposit),
-                                                            float(ecut), engine._stream()))
+    _check(load_library().cd_reverse_norm_ds1(rm.handle, _ptr(w), v.data_ptr(), energy.data_ptr(),
+                                              _ptr(layerE), out.data_ptr(), B, consts, float(max_deposit),
+                                              float(ecut), _stream()))
     return out
 
 
@@ -110,14 +110,14 @@ def ReverseNorm(voxels, e, hgcal=False, **kwargs):
 
 
 def _staged(v, energy, layerE, dims, c, max_deposit, alpha, layer_eps, stage):
-    lib = engine.load_library()
+    lib = load_library()
     B = v.shape[0]
     out = torch.empty((B, int(np.prod(dims))), dtype=torch.float32, device="cuda")
     consts = (C.c_float * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(lib.cd_reverse_norm_staged(v.data_ptr(), energy.data_ptr() if energy is not None else None,
-                                             layerE.data_ptr() if layerE is not None else None, out.data_ptr(), B,
-                                             (C.c_int32 * 3)(*dims), consts, float(max_deposit), 0.0, float(alpha), float(layer_eps),
-                                             int(stage), engine._stream()))
+    _check(lib.cd_reverse_norm_staged(v.data_ptr(), energy.data_ptr() if energy is not None else None,
+                                      layerE.data_ptr() if layerE is not None else None, out.data_ptr(), B,
+                                      (C.c_int32 * 3)(*dims), consts, float(max_deposit), 0.0, float(alpha), float(layer_eps),
+                                      int(stage), _stream()))
     return out
 
 
@@ -207,9 +207,9 @@ def ReverseNormCaloChall(voxels, e, emax=9999.0, emin=0.0001, config=None, shape
     if le is not None and tuple(le.shape) != (B, D + 1):
         raise ValueError("ReverseNorm: layerE must have shape (batch, 1 + layers)")
     out = torch.empty((B, D * H * W), dtype=torch.float32, device="cuda")
-    lib = engine.load_library()
+    lib = load_library()
     dims = (C.c_int32 * 3)(D, H, W)
     consts = (C.c_float * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(lib.cd_reverse_norm(v.data_ptr(), en.data_ptr(), le.data_ptr() if le is not None else None, out.data_ptr(), B,
-                                      dims, consts, float(max_deposit), float(ecut), engine._stream()))
+    _check(lib.cd_reverse_norm(v.data_ptr(), en.data_ptr(), le.data_ptr() if le is not None else None, out.data_ptr(), B,
+                               dims, consts, float(max_deposit), float(ecut), _stream()))
     return out.cpu().numpy(), energy

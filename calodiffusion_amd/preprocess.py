@@ -22,7 +22,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import engine
+from .abi import _check, _ptr, _stream, _upload, load_library
 from .postprocess import (DATASET1_PARAMS, DATASET_PARAMS, SHOWER_MAPS, ds1_geometry, refuse_uncovered_ds1,  # noqa: F401
                           refuse_uncovered_map)
 
@@ -41,14 +41,7 @@ def _refuse_uncovered(who, showerMap, dataset_num, orig_shape):
     refuse_uncovered_map(who, showerMap)
 
 
-def _device_f32(a, name):
-    """numpy array or tensor (host or device) -> contiguous fp32 device tensor; the values are not touched."""
-    if isinstance(a, torch.Tensor):
-        return a.detach().to(device="cuda", dtype=torch.float32).contiguous()
-    a = np.asarray(a)
-    if a.dtype == object:
-        raise TypeError("%s must be a numeric array" % name)
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+_device_f32 = lambda a, name: _upload(a, torch.float32, name)  # noqa: E731  (numpy array or tensor, host or device)
 
 
 def _run(shower, e, dims, showerMap, dataset_num, max_deposit, emin, emax, logE, shower_scale):
@@ -68,11 +61,11 @@ def _run(shower, e, dims, showerMap, dataset_num, max_deposit, emin, emax, logE,
     layerE = torch.empty((B, D + 1), dtype=torch.float32, device="cuda") if "layer" in showerMap else None
     e_out = torch.empty((B, 1), dtype=torch.float32, device="cuda")
     status = torch.empty((1,), dtype=torch.int32, device="cuda")
-    lib = engine.load_library()
+    lib = load_library()
     consts = (C.c_float * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(lib.cd_preprocess(v.data_ptr(), en.data_ptr(), out.data_ptr(), engine._ptr(layerE), e_out.data_ptr(),
-                                    status.data_ptr(), B, (C.c_int32 * 3)(D, H, W), consts, float(max_deposit), float(emin),
-                                    float(emax), int(bool(logE)), float(shower_scale), engine._stream()))
+    _check(lib.cd_preprocess(v.data_ptr(), en.data_ptr(), out.data_ptr(), _ptr(layerE), e_out.data_ptr(),
+                             status.data_ptr(), B, (C.c_int32 * 3)(D, H, W), consts, float(max_deposit), float(emin),
+                             float(emax), int(bool(logE)), float(shower_scale), _stream()))
     bad = int(status.item())
     if bad:
         raise ValueError("preprocess: shower %d (the last such row of this call) has no energy -- incident energy <= 0 or no "
@@ -101,10 +94,10 @@ def _run_ds1(shower, e, gc, grid_form, showerMap, dataset_num, max_deposit, emin
     status = torch.empty((1,), dtype=torch.int32, device="cuda")
     w = gc._fixed_weights()[0] if grid_form else None
     consts = (C.c_double * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(engine.load_library().cd_preprocess_ds1(rm.handle, engine._ptr(w), v.data_ptr(), en.data_ptr(), out.data_ptr(),
-                                                          engine._ptr(layerE), e_out.data_ptr(), status.data_ptr(), B, consts,
-                                                          float(max_deposit), float(emin), float(emax), int(bool(logE)),
-                                                          float(shower_scale), engine._stream()))
+    _check(load_library().cd_preprocess_ds1(rm.handle, _ptr(w), v.data_ptr(), en.data_ptr(), out.data_ptr(),
+                                            _ptr(layerE), e_out.data_ptr(), status.data_ptr(), B, consts,
+                                            float(max_deposit), float(emin), float(emax), int(bool(logE)),
+                                            float(shower_scale), _stream()))
     bad = int(status.item())
     if bad:
         raise ValueError("preprocess: shower %d (the last such row of this call) has no energy -- incident energy <= 0 or no "
@@ -242,7 +235,7 @@ def _run_hgcal(showers, gen_info, bins, showerMap, dataset_num, max_deposit, emi
     k = len(emin)
     if g.dim() != 2 or tuple(g.shape) != (B, k):
         raise ValueError("preprocess_hgcal: gen_info of %s for %d showers and %d EMIN / EMAX columns" % (tuple(g.shape), B, k))
-    lib = engine.load_library()
+    lib = load_library()
     handle, cells, stride, mean, std = None, A * R, A * R, 0.0, 1.0
     if conv is None:
         if v.numel() != B * L * A * R:
@@ -264,10 +257,10 @@ def _run_hgcal(showers, gen_info, bins, showerMap, dataset_num, max_deposit, emi
     e_out = torch.empty((B, k), dtype=torch.float32, device="cuda")
     status = torch.empty((1,), dtype=torch.int32, device="cuda")
     consts = (C.c_double * 6)(c["logit_mean"], c["logit_std"], c["totalE_mean"], c["totalE_std"], c["layers_mean"], c["layers_std"])
-    engine._check(lib.cd_preprocess_hgcal(handle, v.data_ptr(), stride, g.data_ptr(), k, out.data_ptr(), engine._ptr(layerE),
-                                          e_out.data_ptr(), status.data_ptr(), B, L, cells, A * R, consts, float(mean), float(std),
-                                          float(max_deposit), (C.c_double * k)(*emin), (C.c_double * k)(*emax),
-                                          float(shower_scale), engine._stream()))
+    _check(lib.cd_preprocess_hgcal(handle, v.data_ptr(), stride, g.data_ptr(), k, out.data_ptr(), _ptr(layerE),
+                                   e_out.data_ptr(), status.data_ptr(), B, L, cells, A * R, consts, float(mean), float(std),
+                                   float(max_deposit), (C.c_double * k)(*emin), (C.c_double * k)(*emax),
+                                   float(shower_scale), _stream()))
     bad = int(status.item())
     if bad:
         raise ValueError("preprocess_hgcal: shower %d (the last such row of this call) has an incident energy <= 0, NaN or inf; "

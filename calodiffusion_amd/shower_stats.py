@@ -34,7 +34,7 @@ import math
 import numpy as np
 import torch
 
-from . import engine
+from .abi import CdShowerStatsDesc, Handle, _check, _dev32, _ptr, _stream, load_library, require_gpu
 
 # columns of a cd_shower_stats_compute record and of its counts
 E, MAX, ER, ERR, ECOS, ESIN = range(6)
@@ -222,7 +222,7 @@ class ShowerStatistics:
         self.r_bin, self.a_bin, self.r_coord, self.angle = r_bin, a_bin, r_coord, angle
         self.n_rbins, self.n_abins = int(n_rbins), int(n_abins)
         self.n_layers, self.n_cells = r_bin.shape
-        self._handles = {}  # device index -> CdShowerStats handle
+        self._handles = {}  # device index -> abi.Handle of a CdShowerStats
         self._lib = None
 
     @classmethod
@@ -244,28 +244,22 @@ class ShowerStatistics:
         """The handle of the current device, created on first use there."""
         device = torch.cuda.current_device() if torch.cuda.is_available() else -1
         if device not in self._handles:
-            lib = engine.load_library()
-            engine.require_gpu()
+            lib = load_library()
+            require_gpu()
             i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
             f64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
-            desc = engine.CdShowerStatsDesc(C.sizeof(engine.CdShowerStatsDesc), self.n_layers, self.n_cells, self.n_rbins, self.n_abins,
-                                            i32(self.r_bin), i32(self.a_bin), f64(self.r_coord), f64(self.angle))
-            handle = C.c_void_p()
-            engine._check(lib.cd_shower_stats_create(C.byref(desc), C.byref(handle), engine._stream()))
-            self._lib, self._handles[device] = lib, handle
-        return self._handles[device]
+            desc = CdShowerStatsDesc(C.sizeof(CdShowerStatsDesc), self.n_layers, self.n_cells, self.n_rbins, self.n_abins,
+                                     i32(self.r_bin), i32(self.a_bin), f64(self.r_coord), f64(self.angle))
+            owner = Handle(lib.cd_shower_stats_destroy)
+            _check(lib.cd_shower_stats_create(C.byref(desc), C.byref(owner.handle), _stream()))
+            self._lib, self._handles[device] = lib, owner
+        return self._handles[device].handle
 
     def close(self):
-        """Frees the device tables (they are created again on the next call)."""
-        handles, self._handles = getattr(self, "_handles", {}), {}
-        for handle in handles.values():
-            self._lib.cd_shower_stats_destroy(handle)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter teardown: the library may be gone before the last instance
-            pass
+        """Frees the device tables (they are created again on the next call; an instance that goes frees them by itself)."""
+        handles, self._handles = self._handles, {}
+        for owner in handles.values():
+            owner.close()
 
     def _launch(self, showers, hit_threshold, sparsity_eps, profiles=True, out=None):
         """(B, L n) fp32 device tensor -> (records, counts, r_profile, a_profile) tensors on its device (allocated here unless
@@ -278,9 +272,9 @@ class ShowerStatistics:
                        torch.empty((B, self.n_layers, 2), dtype=torch.int32, device=dev),
                        torch.empty((B, self.n_rbins), dtype=torch.float64, device=dev) if profiles else None,
                        torch.empty((B, self.n_abins), dtype=torch.float64, device=dev) if profiles and self.n_abins else None)
-            engine._check(self._lib.cd_shower_stats_compute(handle, showers.data_ptr(), B, float(hit_threshold), float(sparsity_eps),
-                                                            out[0].data_ptr(), out[1].data_ptr(), engine._ptr(out[2]), engine._ptr(out[3]),
-                                                            engine._stream()))
+            _check(self._lib.cd_shower_stats_compute(handle, showers.data_ptr(), B, float(hit_threshold), float(sparsity_eps),
+                                                     out[0].data_ptr(), out[1].data_ptr(), _ptr(out[2]), _ptr(out[3]),
+                                                     _stream()))
         return out
 
     def compute(self, data, hit_threshold=1e-3, sparsity_eps=1e-6, chunk=16384):
@@ -308,7 +302,7 @@ class ShowerStatistics:
 
         if N:
             if isinstance(data, torch.Tensor) and data.is_cuda:
-                run(engine._dev32(data.detach(), "data").reshape(N, self.voxels), 0)
+                run(_dev32(data.detach(), "data").reshape(N, self.voxels), 0)
             else:
                 self._device_handle()  # (raises here without a GPU, before any upload)
                 host = (data.detach().numpy() if isinstance(data, torch.Tensor) else np.asarray(data)).reshape(N, self.voxels)

@@ -6,6 +6,7 @@ from typing import List, Literal, Sequence, Tuple
 import numpy as np
 import torch
 
+from .abi import _check, _ptr, _stream, load_library, require_gpu
 from .configs import LoadJson  # noqa: F401  (same name as the reference helper)
 
 # r-bin edges per DATASET_NUM (utils/utils.py:45-127); HGCal (>= 100) uses unit-width bins
@@ -78,9 +79,8 @@ def load_attr(type_: Literal["sampler", "loss"], algo_name: str):
 
 
 def _conserve(who: str, generated: torch.Tensor, mask, emin: float) -> torch.Tensor:
-    from . import engine
-    lib = engine.load_library()
-    engine.require_gpu()
+    lib = load_library()
+    require_gpu()
     if not isinstance(generated, torch.Tensor) or not generated.is_cuda:
         raise RuntimeError(f"{who}: generated must be a CUDA(ROCm) tensor: calodiffusion_amd computes on the GPU only")
     if generated.dtype != torch.float32 or not generated.is_contiguous() or generated.dim() < 1:
@@ -94,8 +94,8 @@ def _conserve(who: str, generated: torch.Tensor, mask, emin: float) -> torch.Ten
             raise ValueError(f"{who}: mask must be a tensor of generated's shape on its device")
         mask = (mask != 0).contiguous().view(torch.uint8)
     with torch.cuda.device(generated.device):
-        engine._check(lib.cd_threshold_conserve(generated.data_ptr(), engine._ptr(mask), generated.numel() // row_len, row_len,
-                                                float(emin), engine._stream()))
+        _check(lib.cd_threshold_conserve(generated.data_ptr(), _ptr(mask), generated.numel() // row_len, row_len,
+                                         float(emin), _stream()))
     return generated
 
 

@@ -1,11 +1,15 @@
 """CPU: the split of the binding into calodiffusion_amd/abi.py (the C ABI), ops.py (the primitive-op wrappers) and engine.py
-(the engines) -- ``engine.<name>`` still reaches every name other files use, as the same object as in its new home -- and the
-rules of abi.WorkspaceCache, which every owner of library workspaces keeps them in.  Needs neither the library nor a GPU."""
+(the engines) -- ``engine.<name>`` still reaches every name other files use, as the same object as in its new home, and the
+modules that only call the library import without the engines -- and the rules of what abi.py shares: WorkspaceCache, which
+every owner of library workspaces keeps them in, Handle, which every owner of a library handle is or holds, and the refusals
+of _upload.  Needs neither the library nor a GPU."""
 import subprocess
 import sys
 import weakref
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
 from calodiffusion_amd import abi, engine, ops
@@ -32,12 +36,73 @@ def test_engine_still_reaches_every_name_as_the_same_object():
     assert engine.WorkspaceCache is WorkspaceCache
 
 
-@pytest.mark.parametrize("module", ["abi", "ops"])
+@pytest.mark.parametrize("module", ["abi", "ops", "classifier", "evaluate", "geom1", "hgcal", "hlf", "optim", "postprocess", "preprocess",
+                                    "shower_stats", "utils"])
 def test_abi_and_ops_import_without_the_engines(module):
     code = (f"import sys, calodiffusion_amd.{module}; "
             "sys.exit(int('calodiffusion_amd.engine' in sys.modules))")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr or f"importing calodiffusion_amd.{module} imported calodiffusion_amd.engine"
+
+
+class _Destroy:
+    """Stands in for a cd_*_destroy: records the handles it is given."""
+
+    def __init__(self, fail=False):
+        self.seen, self.fail = [], fail
+
+    def __call__(self, handle):
+        self.seen.append(handle.value)
+        if self.fail:
+            raise RuntimeError("the library is gone")
+
+
+def test_a_handle_is_destroyed_once_and_never_while_null():
+    destroy = _Destroy()
+    h = abi.Handle(destroy)
+    assert not h.handle  # (null until a create call fills it)
+    h.close()
+    h.__del__()
+    assert destroy.seen == []  # (a failed create frees nothing)
+    h.handle.value = 0x1234  # what cd_*_create does through C.byref(h.handle)
+    h.close()
+    assert destroy.seen == [0x1234] and not h.handle
+    h.close()  # (twice is harmless)
+    h.__del__()
+    assert destroy.seen == [0x1234]
+
+
+def test_a_handle_going_away_frees_it_and_swallows_a_failing_destroy():
+    destroy = _Destroy()
+    h = abi.Handle(destroy)
+    h.handle.value = 7
+    del h
+    assert destroy.seen == [7]
+    failing = _Destroy(fail=True)
+    h = abi.Handle(failing)
+    h.handle.value = 9
+    h.__del__()  # (interpreter teardown: nothing propagates)
+    assert failing.seen == [9]
+    with pytest.raises(RuntimeError, match="gone"):
+        h.handle.value = 11
+        h.close()  # (an explicit close still reports)
+    assert not h.handle and failing.seen == [9, 11]
+
+
+def test_owners_of_a_handle_are_handles():
+    from calodiffusion_amd import generator, geom1, hgcal
+    for owner in (engine.UnetEngine, generator.Generator, geom1._RadialMap, hgcal._PackedMap):
+        assert issubclass(owner, abi.Handle) and "__del__" not in vars(owner), owner
+
+
+def test_upload_refusals_without_a_gpu(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)  # (what a machine without a GPU answers)
+    with pytest.raises(TypeError, match="shower must be a numeric array"):
+        abi._upload(np.array([1.0, None], dtype=object), torch.float32, "shower")
+    with pytest.raises(RuntimeError, match=r"convert_flat: calodiffusion_amd computes on the GPU only and torch.cuda.is_available\(\) is False"):
+        abi._upload(np.ones((2, 3)), torch.float32, "convert_flat", need_gpu=True)
+    with pytest.raises(RuntimeError, match="convert_flat"):  # (before the array is looked at, as geom1 always refused)
+        abi._upload(np.array([None], dtype=object), torch.float32, "convert_flat", need_gpu=True)
 
 
 def _sizer(n, calls):
